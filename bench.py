@@ -10,9 +10,13 @@ all-reduce over ranks (RCCL, only when --gpus > 1) and UpdateProposal.  Every
 chain-step does the full reference work: D normals through U, logL, Metropolis
 test, scalar adaptation and the second-moment fold.
 
-After the timed headline (N = 1 only, each with its own warm-up and HIP-event timing, none of it inside
-the headline's timed region) the other single-GPU workloads of BASELINE.json go into `extra`: config 2
-with the header-form TDummyLogLikelihood, config 3, config 4's per-GPU share, config 5.
+A plain run sets up, warms up, times --steps windows and prints the line.  Everything else it can measure
+runs only with --full, after the timed headline: the ESS of the adapted ensemble and, at N = 1, the other
+single-GPU workloads of BASELINE.json in `extra` (each with its own warm-up and HIP-event timing, none of it
+inside the headline's timed region: config 2 with the header-form TDummyLogLikelihood, config 3, config 4's
+per-GPU share, config 5) and the CPU baseline.  --dump-outputs DIR writes what the caller of the timed path
+holds after its last window as DIR/<name>.npy (rank 0's chains; the inputs are seeded, so two builds can be
+compared array for array).
 
 Prints ONE JSON line (rank 0).
 """
@@ -41,6 +45,30 @@ def _latest_traffic_file():
 
 
 TRAFFIC_FILE = _latest_traffic_file()   # the newest round's PMC summary (tools/profile_bench.sh + tools/summarize_pmc.py)
+
+
+DUMP_BYTES = 64 * 10**6           # --dump-outputs: at most 64 MB in all
+
+
+def dump_outputs(dirname, per_chain, shared, nchains, limit=DUMP_BYTES):
+    """--dump-outputs: one DIR/<name>.npy (float64) per array.  per_chain: arrays whose last axis is the chain; shared:
+    the rest.  If they would exceed `limit` bytes, the per-chain arrays keep a fixed sample of chains (seed 0, in
+    chain order), whose indices go to chain_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in shared.items()}
+    per = {k: np.asarray(v, dtype=np.float64) for k, v in per_chain.items()}
+    header = 1024                                                      # room for one .npy header
+    budget = limit - sum(v.nbytes for v in out.values()) - header * (len(out) + len(per) + 1)
+    per_chain_bytes = sum(v.nbytes for v in per.values()) // nchains
+    if per_chain_bytes * nchains > budget:
+        keep = max(0, min(nchains, budget // (per_chain_bytes + 8)))
+        idx = np.sort(np.random.default_rng(0).choice(nchains, keep, replace=False))
+        per = {k: np.ascontiguousarray(v[..., idx]) for k, v in per.items()}
+        out["chain_index"] = idx.astype(np.float64)
+    out.update(per)
+    for k, v in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+    return sorted(out)
 
 
 def bytes_per_chain_step(dim):
@@ -334,6 +362,11 @@ def bench_c5(args, pkg, torch, dist, rank, world, local, stream, leapfrog=20):
     fence()
     dt = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        q, momentum, logl = h.state()
+        dump_outputs(args.dump_outputs, {"accepted": q, "accepted_momentum": momentum, "accepted_loglikelihood": logl,
+                                         "mean_epsilon": h.lane("mean_epsilon")},
+                     {"covariance": h.covariance}, chains)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -390,9 +423,13 @@ def main():
     ap.add_argument("--chains", type=int, default=CHAINS_PER_GPU)
     ap.add_argument("--window", type=int, default=WINDOW)
     ap.add_argument("--fast", action="store_true", help="fused multiply-add arithmetic (not the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ess", action="store_true", help="skip the ESS trace after the timed region")
-    ap.add_argument("--no-extras", action="store_true", help="skip the other BASELINE configs after the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the ESS trace, the other BASELINE configs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the arrays of the last timed window to DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-ess", action="store_true", help="with --full: skip the ESS trace after the timed region")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other BASELINE configs after the headline")
     ap.add_argument("--frozen", action="store_true", help="diagnostic: frozen covariance, no moment fold")
     ap.add_argument("--dim", type=int, default=DIM, help="diagnostic: other dimension (not the headline)")
     ap.add_argument("--header-tdummy", action="store_true",
@@ -490,6 +527,10 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:   # (before the ESS trace below moves the chains on)
+        dump_outputs(args.dump_outputs, {"accepted": eng.GetAccepted(), "accepted_loglikelihood": eng.GetAcceptedLogLikelihood(),
+                                         "sigma": eng.lane("sigma"), "naccept": eng.lane("naccept")},
+                     {"covariance": eng.covariance, "decomposition": eng.decomposition}, args.chains)
     rccl_ranks = 1
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if args.native_comm else "cuda")
@@ -529,7 +570,7 @@ def main():
     # (definition of MakeAutocorrelation.C:127-148) pooled over all chains, Geyer's
     # initial positive sequence, minimum over dimensions.
     ess_per_chain_step = None
-    if rank == 0 and not args.no_ess and dim <= 63:   # (the trace of a D = 500 ensemble would not fit)
+    if args.full and rank == 0 and not args.no_ess and dim <= 63:   # (the trace of a D = 500 ensemble would not fit)
         try:
             ess_per_chain_step = measure_ess(eng, torch, dim)
         except Exception as exc:   # a diagnostic, never a reason to lose the bench line
@@ -584,7 +625,7 @@ def main():
                      "chain_steps_per_launch": per_launch},
     }
     eng.close()
-    if rank == 0 and world == 1 and not args.no_extras and args.config == "c2":
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.config == "c2":
         extra = {}
         rng = np.random.default_rng(0)
         try:
@@ -651,7 +692,7 @@ def main():
         except Exception as exc:   # never a reason to lose the headline
             extra["error"] = repr(exc)
         out["extra"] = extra
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(out), flush=True)

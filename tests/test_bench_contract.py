@@ -46,6 +46,65 @@ def test_bench_config_5_line(gpu):
     assert out["roofline"]["bound"] == "mfma" and out["roofline"]["frac"] > 0.0
 
 
+def _bench_line(args, tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=600,
+                       cwd=tmp_path)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_dumps_the_same_outputs_twice(gpu, tmp_path):
+    """A plain run (no --full) times the headline only; --dump-outputs writes the caller's arrays after the last timed
+    window, and two runs with the same arguments write the same bits."""
+    import numpy as np
+    args = ["--steps", "2", "--warmup", "1", "--chains", "4096"]
+    dumps = []
+    for k in range(2):
+        out = _bench_line(args + ["--dump-outputs", str(tmp_path / ("out%d" % k))], tmp_path)
+        assert out["steps"] == 2 and out["ms_per_step"] > 0.0 and out["unit"] == "chain-steps/s" and out["dtype"] == "f64"
+        assert "extra" not in out and "cpu_baseline" not in out and out["ess_per_chain_step"] is None
+        dumps.append({f[:-4]: np.load(tmp_path / ("out%d" % k) / f) for f in os.listdir(tmp_path / ("out%d" % k))})
+    a, b = dumps
+    assert sorted(a) == ["accepted", "accepted_loglikelihood", "covariance", "decomposition", "naccept", "sigma"]
+    assert a["accepted"].shape == (50, 4096) and a["accepted_loglikelihood"].shape == (4096,)
+    assert a["covariance"].shape == (50, 50) and a["decomposition"].shape == (50, 50)
+    assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in a.values())
+    assert 0 < a["naccept"].sum() <= 4096 * 3 * 256
+    assert sorted(b) == sorted(a) and all(np.array_equal(a[k], b[k]) for k in a)
+
+
+@pytest.mark.gpu
+def test_full_bench_run_keeps_the_ess(gpu, tmp_path):
+    """The ESS trace (like the extras and the CPU baseline) runs only under --full."""
+    out = _bench_line(["--steps", "2", "--warmup", "1", "--chains", "4096", "--full", "--no-extras", "--no-cpu-baseline"],
+                      tmp_path)
+    assert out["ess_per_chain_step"] is not None and out["ess_per_chain_step"] > 0.0
+    assert abs(out["ess_per_s"] - out["ess_per_chain_step"] * out["value"]) < 1e-9 * out["ess_per_s"]
+    assert "extra" not in out and "cpu_baseline" not in out
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_limit(tmp_path):
+    """--dump-outputs: over the size limit, the per-chain arrays keep the same seeded sample of chains every time."""
+    import numpy as np
+    import bench
+    x = np.arange(7 * 1000, dtype=np.float64).reshape(7, 1000)
+    names = bench.dump_outputs(str(tmp_path / "all"), {"x": x, "n": np.arange(1000, dtype=np.int32)}, {"c": np.eye(3)}, 1000)
+    assert names == ["c", "n", "x"] and np.array_equal(np.load(tmp_path / "all" / "x.npy"), x)
+    assert np.load(tmp_path / "all" / "n.npy").dtype == np.float64
+    for d in ("s0", "s1"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "n": np.arange(1000, dtype=np.int32)}, {"c": np.eye(3)}, 1000,
+                           limit=40000)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 40000
+    idx = np.load(tmp_path / "s0" / "chain_index.npy")
+    assert 0 < len(idx) < 1000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "s1" / "chain_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "s0" / "x.npy"), x[:, idx.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "s0" / "n.npy"), idx)
+
+
 # ---- `python bench.py --gpus N` launches its own ranks (no GPU needed for the logic) ----
 def test_rank_environments(smcmc):
     envs = smcmc.distributed.rank_environments(4, 29511, {"PATH": "/bin", "WORLD_SIZE": "9"})
