@@ -383,6 +383,22 @@ int smcmc_hmc_copy_positions(smcmc_hmc* h, double* dst_device);
 int smcmc_hmc_nchains_padded(const smcmc_hmc* h);
 int smcmc_hmc_read_lane_f64(smcmc_hmc* h, int field, double* out);
 int smcmc_hmc_read_lane_i32(smcmc_hmc* h, int field, int32_t* out);
+/* SMCMC_MODE_POOLED (default): the covariance-driven tuning pooled over the ensemble, as above.  SMCMC_MODE_PER_CHAIN:
+ * every chain keeps its own fAveragePoint / fEstimatedCovariance and runs UpdateCovariance + UpdateErrorMatrix
+ * (:665-858) after each of its steps, whatever is fixed (with a fixed step and count only the Trace / Orbit outputs
+ * move), on the device: chain c is, bit for bit, the reference chain on the stream (seed, chain_offset + c), and
+ * smcmc_hmc_step enqueues its steps without waiting on the device.  In that mode the sync interval and
+ * set_track_covariance have no effect, smcmc_hmc_sync is a no-op, reduce / export / import / apply_moments are
+ * SMCMC_ERR_LOGIC (nothing is pooled: shard by chain_offset), get_tuning / get_average_point / get_covariance report
+ * chain 0, and gradient type 2 (the covariant gradient) is SMCMC_ERR_UNSUPPORTED, whichever of type and mode is set
+ * first.  The central point (:391-395, 733-744) stays with the caller, as in pooled mode.  Per-chain state that does not
+ * fit in device memory fails Start with SMCMC_ERR_HIP.  Set before smcmc_hmc_start (SMCMC_ERR_LOGIC after it); other
+ * modes are SMCMC_ERR_INVALID. */
+int smcmc_hmc_set_mode(smcmc_hmc* h, int mode);
+int smcmc_hmc_get_mode(const smcmc_hmc* h);
+/* chain `chain`'s fAveragePoint [dim], fEstimatedCovariance [dim*dim] and tuning[10] in the layout of
+ * smcmc_hmc_get_tuning; any pointer may be NULL.  In SMCMC_MODE_POOLED the shared values. */
+int smcmc_hmc_read_chain_tuning(smcmc_hmc* h, int chain, double* average, double* covariance, double* tuning);
 
 /* ---- variable-at-a-time chains: TSimpleMCMC<L, TProposeVAATStep> ---------
  * N independent chains of sMCMC::TSimpleMCMC<L, sMCMC::TProposeVAATStep> (TProposeVAATStep.H:22-307, the proposal
@@ -442,6 +458,12 @@ int smcmc_selftest_detmath(int device, int kind, int n, const double* x, const d
 int smcmc_selftest_mfma(int device, int K, const double* a, const double* b, double* c);
 /* The same for v_mfma_f64_4x4x4_4b_f64 as the moment fold uses it: c[4][16] = sum_k a[4][k] b[k][16]. */
 int smcmc_selftest_mfma_strip(int device, int K, const double* a, const double* b, double* c);
+/* UpdateErrorMatrix's eigenvalue step (TSimpleHMC.H:760-830) on one covariance cov[dim*dim] (dim <= 512) with
+ * fEstimatedCovarianceTrace = est_trace: device >= 0 runs SMCMC_MODE_PER_CHAIN's device routine on that device,
+ * device < 0 the host routine of the pooled mode.  out[dim*dim + dim + 5]: the covariance after the repair loop
+ * (dim*dim), the eigenvalues of its last pass (dim), then max scale, min scale, the number of repair passes,
+ * fCurrentCovarianceTrace and fEstimatedOrbitLength. */
+int smcmc_selftest_hmc_error_matrix(int device, int dim, double est_trace, const double* cov, double* out);
 
 /* ---- posterior reducer: autocorrelation of a saved trace ----------------------
  * MakeAutocorrelation.C:108-148 defines a(lag) = (E[x_t x_(t-lag)] - mean^2) / var per dimension.

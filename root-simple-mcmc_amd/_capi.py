@@ -143,6 +143,9 @@ SIGNATURES = {
     "smcmc_hmc_nchains_padded": (C.c_int, [_H]),
     "smcmc_hmc_read_lane_f64": (C.c_int, [_H, C.c_int, _dp]),
     "smcmc_hmc_read_lane_i32": (C.c_int, [_H, C.c_int, _ip]),
+    "smcmc_hmc_set_mode": (C.c_int, [_H, C.c_int]),
+    "smcmc_hmc_get_mode": (C.c_int, [_H]),
+    "smcmc_hmc_read_chain_tuning": (C.c_int, [_H, C.c_int, _dp, _dp, _dp]),
     "smcmc_vaat_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(_H)]),
     "smcmc_vaat_destroy": (C.c_int, [_H]),
     "smcmc_vaat_last_error": (C.c_char_p, [_H]),
@@ -172,6 +175,7 @@ SIGNATURES = {
     "smcmc_selftest_detmath": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]),
     "smcmc_selftest_mfma": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp]),
     "smcmc_selftest_mfma_strip": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp]),
+    "smcmc_selftest_hmc_error_matrix": (C.c_int, [C.c_int, C.c_int, C.c_double, _dp, _dp]),
     "smcmc_autocorrelation_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                              C.c_void_p]),
 }

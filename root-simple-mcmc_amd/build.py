@@ -77,6 +77,17 @@ def _units(user_flag=None):
     return units
 
 
+def _compile_cost(unit):
+    """A rough rank of a unit's compile time: the step-kernel instances grow with their register dimension, the
+    checked and user-likelihood ones most (they carry the assembly listing check or the user's walk)."""
+    src, defs, _ = unit
+    if src != "smcmc_inst.hip":
+        return 40
+    dp = int(next((d.split("=")[1] for d in defs if d.startswith("-DSMCMC_DP=")), "0"))
+    like = int(next((d.split("=")[1] for d in defs if d.startswith("-DSMCMC_LIKE=")), "0"))
+    return dp + (30 if like == 3 else 0)
+
+
 _EXTRA = {"files": []}   # the user likelihood header, part of the stamps of the units built with it
 _STALE = []              # SMCMC_BUILD_ONLY: units linked although their sources changed
 
@@ -214,6 +225,8 @@ def build(jobs=None, verbose=False, user_likelihood=None, output=None, with_plai
         if u[2] not in seen:
             seen.add(u[2])
             todo.append(u)
+    # longest units first, so that no long compile starts last and runs alone at the end of the pool
+    todo.sort(key=_compile_cost, reverse=True)
     jobs = jobs or min(8, os.cpu_count() or 1)
     built = {}
     refused = []

@@ -7,7 +7,8 @@
 // ensemble: one step per launch, the accepted points folded into moment sums on the device
 // (smcmc_fold_kernel.hip.h), the pooled running covariance and UpdateErrorMatrix on the host
 // (smcmc_hmc_shared.hpp) every `sync_every` steps, the new step length / leapfrog count applied
-// per chain on the device.
+// per chain on the device.  SMCMC_MODE_PER_CHAIN keeps that tuning per chain instead, on the device after every step
+// (smcmc_hmc_perchain.hip.h): chain c is the reference chain, and no host work happens between steps.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,6 +23,7 @@
 #include "smcmc_hmc_mfma_kernel.hip.h"
 #include "smcmc_fold_ring.hip.h"
 #include "smcmc_hmc_shared.hpp"
+#include "smcmc_hmc_perchain.hip.h"
 
 using namespace smcmc;
 
@@ -61,6 +63,11 @@ struct smcmc_hmc {
     double* h_hscal = nullptr;     // pinned: {n, average trials, covariance trials, trace}
     bool host_stale = false;       // the device holds newer average / covariance than *shared
     bool shared_on_device = false; // hmc_push has run since the host last (re)initialised *shared
+    // SMCMC_MODE_PER_CHAIN: every chain's own running average / covariance and tuning scalars (smcmc_hmc_perchain.hip.h)
+    int mode = SMCMC_MODE_POOLED;
+    double *d_pc_avg = nullptr, *d_pc_exxt = nullptr, *d_pc_covdiag = nullptr, *d_pc_scal = nullptr, *d_pc_scratch = nullptr;
+    int32_t* d_pc_work = nullptr;
+    int pc_grid = 0;               // workgroups of hmc_pc_error_kernel
     std::string error;
 };
 
@@ -404,6 +411,108 @@ hipError_t hmc_dispatch(smcmc_hmc* h, const HmcParams& p) {
                        : launch_hmc<8, kPanelCW>(p, h->likelihood, h->stream);
 }
 
+// ---- SMCMC_MODE_PER_CHAIN ----
+bool hmc_per_chain(const smcmc_hmc* h) { return h->mode == SMCMC_MODE_PER_CHAIN; }
+
+// buffers of the per-chain tuning, allocated at the first Start in this mode
+int hmc_pc_buffers(smcmc_hmc* h) {
+    if (h->d_pc_scal) return SMCMC_OK;
+    const size_t D = (size_t)h->dim, NP = (size_t)h->npad;
+    // the error kernel's grid: enough workgroups to cover the CUs a few times over; a D x D image each beyond LDS
+    int grid = std::min(1024, h->nchains);
+    if (h->dim > kPcLdsDim) grid = std::min<size_t>(grid, std::max<size_t>(1, ((size_t)256 << 20) / (D * D * sizeof(double))));
+    h->pc_grid = std::max(1, grid);
+    if (!h->d_p0) HMC_TRY(h, hipMalloc(&h->d_p0, sizeof(double) * D * NP));
+    if (!h->d_qprev) HMC_TRY(h, hipMalloc(&h->d_qprev, sizeof(double) * D * NP));
+    HMC_TRY(h, hipMalloc(&h->d_pc_avg, sizeof(double) * D * NP));
+    HMC_TRY(h, hipMalloc(&h->d_pc_exxt, sizeof(double) * pc_npacked(h->dim) * NP));
+    HMC_TRY(h, hipMalloc(&h->d_pc_covdiag, sizeof(double) * D * NP));
+    HMC_TRY(h, hipMalloc(&h->d_pc_work, sizeof(int32_t) * (NP + 1)));
+    if (h->dim > kPcLdsDim) HMC_TRY(h, hipMalloc(&h->d_pc_scratch, sizeof(double) * D * D * (size_t)h->pc_grid));
+    HMC_TRY(h, hipMalloc(&h->d_pc_scal, sizeof(double) * kPcCount * NP));
+    return SMCMC_OK;
+}
+
+// the covariance part of Start (:236-266) for every chain: fAveragePoint = its own start point, the rest as HmcShared::start
+int hmc_pc_start(smcmc_hmc* h, const std::vector<double>& x) {
+    int st = hmc_pc_buffers(h);
+    if (st) {
+        h->error = "per-chain HMC tuning state does not fit in device memory: " + h->error;
+        return st;
+    }
+    const size_t D = (size_t)h->dim, NP = (size_t)h->npad;
+    HMC_TRY(h, hipMemcpyAsync(h->d_pc_avg, x.data(), sizeof(double) * D * NP, hipMemcpyHostToDevice, h->stream));
+    HMC_TRY(h, hipMemsetAsync(h->d_pc_exxt, 0, sizeof(double) * pc_npacked(h->dim) * NP, h->stream));
+    HMC_TRY(h, hipMemsetAsync(h->d_pc_covdiag, 0, sizeof(double) * D * NP, h->stream));
+    HMC_TRY(h, hipMemsetAsync(h->d_pc_work, 0, sizeof(int32_t) * (NP + 1), h->stream));
+    HMC_TRY(h, hipMemsetAsync(h->d_qprev, 0, sizeof(double) * D * NP, h->stream));
+    std::vector<double> scal((size_t)kPcCount * NP, 0.0);
+    for (size_t c = 0; c < NP; ++c) scal[(size_t)kPcEstTrace * NP + c] = (double)D;   // fEstimatedCovarianceTrace = dim
+    HMC_TRY(h, hipMemcpyAsync(h->d_pc_scal, scal.data(), sizeof(double) * scal.size(), hipMemcpyHostToDevice, h->stream));
+    HMC_TRY(h, hipStreamSynchronize(h->stream));   // the staging vectors go out of scope
+    return SMCMC_OK;
+}
+
+// UpdateCovariance + UpdateErrorMatrix (:337-341) of every chain after the step that just ran, on the stream
+int hmc_pc_update(smcmc_hmc* h) {
+    HmcPcParams q;
+    std::memset(&q, 0, sizeof(q));
+    const size_t NP = (size_t)h->npad;
+    q.nchains = h->nchains; q.npad = h->npad; q.dim = h->dim;
+    q.step_count = (int)h->step_count;
+    q.cov_window = h->shared->covWindow;
+    q.qprev = h->d_qprev;
+    q.contributes = h->d_lane_i32 + (size_t)kHmcLaneContributes * NP;
+    q.lane_f64 = h->d_lane_f64; q.lane_i32 = h->d_lane_i32;
+    q.avg = h->d_pc_avg; q.exxt = h->d_pc_exxt; q.covdiag = h->d_pc_covdiag; q.scal = h->d_pc_scal;
+    q.work = h->d_pc_work; q.scratch = h->d_pc_scratch;
+    const size_t np = pc_npacked(h->dim);
+    const unsigned ny = (unsigned)((np + 4 * kPcExxtRun - 1) / (4 * kPcExxtRun));
+    hipLaunchKernelGGL(hmc_pc_exxt_kernel, dim3(h->npad / kWave, ny), dim3(kWave, 4), 0, h->stream, q);
+    hipLaunchKernelGGL(hmc_pc_decide_kernel, dim3((h->nchains + 255) / 256), dim3(256), 0, h->stream, q);
+    hipLaunchKernelGGL(hmc_pc_error_kernel, dim3(h->pc_grid), dim3(kWave), 0, h->stream, q);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hfail(h, SMCMC_ERR_HIP, std::string("per-chain tuning launch: ") + hipGetErrorString(e));
+    return SMCMC_OK;
+}
+
+// chain c's fAveragePoint, fEstimatedCovariance and tuning scalars (any pointer may be null)
+int hmc_pc_read(smcmc_hmc* h, int c, double* average, double* covariance, double* tuning) {
+    if (!h->started || !h->d_pc_scal) return hfail(h, SMCMC_ERR_LOGIC, "the per-chain tuning starts with Start");
+    const int D = h->dim;
+    const size_t NP = (size_t)h->npad;
+    HMC_TRY(h, hipStreamSynchronize(h->stream));
+    double sc[kPcCount];
+    HMC_TRY(h, hipMemcpy2D(sc, sizeof(double), h->d_pc_scal + c, NP * sizeof(double), sizeof(double), kPcCount,
+                           hipMemcpyDeviceToHost));
+    if (tuning) std::copy(sc, sc + kPcTuningFields, tuning);
+    std::vector<double> avg((size_t)D);
+    if (average || covariance)
+        HMC_TRY(h, hipMemcpy2D(avg.data(), sizeof(double), h->d_pc_avg + c, NP * sizeof(double), sizeof(double), (size_t)D,
+                               hipMemcpyDeviceToHost));
+    if (average) std::copy(avg.begin(), avg.end(), average);
+    if (!covariance) return SMCMC_OK;
+    if (sc[kPcCovTrials] == 0.0) {                                       // Start's identity (:255-258)
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j < D; ++j) covariance[(size_t)i * D + j] = (i == j) ? 1.0 : 0.0;
+    } else if (sc[kPcCovState] != 0.0) {                                 // what the repair loop left (:793-808)
+        std::vector<double> dg((size_t)D);
+        HMC_TRY(h, hipMemcpy2D(dg.data(), sizeof(double), h->d_pc_covdiag + c, NP * sizeof(double), sizeof(double),
+                               (size_t)D, hipMemcpyDeviceToHost));
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j < D; ++j) covariance[(size_t)i * D + j] = (i == j) ? dg[i] : 0.0;
+    } else {                                                             // :689
+        std::vector<double> ex(pc_npacked(D));
+        HMC_TRY(h, hipMemcpy2D(ex.data(), sizeof(double), h->d_pc_exxt + c, NP * sizeof(double), sizeof(double), ex.size(),
+                               hipMemcpyDeviceToHost));
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j <= i; ++j)
+                covariance[(size_t)i * D + j] = covariance[(size_t)j * D + i] =
+                    ex[(size_t)i * (i + 1) / 2 + j] - avg[i] * avg[j];
+    }
+    return SMCMC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -468,6 +577,8 @@ int smcmc_hmc_destroy(smcmc_hmc* h) {
     (void)hipHostFree(h->h_hscal);
     (void)hipFree(h->d_fd_grad);
     (void)hipHostFree(h->h_moments);
+    (void)hipFree(h->d_pc_avg); (void)hipFree(h->d_pc_exxt); (void)hipFree(h->d_pc_covdiag); (void)hipFree(h->d_pc_scal);
+    (void)hipFree(h->d_pc_scratch); (void)hipFree(h->d_pc_work);
     delete h->shared;
     delete h;
     return SMCMC_OK;
@@ -542,6 +653,8 @@ int smcmc_hmc_set_gradient_type(smcmc_hmc* h, int type) {
     if (!h || type < 0 || type > 5) return SMCMC_ERR_INVALID;
     if (!h->exact && (type == 2 || type == 3 || type == 5))
         return hfail(h, SMCMC_ERR_UNSUPPORTED, "gradient types 2, 3 and 5 run in reference-order arithmetic only");
+    if (type == 2 && hmc_per_chain(h))
+        return hfail(h, SMCMC_ERR_UNSUPPORTED, "the covariant gradient (type 2) is not available in SMCMC_MODE_PER_CHAIN");
     h->gradient_type = type;
     return SMCMC_OK;
 }
@@ -552,8 +665,32 @@ int smcmc_hmc_set_track_covariance(smcmc_hmc* h, int on) {
     return SMCMC_OK;
 }
 int smcmc_hmc_moment_group(const smcmc_hmc* h) { return h ? h->slice_chains : 0; }
+int smcmc_hmc_set_mode(smcmc_hmc* h, int mode) {
+    if (!h) return SMCMC_ERR_INVALID;
+    if (mode != SMCMC_MODE_POOLED && mode != SMCMC_MODE_PER_CHAIN)
+        return hfail(h, SMCMC_ERR_INVALID, "HMC modes: SMCMC_MODE_POOLED, SMCMC_MODE_PER_CHAIN");
+    if (h->started) return hfail(h, SMCMC_ERR_LOGIC, "choose the mode before Start");
+    if (mode == SMCMC_MODE_PER_CHAIN && h->gradient_type == 2)
+        return hfail(h, SMCMC_ERR_UNSUPPORTED, "the covariant gradient (type 2) is not available in SMCMC_MODE_PER_CHAIN");
+    h->mode = mode;
+    return SMCMC_OK;
+}
+int smcmc_hmc_get_mode(const smcmc_hmc* h) { return h ? h->mode : -1; }
+int smcmc_hmc_read_chain_tuning(smcmc_hmc* h, int chain, double* average, double* covariance, double* tuning) {
+    if (!h || chain < 0 || chain >= h->nchains) return SMCMC_ERR_INVALID;
+    if (!hmc_per_chain(h)) {
+        int st = SMCMC_OK;
+        if (average) st = smcmc_hmc_get_average_point(h, average);
+        if (!st && covariance) st = smcmc_hmc_get_covariance(h, covariance);
+        if (!st && tuning) st = smcmc_hmc_get_tuning(h, tuning);
+        return st;
+    }
+    HMC_ON_DEVICE(h);
+    return hmc_pc_read(h, chain, average, covariance, tuning);
+}
 int smcmc_hmc_get_tuning(smcmc_hmc* h, double* out) {
     if (!h || !out) return SMCMC_ERR_INVALID;
+    if (hmc_per_chain(h) && h->started) return smcmc_hmc_read_chain_tuning(h, 0, nullptr, nullptr, out);
     const HmcShared& S = *h->shared;
     out[0] = S.curTrace; out[1] = S.orbitLength; out[2] = S.updateCount; out[3] = S.covTrials;
     out[4] = S.averageTrials; out[5] = S.stepsRemaining; out[6] = S.stepsSinceUpdate; out[7] = S.maxScale;
@@ -562,12 +699,14 @@ int smcmc_hmc_get_tuning(smcmc_hmc* h, double* out) {
 }
 int smcmc_hmc_get_average_point(smcmc_hmc* h, double* out) {
     if (!h || !out) return SMCMC_ERR_INVALID;
+    if (hmc_per_chain(h) && h->started) return smcmc_hmc_read_chain_tuning(h, 0, out, nullptr, nullptr);
     { int pst = hmc_pull(h); if (pst) return pst; }
     std::copy(h->shared->average.begin(), h->shared->average.end(), out);
     return SMCMC_OK;
 }
 int smcmc_hmc_get_covariance(smcmc_hmc* h, double* out) {
     if (!h || !out) return SMCMC_ERR_INVALID;
+    if (hmc_per_chain(h) && h->started) return smcmc_hmc_read_chain_tuning(h, 0, nullptr, out, nullptr);
     { int pst = hmc_pull(h); if (pst) return pst; }
     std::copy(h->shared->cov.begin(), h->shared->cov.end(), out);
     return SMCMC_OK;
@@ -673,6 +812,10 @@ int smcmc_hmc_start(smcmc_hmc* h, const double* x0, int broadcast) {
     std::vector<double> p0(D);
     for (int d = 0; d < D; ++d) p0[d] = x[(size_t)d * NP];
     h->shared->start(p0.data());
+    if (hmc_per_chain(h)) {
+        st = hmc_pc_start(h, x);
+        if (st) return st;
+    }
     h->shared_on_device = false;   // pushed again at the next pooled update
     h->host_stale = false;
     h->cov_dirty = true;
@@ -694,6 +837,19 @@ int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
         if (!h->exact) return hfail(h, SMCMC_ERR_UNSUPPORTED, "gradient types 2, 3 and 5 run in reference-order arithmetic only");
         int gst = hmc_generic_buffers(h);
         if (gst) return gst;
+    }
+    if (hmc_per_chain(h)) {
+        // every chain tunes itself after every step (:337-341), whatever is fixed; nothing waits on the device
+        for (int s = 0; s < nsteps; ++s) {
+            HmcParams p = hmc_params(h, 1, 0);
+            p.adaptive = 1;
+            hipError_t e = hmc_dispatch(h, p);
+            if (e != hipSuccess) return hfail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
+            h->step_count += 1u;
+            int st = hmc_pc_update(h);
+            if (st) return st;
+        }
+        return SMCMC_OK;
     }
     if (!hmc_tracking(h)) {
         // fixed step length and leapfrog count: the chains share nothing, one launch runs all the steps
@@ -735,7 +891,9 @@ int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
 
 // the pooled update now, whatever the interval (a partial window at the end of a run)
 int smcmc_hmc_sync(smcmc_hmc* h) {
-    if (!h || !h->started) return SMCMC_ERR_INVALID;
+    if (!h) return SMCMC_ERR_INVALID;
+    if (hmc_per_chain(h)) return SMCMC_OK;   // nothing is pooled
+    if (!h->started) return SMCMC_ERR_INVALID;
     HMC_ON_DEVICE(h);
     if (!h->d_gacc) return SMCMC_OK;
     return hmc_sync(h);
@@ -745,7 +903,9 @@ int smcmc_hmc_sync(smcmc_hmc* h) {
 int smcmc_hmc_moments_size(const smcmc_hmc* h) { return h ? (int)(((size_t)h->dim + 1) * ((size_t)h->dim + 2) / 2) : 0; }
 
 int smcmc_hmc_reduce_moments(smcmc_hmc* h) {
-    if (!h || !h->started) return SMCMC_ERR_INVALID;
+    if (!h) return SMCMC_ERR_INVALID;
+    if (hmc_per_chain(h)) return hfail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN pools no moments: shard by chain_offset");
+    if (!h->started) return SMCMC_ERR_INVALID;
     HMC_ON_DEVICE(h);
     int st = hmc_tracking_buffers(h);
     if (st) return st;
@@ -753,6 +913,7 @@ int smcmc_hmc_reduce_moments(smcmc_hmc* h) {
 }
 
 int smcmc_hmc_export_moments(smcmc_hmc* h, double* dst_device) {
+    if (h && hmc_per_chain(h)) return hfail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN pools no moments: shard by chain_offset");
     if (!h || !dst_device || !h->d_moments) return SMCMC_ERR_INVALID;
     HMC_ON_DEVICE(h);
     HMC_TRY(h, hipMemcpyAsync(dst_device, h->d_moments, sizeof(double) * (size_t)smcmc_hmc_moments_size(h), hipMemcpyDeviceToDevice,
@@ -761,6 +922,7 @@ int smcmc_hmc_export_moments(smcmc_hmc* h, double* dst_device) {
 }
 
 int smcmc_hmc_import_moments(smcmc_hmc* h, const double* src_device) {
+    if (h && hmc_per_chain(h)) return hfail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN pools no moments: shard by chain_offset");
     if (!h || !src_device || !h->d_moments) return SMCMC_ERR_INVALID;
     HMC_ON_DEVICE(h);
     HMC_TRY(h, hipMemcpyAsync(h->d_moments, src_device, sizeof(double) * (size_t)smcmc_hmc_moments_size(h), hipMemcpyDeviceToDevice,
@@ -769,6 +931,7 @@ int smcmc_hmc_import_moments(smcmc_hmc* h, const double* src_device) {
 }
 
 int smcmc_hmc_apply_moments(smcmc_hmc* h) {
+    if (h && hmc_per_chain(h)) return hfail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN pools no moments: shard by chain_offset");
     if (!h || !h->started || !h->d_moments) return SMCMC_ERR_INVALID;
     HMC_ON_DEVICE(h);
     return hmc_apply(h);
@@ -817,3 +980,43 @@ int smcmc_hmc_read_lane_i32(smcmc_hmc* h, int field, int32_t* out) {
 }
 
 }  // extern "C"
+
+// :760-830 on one covariance: device >= 0 the per-chain mode's device routine (hmc_pc_selftest_kernel), device < 0 the
+// host's HmcShared.  out: [dim*dim] covariance after the repair loop, [dim] eigenvalues of the last pass, max scale,
+// min scale, repair passes, trace, orbit length
+extern "C" int smcmc_selftest_hmc_error_matrix(int device, int dim, double est_trace, const double* cov, double* out) {
+    if (dim < 1 || dim > kPcMaxDim || !cov || !out) return SMCMC_ERR_INVALID;
+    const size_t D = (size_t)dim, nout = D * D + D + 5;
+    if (device < 0) {
+        HmcShared S(dim);
+        S.cov.assign(cov, cov + D * D);
+        S.estTrace = est_trace;
+        std::vector<double> eig(D);
+        int passes = 0;
+        S.scaleFromCovariance(eig, passes);
+        std::copy(S.cov.begin(), S.cov.end(), out);
+        std::copy(eig.begin(), eig.end(), out + D * D);
+        double* t = out + D * D + D;
+        t[0] = S.maxScale; t[1] = S.minScale; t[2] = passes; t[3] = S.curTrace; t[4] = S.orbitLength;
+        return SMCMC_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device >= ndev) return SMCMC_ERR_NO_DEVICE;
+    HmcDeviceGuard guard(device);
+    double *d_cov = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+    int st = SMCMC_OK;
+    if (hipMalloc(&d_cov, sizeof(double) * D * D) != hipSuccess || hipMalloc(&d_out, sizeof(double) * nout) != hipSuccess ||
+        hipMalloc(&d_scratch, sizeof(double) * D * D) != hipSuccess) {
+        st = SMCMC_ERR_HIP;
+    } else if (hipMemcpy(d_cov, cov, sizeof(double) * D * D, hipMemcpyHostToDevice) != hipSuccess) {
+        st = SMCMC_ERR_HIP;
+    } else {
+        hipLaunchKernelGGL(hmc_pc_selftest_kernel, dim3(1), dim3(kWave), 0, nullptr, dim, est_trace, (const double*)d_cov,
+                           d_scratch, d_out);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(out, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost) != hipSuccess)
+            st = SMCMC_ERR_HIP;
+    }
+    (void)hipFree(d_cov); (void)hipFree(d_out); (void)hipFree(d_scratch);
+    return st;
+}

@@ -125,6 +125,17 @@ public:
         stepsRemaining = 2 * D + stepCount;                                  // :760
         stepsSinceUpdate = 0;
         std::vector<double> eig((size_t)D);
+        int passes = 0;
+        scaleFromCovariance(eig, passes);
+        invert(cov, error);                                                  // :849-850
+        ++updateCount;
+    }
+
+    // :764-830: eigenvalues of `cov` (into eig, those of the last pass), the repair loop until they are all
+    // non-negative (`passes` repairs; cov holds the result), then fCurrentCovarianceTrace = fEstimatedCovarianceTrace,
+    // the max / min scale and the orbit length
+    void scaleFromCovariance(std::vector<double>& eig, int& passes) {
+        passes = 0;
         double maxS = 0.0, minS = 1E+20;                                     // :764-765
         for (;;) {                                                           // :766-809
             eigenvalues(cov, eig);
@@ -136,6 +147,7 @@ public:
                 if (e < 0) positive = false;
             }
             if (positive) break;
+            ++passes;
             for (int i = 0; i < D; ++i) {
                 double r = estTrace * 1E-6;
                 r /= D;
@@ -157,8 +169,6 @@ public:
         orbitLength = 2.0 * 3.14 * maxS;                                     // :830
         maxScale = maxS;
         minScale = minS;
-        invert(cov, error);                                                  // :849-850
-        ++updateCount;
     }
 
 private:

@@ -466,6 +466,22 @@ def selftest_mfma(a, b, device=0):
     return c
 
 
+def selftest_hmc_error_matrix(cov, est_trace, device=0):
+    """UpdateErrorMatrix's eigenvalue step (TSimpleHMC.H:760-830) on one covariance: device >= 0 the per-chain HMC mode's
+    device routine, device < 0 the pooled mode's host routine.  Returns (covariance after the repair loop, eigenvalues
+    of the last pass, dict of max_scale, min_scale, passes, trace, orbit)."""
+    lib = _capi.load()
+    cov = _f64(cov)
+    d = cov.shape[0]
+    out = np.zeros(d * d + d + 5)
+    st = lib.smcmc_selftest_hmc_error_matrix(int(device), d, float(est_trace), _ptr(cov), _ptr(out))
+    if st != _capi.OK:
+        raise SmcmcError(st, lib.smcmc_status_string(st).decode())
+    tail = out[d * d + d:]
+    return (out[:d * d].reshape(d, d), out[d * d:d * d + d],
+            dict(zip(("max_scale", "min_scale", "passes", "trace", "orbit"), tail)))
+
+
 def selftest_mfma_strip(a, b, device=0):
     lib = _capi.load()
     a, b = _f64(a), _f64(b)
@@ -480,10 +496,11 @@ class HmcEngine:
     """N sMCMC::TSimpleHMC chains (reference TSimpleHMC.H:119-973) with the analytic gradient of a device
     likelihood.  SetMeanEpsilon(negative) + SetLeapFrog(n) fix the step: independent chains, many steps per launch.
     Otherwise every chain retunes its own step length and leapfrog count (:302-345) and the covariance-driven
-    retuning (:665-858) is pooled over the ensemble every SetSyncInterval steps."""
+    retuning (:665-858) is pooled over the ensemble every SetSyncInterval steps (mode=MODE_POOLED, the default) or
+    kept by every chain for itself after each step, as the reference chain does (mode=MODE_PER_CHAIN)."""
 
     def __init__(self, dim, nchains=1, likelihood=LIKE_ISO_GAUSS, likelihood_params=None, seed=20240607,
-                 chain_offset=0, device=0, stream=None, exact=True, library=None):
+                 chain_offset=0, device=0, stream=None, exact=True, library=None, mode=MODE_POOLED):
         # library: path of a build that carries a user likelihood (LIKE_USER as an HMC target through gradient type 2 / 3 / 5)
         self._lib = _capi.load(library)
         self.dim, self.nchains = int(dim), int(nchains)
@@ -503,6 +520,8 @@ class HmcEngine:
             self._check(self._lib.smcmc_hmc_set_stream(self._h, C.c_void_p(int(stream))))
         if not exact:
             self._check(self._lib.smcmc_hmc_set_exact_arithmetic(self._h, 0))
+        if mode != MODE_POOLED:
+            self.SetMode(mode)
 
     def _check(self, st):
         if st != _capi.OK:
@@ -545,6 +564,20 @@ class HmcEngine:
 
     def GetGradientType(self): return int(self._lib.smcmc_hmc_get_gradient_type(self._h))
     def sync(self): self._check(self._lib.smcmc_hmc_sync(self._h))
+
+    def SetMode(self, mode):
+        """MODE_POOLED or MODE_PER_CHAIN, before Start."""
+        self._check(self._lib.smcmc_hmc_set_mode(self._h, int(mode)))
+
+    def GetMode(self): return int(self._lib.smcmc_hmc_get_mode(self._h))
+
+    def chain_tuning(self, c):
+        """(fAveragePoint, fEstimatedCovariance, tuning dict) of chain c (MODE_PER_CHAIN: its own; else the shared ones)."""
+        avg = np.zeros(self.dim)
+        cov = np.zeros((self.dim, self.dim))
+        tun = np.zeros(len(_capi.HMC_TUNING))
+        self._check(self._lib.smcmc_hmc_read_chain_tuning(self._h, int(c), _ptr(avg), _ptr(cov), _ptr(tun)))
+        return avg, cov, dict(zip(_capi.HMC_TUNING, tun))
 
     # the pooled update in pieces (a sharded ensemble adds the ranks' moment vectors between export and import)
     @property
