@@ -72,7 +72,8 @@ typedef enum {
                                decomposition ([k][chain] columns in device memory), runs UpdateState every step
                                (:1721-1831, the covariance loop of :1795-1820 included) and UpdateProposal when its own
                                --fNextUpdate < 1 on an accepted step (:1824-1826).  Every chain is bit for bit the
-                               reference chain on its random stream.  dim <= 63, reference-order arithmetic, Gaussian
+                               reference chain on its random stream.  dim <= 63 (up to smcmc_max_perchain_dim() with
+                               SMCMC_P_PERCHAIN_WORKGROUP = 1 set first), reference-order arithmetic, Gaussian
                                proposals in every dimension; memory 12 dim (dim + 1) + 32 dim bytes per chain.
                                The shared getters (centre, covariance, decomposition, trials, trace) answer for
                                chain 0, the setters act on every chain; smcmc_read_chain_proposal reads any chain. */
@@ -122,6 +123,15 @@ typedef enum {
                                          * bits either way.  Every built-in likelihood runs on both; SMCMC_LIKE_USER (a library
                                          * built with a user likelihood) on the per-wavefront kernel only, whatever is set
                                          * here.  Reads back what runs. */
+    SMCMC_P_PERCHAIN_WORKGROUP = 26,    /* SMCMC_MODE_PER_CHAIN: 1 = one chain per WORKGROUP of 512 threads (the chain's covariance
+                                         * and decomposition in registers for a whole launch), the kernel that serves
+                                         * 1 <= dim <= smcmc_max_perchain_dim(); set it before smcmc_set_mode to ask for the mode
+                                         * above dim 63 (the O(D^2) images of the mode are then D^2 doubles per chain and more).
+                                         * 0 (default): the two kernels of SMCMC_P_PERCHAIN_WAVE, dim <= 63.  Same images, same
+                                         * bits: at dim <= 63 the choice may change between launches; above 63 setting 0 again on a
+                                         * per-chain engine is SMCMC_ERR_UNSUPPORTED.  Every built-in likelihood; SMCMC_LIKE_USER
+                                         * when the user header defines SMCMC_USER_LIKELIHOOD_ANY_DIM.  Reads back 1 exactly when
+                                         * this kernel is what runs (SMCMC_P_PERCHAIN_WAVE then reads back 0). */
     SMCMC_P_COUNT_
 } smcmc_param;
 
@@ -174,6 +184,7 @@ const char* smcmc_status_string(int status);
 int smcmc_version(void);
 int smcmc_max_register_dim(void);   /* largest dim of the register-resident kernels (63) */
 int smcmc_max_dim(void);            /* largest dim any kernel covers (512) */
+int smcmc_max_perchain_dim(void);   /* largest dim of SMCMC_MODE_PER_CHAIN (SMCMC_P_PERCHAIN_WORKGROUP = 1) */
 /* hipStream_t to launch on (NULL = default stream). */
 int smcmc_set_stream(smcmc_engine* h, void* hip_stream);
 
@@ -230,7 +241,8 @@ int smcmc_step(smcmc_engine* h, int nsteps, int metropolis);
  * [0, dim) fAccepted, [dim, 2 dim) fProposed, [2 dim, 3 dim) the diagonal of the chain's covariance (GetCovarianceTrace,
  * TSimpleMCMC.H:961-967, is its sum in index order: the reader adds it up; SMCMC_REC_COVARIANCE_TRACE itself is 0), then
  * the scalars of smcmc_record_field.  SMCMC_MODE_PER_CHAIN with the
- * one-chain-per-wavefront kernel (SMCMC_P_PERCHAIN_WAVE); SMCMC_ERR_UNSUPPORTED otherwise.  include/TSimpleMCMC_amd.H
+ * one-chain-per-wavefront kernel (SMCMC_P_PERCHAIN_WAVE) or the one-chain-per-workgroup kernel
+ * (SMCMC_P_PERCHAIN_WORKGROUP); SMCMC_ERR_UNSUPPORTED otherwise.  include/TSimpleMCMC_amd.H
  * runs Step() ahead with it (TSimpleMCMC.H:370-496 one call at a time is one launch and three read-backs per step). */
 typedef enum {
     SMCMC_REC_LOGL = 0, SMCMC_REC_LOGL_PROPOSED, SMCMC_REC_STEP_RMS, SMCMC_REC_LAST_ACCEPT, SMCMC_REC_TRIALS,

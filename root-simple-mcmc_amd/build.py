@@ -51,11 +51,13 @@ def _units(user_flag=None):
     hmc = ("smcmc_hmc_engine.hip", [user_flag], "hmc_engine_user") if user_flag else ("smcmc_hmc_engine.hip", [], "hmc_engine")
     wave = (("smcmc_perchain_wave_inst.hip", [user_flag], "perchain_wave_user") if user_flag
             else ("smcmc_perchain_wave_inst.hip", [], "perchain_wave"))
+    wg = (("smcmc_perchain_wg_inst.hip", [user_flag], "perchain_wg_user") if user_flag
+          else ("smcmc_perchain_wg_inst.hip", [], "perchain_wg"))
     units = [engine, ("smcmc_selftest.hip", [], "selftest"), ("smcmc_autocorr.hip", [], "autocorr"),
              hmc, ("smcmc_hmc_mfma_inst.hip", [], "hmc_mfma"),
              vaat, ("smcmc_vaat_large.hip", [], "vaat_large"),
              ("smcmc_pooled_update.hip", [], "pooled_update"), ("smcmc_perchain_inst.hip", [], "perchain"),
-             wave,
+             wave, wg,
              ("smcmc_panel_mfma_inst.hip", [], "panel_mfma"), ("smcmc_fold_inst.hip", [], "fold")]
     for dp in dp_list():
         for like in LIKELIHOODS:
@@ -81,6 +83,8 @@ def _compile_cost(unit):
     """A rough rank of a unit's compile time: the step-kernel instances grow with their register dimension, the
     checked and user-likelihood ones most (they carry the assembly listing check or the user's walk)."""
     src, defs, _ = unit
+    if src == "smcmc_perchain_wg_inst.hip":
+        return 200        # the largest unit: start it first
     if src != "smcmc_inst.hip":
         return 40
     dp = int(next((d.split("=")[1] for d in defs if d.startswith("-DSMCMC_DP=")), "0"))
@@ -135,13 +139,35 @@ def _compile(unit):
     if src in CHECKED_SOURCES and _has_assembly_reads(defs):
         _compile_checked(src, defs, name, obj)
     else:
-        cmd = [HIPCC] + FLAGS + defs + ["-c", os.path.join(CSRC, src), "-o", obj]
+        usage = src in NO_SCRATCH_SOURCES
+        cmd = [HIPCC] + FLAGS + defs + (["-Rpass-analysis=kernel-resource-usage"] if usage else []) + \
+            ["-c", os.path.join(CSRC, src), "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {name}:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
+        if usage:
+            _check_no_scratch(name, obj, r.stderr)
     with open(stamp_file, "w") as f:
         f.write(stamp)
     return obj, True
+
+
+# Translation units whose kernels hold a chain's state in registers for a whole launch: every kernel in them must use
+# no scratch (private segment), which the compiler's resource report (-Rpass-analysis=kernel-resource-usage) states
+# per kernel.  A unit that spills is refused, not built.
+NO_SCRATCH_SOURCES = ("smcmc_perchain_wg_inst.hip",)
+
+
+def _check_no_scratch(name, obj, remarks):
+    kernels = re.findall(r"remark: Function Name: (\S+)", remarks)
+    scratch = [int(v) for v in re.findall(r"remark:\s+ScratchSize \[bytes/lane\]: (\d+)", remarks)]
+    if not kernels or len(kernels) != len(scratch):
+        os.remove(obj)
+        raise RuntimeError(f"{name}: no kernel resource report to check")
+    bad = [(k, b) for k, b in zip(kernels, scratch) if b != 0]
+    if bad:
+        os.remove(obj)
+        raise RuntimeError(f"{name}: kernels that use scratch: " + ", ".join(f"{k} ({b} B/lane)" for k, b in bad))
 
 
 # Translation units whose kernels place LDS reads and their waits by hand (inline assembly): compiled with the

@@ -23,6 +23,7 @@
 #include "smcmc_fold_ring.hip.h"
 #include "smcmc_perchain_kernel.hip.h"
 #include "smcmc_perchain_wave.hip.h"
+#include "smcmc_perchain_wg.hip.h"
 #include "smcmc_proposal.hpp"
 
 using namespace smcmc;
@@ -142,6 +143,7 @@ struct smcmc_engine {
     bool pc_frozen = false;        // SMCMC_P_COVARIANCE_FROZEN
     bool pc_broken = false;        // a per-chain launch ended in an error with the chains part-way: Start / Restore again
     int pc_wave = -1;              // SMCMC_P_PERCHAIN_WAVE: -1 automatic, 0 / 1 one chain per lane / per wavefront
+    bool pc_wg = false;            // SMCMC_P_PERCHAIN_WORKGROUP: one chain per workgroup (dim <= smcmc::kWgMaxDim)
     smcmc::PerChainRecord pc_rec = {nullptr, 0, 0};   // the per-step record of the launch in progress (smcmc_step_recorded)
     double* d_pc_rec = nullptr;    // its device buffer
     double* d_pc_stage = nullptr;  // the fallback ladder's staging records (pc_host_ladder), allocated at the first ladder
@@ -674,9 +676,6 @@ int ensure_ring(smcmc_engine* h) {
         hipMalloc(&h->d_ring_logl, sizeof(double) * (size_t)h->npad * steps) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipFree(h->d_ring); (void)hipFree(h->d_ring_logl);
-    (void)hipFree(h->d_pc_rec);
-    for (int k = 0; k < 8; ++k) (void)hipFree(h->snap[k]);
-    smcmc::fold_ring_release(h->fold);
         h->d_ring = nullptr; h->d_ring_logl = nullptr;
         h->ring_steps = 0;
         return SMCMC_OK;
@@ -913,12 +912,18 @@ bool pc_use_wave(const smcmc_engine* h) {
     return true;     // measured faster at every ensemble size, 1 to 65 536 chains (profiles/r04_notes.md)
 }
 
+// One chain per workgroup (smcmc_perchain_wg.hip.h) when SMCMC_P_PERCHAIN_WORKGROUP asks for it: the only kernel above
+// dim 63; at dim <= 63 it shares the images of the two others.
+bool pc_use_wg(const smcmc_engine* h) { return h->pc_wg && smcmc::perchain_wg_serves(h->likelihood); }
+
 int pc_run(smcmc_engine* h, PerChainParams q) {
-    const bool wave = pc_use_wave(h);
-    if (h->pc_rec.rec && !wave)
+    const bool wg = pc_use_wg(h);
+    const bool wave = !wg && pc_use_wave(h);
+    if (h->pc_rec.rec && !wave && !wg)
         return fail(h, SMCMC_ERR_UNSUPPORTED, "a per-step record needs the one-chain-per-wavefront kernel (SMCMC_P_PERCHAIN_WAVE)");
     for (int round = 0; round < 1000; ++round) {
-        const hipError_t e = wave ? smcmc::launch_perchain_wave(q, h->pc_rec, h->likelihood, h->stream)
+        const hipError_t e = wg ? smcmc::launch_perchain_wg(q, h->pc_rec, h->likelihood, h->stream)
+                           : wave ? smcmc::launch_perchain_wave(q, h->pc_rec, h->likelihood, h->stream)
                                   : launch_perchain(q, h->likelihood, h->stream);
         if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("per-chain kernel launch: ") + hipGetErrorString(e));
         int flagged = 0;
@@ -934,12 +939,19 @@ int pc_run(smcmc_engine* h, PerChainParams q) {
     return fail(h, SMCMC_ERR_RUNTIME, "per-chain update: the fallback ladder does not converge");
 }
 
+// the dimensions SMCMC_MODE_PER_CHAIN serves: <= 63, or up to smcmc::kWgMaxDim on the one-chain-per-workgroup kernel
+bool pc_dim_served(const smcmc_engine* h) {
+    if (!h->panel_w && h->dim <= kPcMaxDim) return true;
+    return pc_use_wg(h) && h->dim <= smcmc::kWgMaxDim;
+}
+
 int pc_check_supported(smcmc_engine* h) {
-    if (h->panel_w || h->dim > kPcMaxDim)
-        return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN serves dim <= 63");
+    if (!pc_dim_served(h))
+        return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN serves dim <= 63 (up to smcmc_max_perchain_dim() with "
+                                              "SMCMC_P_PERCHAIN_WORKGROUP = 1)");
     if (!h->exact)
         return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN runs in reference-order arithmetic (SMCMC_P_EXACT_ARITHMETIC = 1)");
-    if (h->likelihood == SMCMC_LIKE_USER && !smcmc::perchain_wave_serves(SMCMC_LIKE_USER))   // (the one-chain-per-wavefront kernel only)
+    if (h->likelihood == SMCMC_LIKE_USER && !smcmc::perchain_wave_serves(SMCMC_LIKE_USER) && !pc_use_wg(h))   // (not the per-lane kernel)
         return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN serves the built-in likelihoods");
     for (int d = 0; d < h->dim; ++d)
         if (h->prop->ptype[d] != 0)
@@ -1178,6 +1190,7 @@ extern "C" {
 
 int smcmc_version(void) { return 100; }
 int smcmc_max_register_dim(void) { return kDPList[kNumDP - 1]; }
+int smcmc_max_perchain_dim(void) { return smcmc::kWgMaxDim; }
 int smcmc_max_dim(void) { return 8 * kPanelCW; }
 
 const char* smcmc_status_string(int status) {
@@ -1289,6 +1302,13 @@ int smcmc_destroy(smcmc_engine* h) {
     (void)hipFree(h->d_ring); (void)hipFree(h->d_ring_logl);
     (void)hipFree(h->d_pc_cov); (void)hipFree(h->d_pc_ut); (void)hipFree(h->d_pc_centre); (void)hipFree(h->d_pc_last);
     (void)hipFree(h->d_pc_tmpl); (void)hipFree(h->d_pc_flag); (void)hipFree(h->d_pc_stage); (void)hipFree(h->d_pc_stage_chains);
+    (void)hipFree(h->d_pc_rec);
+    h->d_pc_rec = nullptr;
+    for (int k = 0; k < 8; ++k) {
+        (void)hipFree(h->snap[k]);
+        h->snap[k] = nullptr;
+    }
+    smcmc::fold_ring_release(h->fold);
     (void)hipHostFree(h->h_scal);
     if (h->status_event) (void)hipEventDestroy(h->status_event);
     delete h->prop;
@@ -1319,8 +1339,9 @@ int smcmc_set_mode(smcmc_engine* h, int mode) {
     if (!h || (mode != SMCMC_MODE_FROZEN && mode != SMCMC_MODE_POOLED && mode != SMCMC_MODE_PER_CHAIN)) return SMCMC_ERR_INVALID;
     if (h->started && mode != h->mode && (mode == SMCMC_MODE_PER_CHAIN || h->mode == SMCMC_MODE_PER_CHAIN))
         return fail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN is chosen before Start");
-    if (mode == SMCMC_MODE_PER_CHAIN && (h->panel_w || h->dim > kPcMaxDim))
-        return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN serves dim <= 63");
+    if (mode == SMCMC_MODE_PER_CHAIN && !pc_dim_served(h))
+        return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN serves dim <= 63 (up to smcmc_max_perchain_dim() with "
+                                              "SMCMC_P_PERCHAIN_WORKGROUP = 1)");
     h->mode = mode;
     h->prop->covFrozen = (mode == SMCMC_MODE_FROZEN);
     return SMCMC_OK;
@@ -1427,6 +1448,11 @@ int smcmc_set_param(smcmc_engine* h, int which, double v) {
             return (per_chain(h) && h->started) ? broadcast_lane_f64(h, SMCMC_LANE_CENTER_TRIALS, v) : SMCMC_OK;
         case SMCMC_P_COVARIANCE_FROZEN: h->pc_frozen = (v != 0.0); return SMCMC_OK;
         case SMCMC_P_PERCHAIN_WAVE: h->pc_wave = (v < 0.0) ? -1 : (v != 0.0 ? 1 : 0); return SMCMC_OK;
+        case SMCMC_P_PERCHAIN_WORKGROUP:
+            if (v == 0.0 && per_chain(h) && (h->panel_w || h->dim > kPcMaxDim))
+                return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN above dim 63 runs on the one-chain-per-workgroup kernel");
+            h->pc_wg = (v != 0.0);
+            return SMCMC_OK;
         case SMCMC_P_DENSE_QUADFORM:
             h->dense_quadform = (v != 0.0);
             return (h->started && h->likelihood == SMCMC_LIKE_QUADFORM) ? upload_like_csr(h) : SMCMC_OK;
@@ -1540,7 +1566,8 @@ int smcmc_get_param(smcmc_engine* h, int which, double* out) {
         case SMCMC_P_OVERLAP_UPDATE: *out = h->overlap_update ? 1.0 : 0.0; break;
         case SMCMC_P_COVARIANCE_FROZEN: *out = (h->pc_frozen || h->mode == SMCMC_MODE_FROZEN) ? 1.0 : 0.0; break;
         case SMCMC_P_DENSE_QUADFORM: *out = (h->dense_quadform || h->d_like_rowptr == nullptr) ? 1.0 : 0.0; break;
-        case SMCMC_P_PERCHAIN_WAVE: *out = (per_chain(h) && h->dim <= kPcMaxDim && pc_use_wave(h)) ? 1.0 : 0.0; break;
+        case SMCMC_P_PERCHAIN_WAVE: *out = (per_chain(h) && h->dim <= kPcMaxDim && !pc_use_wg(h) && pc_use_wave(h)) ? 1.0 : 0.0; break;
+        case SMCMC_P_PERCHAIN_WORKGROUP: *out = (per_chain(h) && pc_use_wg(h)) ? 1.0 : 0.0; break;
         default: return fail(h, SMCMC_ERR_INVALID, "unknown parameter");
     }
     return SMCMC_OK;
