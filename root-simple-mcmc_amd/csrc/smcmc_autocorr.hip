@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "smcmc.h"
+#include "smcmc_host.hpp"
 
 namespace {
 
@@ -107,29 +108,25 @@ extern "C" int smcmc_autocorrelation_sums(const double* trace_device, int nslots
     hipStream_t s = (hipStream_t)stream;
     const int nblocks = nchains_padded / kWave;
     const size_t nout = (size_t)dim * (kLags + 1);
-    double *d_centre = nullptr, *d_partial = nullptr, *d_out = nullptr;
-    int status = SMCMC_ERR_HIP;
-    do {
-        if (hipMalloc(&d_centre, sizeof(double) * dim) != hipSuccess) break;
-        if (hipMalloc(&d_partial, sizeof(double) * nout * nblocks) != hipSuccess) break;
-        if (hipMalloc(&d_out, sizeof(double) * nout) != hipSuccess) break;
-        if (centre) {
-            if (hipMemcpyAsync(d_centre, centre, sizeof(double) * dim, hipMemcpyHostToDevice, s) != hipSuccess) break;
-        } else if (hipMemsetAsync(d_centre, 0, sizeof(double) * dim, s) != hipSuccess) break;
-        hipLaunchKernelGGL(autocorr_partial_kernel<0>, dim3(nblocks, dim), dim3(kWave), 0, s, trace_device, nslots, dim,
-                           (size_t)dim_stride, nchains, (size_t)nchains_padded, d_centre, d_partial);
-        if (hipGetLastError() != hipSuccess) break;
-        hipLaunchKernelGGL(autocorr_partial_kernel<kPassLags>, dim3(nblocks, dim), dim3(kWave), 0, s, trace_device, nslots,
-                           dim, (size_t)dim_stride, nchains, (size_t)nchains_padded, d_centre, d_partial);
-        if (hipGetLastError() != hipSuccess) break;
-        hipLaunchKernelGGL(autocorr_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, d_partial, nblocks,
-                           dim, d_out);
-        if (hipGetLastError() != hipSuccess) break;
-        if (hipMemcpyAsync(lagged, d_out, sizeof(double) * dim * kLags, hipMemcpyDeviceToHost, s) != hipSuccess) break;
-        if (hipMemcpyAsync(sum, d_out + (size_t)dim * kLags, sizeof(double) * dim, hipMemcpyDeviceToHost, s) != hipSuccess) break;
-        if (hipStreamSynchronize(s) != hipSuccess) break;
-        status = SMCMC_OK;
-    } while (false);
-    (void)hipFree(d_centre); (void)hipFree(d_partial); (void)hipFree(d_out);
-    return status;
+    smcmc::DeviceBuffer<double> d_centre, d_partial, d_out;
+    if (d_centre.allocate(dim) != hipSuccess || d_partial.allocate(nout * nblocks) != hipSuccess ||
+        d_out.allocate(nout) != hipSuccess)
+        return SMCMC_ERR_HIP;
+    const hipError_t c = centre ? hipMemcpyAsync(d_centre, centre, sizeof(double) * dim, hipMemcpyHostToDevice, s)
+                                : hipMemsetAsync(d_centre, 0, sizeof(double) * dim, s);
+    if (c != hipSuccess) return SMCMC_ERR_HIP;
+    hipLaunchKernelGGL(autocorr_partial_kernel<0>, dim3(nblocks, dim), dim3(kWave), 0, s, trace_device, nslots, dim,
+                       (size_t)dim_stride, nchains, (size_t)nchains_padded, d_centre.get(), d_partial.get());
+    if (hipGetLastError() != hipSuccess) return SMCMC_ERR_HIP;
+    hipLaunchKernelGGL(autocorr_partial_kernel<kPassLags>, dim3(nblocks, dim), dim3(kWave), 0, s, trace_device, nslots,
+                       dim, (size_t)dim_stride, nchains, (size_t)nchains_padded, d_centre.get(), d_partial.get());
+    if (hipGetLastError() != hipSuccess) return SMCMC_ERR_HIP;
+    hipLaunchKernelGGL(autocorr_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, d_partial.get(), nblocks,
+                       dim, d_out.get());
+    if (hipGetLastError() != hipSuccess) return SMCMC_ERR_HIP;
+    if (hipMemcpyAsync(lagged, d_out, sizeof(double) * dim * kLags, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(sum, d_out + (size_t)dim * kLags, sizeof(double) * dim, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return SMCMC_ERR_HIP;
+    return SMCMC_OK;
 }

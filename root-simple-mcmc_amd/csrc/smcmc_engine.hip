@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "smcmc.h"
+#include "smcmc_host.hpp"
 #include "smcmc_kernels.hip.h"
 #include "smcmc_panel_kernel.hip.h"
 #include "smcmc_panel_mfma_kernel.hip.h"
@@ -29,23 +30,6 @@
 using namespace smcmc;
 
 namespace {
-
-// register-resident kernel families, smallest first (SMCMC_FOR_EACH_DP)
-#define SMCMC_DP_ENTRY(n) n,
-constexpr int kDPList[] = {SMCMC_FOR_EACH_DP(SMCMC_DP_ENTRY)};
-#undef SMCMC_DP_ENTRY
-constexpr int kNumDP = sizeof(kDPList) / sizeof(kDPList[0]);
-
-bool stress_likelihood(int like) {
-    return like == SMCMC_LIKE_ASYM || like == SMCMC_LIKE_HORRIFIC || like == SMCMC_LIKE_CONSTRAINED;
-}
-
-int pick_dp(int dim, int like) {
-    // the stress likelihoods are instantiated for the 31- and 63-wide families only (launch_step)
-    for (int i = 0; i < kNumDP; ++i)
-        if (dim <= kDPList[i] && (!stress_likelihood(like) || kDPList[i] == 31 || kDPList[i] == 63)) return kDPList[i];
-    return -1;
-}
 
 hipError_t dispatch_step(int dp, const StepParams& p, int like, bool exact, bool fullu, bool moments,
                          hipStream_t s) {
@@ -93,42 +77,42 @@ struct smcmc_engine {
     std::vector<double> like_params;
     bool has_forced = false;
     // device
-    double* d_x = nullptr;
-    double* d_lane_f64 = nullptr;
-    int32_t* d_lane_i32 = nullptr;
-    double* d_U = nullptr;
-    double* d_Uop = nullptr;       // large dimensions, fused order: U^T in matrix-operand order (smcmc_panel_mfma_kernel.hip.h)
-    double* d_like = nullptr;
-    // QUADFORM with a sparse Error matrix: the non-zero entries of Error^T, row by row (quadform_csr); nullptr = dense only
-    int32_t* d_like_rowptr = nullptr;
-    int32_t* d_like_cols = nullptr;
-    int32_t* d_like_rows = nullptr;
-    double* d_like_vals = nullptr;
+    DeviceBuffer<double> d_x;
+    DeviceBuffer<double> d_lane_f64;
+    DeviceBuffer<int32_t> d_lane_i32;
+    DeviceBuffer<double> d_U;
+    DeviceBuffer<double> d_Uop;    // large dimensions, fused order: U^T in matrix-operand order (smcmc_panel_mfma_kernel.hip.h)
+    DeviceBuffer<double> d_like;
+    // QUADFORM with a sparse Error matrix: the non-zero entries of Error^T, row by row (quadform_csr); empty = dense only
+    DeviceBuffer<int32_t> d_like_rowptr;
+    DeviceBuffer<int32_t> d_like_cols;
+    DeviceBuffer<int32_t> d_like_rows;
+    DeviceBuffer<double> d_like_vals;
     int like_nnz = 0;
     bool dense_quadform = false;   // SMCMC_P_DENSE_QUADFORM
-    double* d_c0 = nullptr;
-    double* d_gacc = nullptr;
-    double* d_moments = nullptr;
-    double* d_chunks = nullptr;
-    double* h_moments = nullptr;   // pinned host copy of the packed moments (read back at every sync)
-    double* d_forced = nullptr;
-    double* d_scratch = nullptr;   // dim > 63, quadratic form in reference order: the proposal image its serial sum reads
+    DeviceBuffer<double> d_c0;
+    DeviceBuffer<double> d_gacc;
+    DeviceBuffer<double> d_moments;
+    DeviceBuffer<double> d_chunks;
+    PinnedBuffer<double> h_moments;   // host copy of the packed moments (read back at every sync)
+    DeviceBuffer<double> d_forced;
+    DeviceBuffer<double> d_scratch;   // dim > 63, quadratic form in reference order: the proposal image its serial sum reads
     // dim > 63, pooled covariance fed every step: the accepted point after each step of a launch, for the folds that follow it
-    double* d_ring = nullptr;      // [ring_steps][dim][npad]
-    double* d_ring_logl = nullptr; // [ring_steps][npad] (the kernels save both)
+    DeviceBuffer<double> d_ring;      // [ring_steps][dim][npad]
+    DeviceBuffer<double> d_ring_logl; // [ring_steps][npad] (the kernels save both)
     int ring_steps = -1;           // -1: not decided yet; 0: no ring (the state is too large), else steps per launch
     smcmc::FoldRing fold;          // dim > 63: the fold kernel's plan for this ensemble (smcmc_fold_ring.hip.h)
     ncclComm_t comm = nullptr;     // smcmc_comm_init
     int comm_ranks = 0;
-    double* d_proposed = nullptr;  // [dp][npad], allocated by SMCMC_P_KEEP_PROPOSED
+    DeviceBuffer<double> d_proposed;  // [dp][npad], allocated by SMCMC_P_KEEP_PROPOSED
     bool keep_proposed = false;
-    double* d_uniform = nullptr;   // [2][dp] bounds of the uniform dimensions
+    DeviceBuffer<double> d_uniform;   // [2][dp] bounds of the uniform dimensions
     int scan_dim = -1;             // fScanDimension
     // the pooled update on the device (smcmc_pooled_update.hip.h): the device copy of the shared proposal's numbers
     bool device_update = true;     // SMCMC_P_DEVICE_UPDATE
     bool overlap_update = false;   // SMCMC_P_OVERLAP_UPDATE
-    double *d_centre = nullptr, *d_cov = nullptr, *d_decomp = nullptr, *d_scal = nullptr;
-    double* h_scal = nullptr;      // pinned: the scalars (status word included) of the latest device update
+    DeviceBuffer<double> d_centre, d_cov, d_decomp, d_scal;
+    PinnedBuffer<double> h_scal;   // the scalars (status word included) of the latest device update
     double* h_scal_dev = nullptr;  // ... as the device addresses it (hipHostGetDevicePointer), null if it cannot
     hipEvent_t status_event = nullptr;
     bool update_prepared = false;  // pooled_update_prepare() has run on this engine's device
@@ -137,38 +121,29 @@ struct smcmc_engine {
     bool device_stale = true;      // *prop was changed on the host since the device copy was written
     struct { int updateCount, nextUpdate, lastPath; double acceptanceTrials; bool decompFull; } before_update{};
     // SMCMC_MODE_PER_CHAIN (smcmc_perchain_kernel.hip.h): every chain's own adaptive state, [k][chain] columns
-    double *d_pc_cov = nullptr, *d_pc_ut = nullptr, *d_pc_centre = nullptr, *d_pc_last = nullptr;
-    double* d_pc_tmpl = nullptr;   // what the host hands to every chain at Start / Restore / ResetProposal: cov packed, then ut
-    int* d_pc_flag = nullptr;      // chains that stopped for the host's fallback ladder in the latest launch
+    DeviceBuffer<double> d_pc_cov, d_pc_ut, d_pc_centre, d_pc_last;
+    DeviceBuffer<double> d_pc_tmpl;   // what the host hands to every chain at Start / Restore / ResetProposal: cov packed, then ut
+    DeviceBuffer<int> d_pc_flag;      // chains that stopped for the host's fallback ladder in the latest launch
     bool pc_frozen = false;        // SMCMC_P_COVARIANCE_FROZEN
     bool pc_broken = false;        // a per-chain launch ended in an error with the chains part-way: Start / Restore again
     int pc_wave = -1;              // SMCMC_P_PERCHAIN_WAVE: -1 automatic, 0 / 1 one chain per lane / per wavefront
     bool pc_wg = false;            // SMCMC_P_PERCHAIN_WORKGROUP: one chain per workgroup (dim <= smcmc::kWgMaxDim)
     smcmc::PerChainRecord pc_rec = {nullptr, 0, 0};   // the per-step record of the launch in progress (smcmc_step_recorded)
-    double* d_pc_rec = nullptr;    // its device buffer
-    double* d_pc_stage = nullptr;  // the fallback ladder's staging records (pc_host_ladder), allocated at the first ladder
-    int32_t* d_pc_stage_chains = nullptr;
+    DeviceBuffer<double> d_pc_rec;    // its device buffer
+    DeviceBuffer<double> d_pc_stage;  // the fallback ladder's staging records (pc_host_ladder), allocated at the first ladder
+    DeviceBuffer<int32_t> d_pc_stage_chains;
     // smcmc_snapshot / smcmc_rollback: a copy of the ensemble's state on the device (SMCMC_MODE_PER_CHAIN)
-    void* snap[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    DeviceBuffer<unsigned char> snap[8];
     uint32_t snap_total_steps = 0;
     bool snap_valid = false, snap_has_forced = false;
-    size_t pc_rec_cap = 0;         // ... and capacity in doubles
     std::string error;
+    ~smcmc_engine() {
+        if (status_event) (void)hipEventDestroy(status_event);
+        delete prop;
+    }
 };
 
 namespace {
-
-int fail(smcmc_engine* h, int status, const std::string& msg) {
-    if (h) h->error = msg;
-    return status;
-}
-
-#define HIP_TRY(h, expr)                                                                   \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail((h), SMCMC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 int status_of(smcmc_engine* h, UpdateStatus st) {
     switch (st) {
@@ -181,22 +156,6 @@ int status_of(smcmc_engine* h, UpdateStatus st) {
     }
     return SMCMC_ERR_RUNTIME;
 }
-
-// Every entry point that touches the device runs on the engine's own device and leaves the
-// caller's current device as it found it (two engines on two devices may share a thread).
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    explicit DeviceGuard(int device) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != device) switched = (hipSetDevice(device) == hipSuccess);
-    }
-    ~DeviceGuard() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-#define ON_DEVICE(h) DeviceGuard device_guard_((h)->device)
 
 // What UpdateProposal does to the per-chain scalars (TSimpleMCMC.H:1042-1043, 1081-1086): sigma is rescaled
 // by sqrt(old trace / new trace) and the acceptance trials are de-weighted.  Applied to every chain's
@@ -320,8 +279,7 @@ int upload_shared(smcmc_engine* h) {
 // matrix is finite, has a full diagonal (so that a non-finite coordinate always shows in the sparse sum, which then
 // falls back on the dense one) and at most a quarter of its entries are non-zero.
 int upload_like_csr(smcmc_engine* h) {
-    (void)hipFree(h->d_like_rowptr); (void)hipFree(h->d_like_cols); (void)hipFree(h->d_like_vals); (void)hipFree(h->d_like_rows);
-    h->d_like_rowptr = nullptr; h->d_like_cols = nullptr; h->d_like_vals = nullptr; h->d_like_rows = nullptr; h->like_nnz = 0;
+    h->d_like_rowptr = {}; h->d_like_cols = {}; h->d_like_vals = {}; h->d_like_rows = {}; h->like_nnz = 0;
     if (h->likelihood != SMCMC_LIKE_QUADFORM || h->dense_quadform) return SMCMC_OK;
     const int D = h->dim;
     std::vector<int32_t> rows, cols;
@@ -335,32 +293,40 @@ int upload_like_csr(smcmc_engine* h) {
         }
     }
     if (cols.size() * 4 > (size_t)D * D) return SMCMC_OK;
-    h->like_nnz = (int)cols.size();
+    const int nnz = (int)cols.size();
     while (cols.size() % smcmc::kQuadChunk != 0) { rows.push_back(0); cols.push_back(0); vals.push_back(0.0); }   // zero entries: skipped terms
     const int32_t padded = (int32_t)cols.size();
-    HIP_TRY(h, hipMalloc(&h->d_like_rowptr, sizeof(int32_t)));
-    HIP_TRY(h, hipMalloc(&h->d_like_rows, sizeof(int32_t) * rows.size()));
-    HIP_TRY(h, hipMalloc(&h->d_like_cols, sizeof(int32_t) * cols.size()));
-    HIP_TRY(h, hipMalloc(&h->d_like_vals, sizeof(double) * vals.size()));
-    HIP_TRY(h, hipMemcpyAsync(h->d_like_rowptr, &padded, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_like_rows, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_like_cols, cols.data(), sizeof(int32_t) * cols.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_like_vals, vals.data(), sizeof(double) * vals.size(), hipMemcpyHostToDevice, h->stream));
+    // all four on the device or none: an engine without them takes the dense sum
+    DeviceBuffer<int32_t> d_rowptr, d_rows, d_cols;
+    DeviceBuffer<double> d_vals;
+    HIP_TRY(h, d_rowptr.allocate(1));
+    HIP_TRY(h, d_rows.allocate(rows.size()));
+    HIP_TRY(h, d_cols.allocate(cols.size()));
+    HIP_TRY(h, d_vals.allocate(vals.size()));
+    HIP_TRY(h, hipMemcpyAsync(d_rowptr, &padded, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_rows, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_cols, cols.data(), sizeof(int32_t) * cols.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_vals, vals.data(), sizeof(double) * vals.size(), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->d_like_rowptr = std::move(d_rowptr); h->d_like_rows = std::move(d_rows);
+    h->d_like_cols = std::move(d_cols); h->d_like_vals = std::move(d_vals);
+    h->like_nnz = nnz;
     return SMCMC_OK;
 }
 
 int upload_like(smcmc_engine* h) {
     if (h->panel_w && !h->d_scratch && (h->likelihood == SMCMC_LIKE_USER || h->likelihood == SMCMC_LIKE_CONSTRAINED)) {
         // large dimensions: one lane per chain evaluates these from the proposal's [dim][chain] image
-        HIP_TRY(h, hipMalloc(&h->d_scratch, sizeof(double) * (size_t)h->npad * h->dim));
+        HIP_TRY(h, h->d_scratch.allocate((size_t)h->npad * h->dim));
         HIP_TRY(h, hipMemsetAsync(h->d_scratch, 0, sizeof(double) * (size_t)h->npad * h->dim, h->stream));
     }
+    std::vector<double> prm;
+    int st = check_like_params(h, h->likelihood, (size_t)h->dp * h->dp, "a user likelihood takes at most dim_padded^2 parameters", prm);
+    if (st) return st;
     if (h->likelihood == SMCMC_LIKE_QUADFORM) {
-        if ((int)h->like_params.size() != h->dim * h->dim)
-            return fail(h, SMCMC_ERR_INVALID, "QUADFORM needs dim*dim likelihood parameters (the Error matrix)");
         const int D = h->dim;
-        { int stc_ = upload_like_csr(h); if (stc_) return stc_; }
+        st = upload_like_csr(h);
+        if (st) return st;
         if ((h->panel_w && h->exact) || h->mode == SMCMC_MODE_PER_CHAIN) {
             // large dimensions, reference order (and the per-chain kernel at any dimension): one lane per chain walks the
             // D^2-term sum of TDummyLogLikelihood.H:24-28 with j innermost; it reads row i of Error^T (scalar loads) and
@@ -369,7 +335,7 @@ int upload_like(smcmc_engine* h) {
             for (int i = 0; i < D; ++i)
                 for (int j = 0; j < D; ++j) et[(size_t)i * D + j] = h->like_params[(size_t)j * D + i];
             if (h->panel_w && !h->d_scratch) {
-                HIP_TRY(h, hipMalloc(&h->d_scratch, sizeof(double) * (size_t)h->npad * D));
+                HIP_TRY(h, h->d_scratch.allocate((size_t)h->npad * D));
                 HIP_TRY(h, hipMemsetAsync(h->d_scratch, 0, sizeof(double) * (size_t)h->npad * D, h->stream));
             }
             HIP_TRY(h, hipMemcpyAsync(h->d_like, et.data(), et.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -398,34 +364,18 @@ int upload_like(smcmc_engine* h) {
         return upload_padded(h, et.data(), h->d_like);
     }
     if (stress_likelihood(h->likelihood)) {
-        std::vector<double> prm;
-        if (h->likelihood == SMCMC_LIKE_ASYM) {
-            prm = {-1.0, 100.0};                                   // TAsymLogLikelihood.H:21-22
-            if (h->like_params.size() == 2) prm = h->like_params;
-            else if (!h->like_params.empty()) return fail(h, SMCMC_ERR_INVALID, "ASYM takes {positiveSlope, negativeSlope}");
-        } else if (h->likelihood == SMCMC_LIKE_CONSTRAINED) {
-            if ((int)h->like_params.size() != 2 + 2 * h->dim)
-                return fail(h, SMCMC_ERR_INVALID,
-                            "CONSTRAINED needs {SummedValues, SummedConstraint, ExpectedValues[dim], PriorConstraints[dim]}");
-            prm = h->like_params;
-        } else {
-            prm = {0.0};
-        }
+        if (prm.empty()) prm = {0.0};                              // HORRIFIC reads none
         HIP_TRY(h, hipMemcpyAsync(h->d_like, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         return SMCMC_OK;
     }
     if (h->likelihood == SMCMC_LIKE_USER) {
-        if (h->like_params.size() > (size_t)h->dp * h->dp)
-            return fail(h, SMCMC_ERR_INVALID, "a user likelihood takes at most dim_padded^2 parameters");
-        if (!h->like_params.empty())
-            HIP_TRY(h, hipMemcpyAsync(h->d_like, h->like_params.data(), h->like_params.size() * sizeof(double),
-                                      hipMemcpyHostToDevice, h->stream));
+        if (!prm.empty())
+            HIP_TRY(h, hipMemcpyAsync(h->d_like, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         return SMCMC_OK;
     }
-    double b = 100.0;   // ROSEN_B, THardLogLikelihood.H:53
-    if (h->likelihood == SMCMC_LIKE_ROSENBROCK && !h->like_params.empty()) b = h->like_params[0];
+    const double b = prm.empty() ? 100.0 : prm[0];   // ROSENBROCK's, or the unused default of the others
     HIP_TRY(h, hipMemcpyAsync(h->d_like, &b, sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SMCMC_OK;
@@ -672,14 +622,15 @@ int ensure_ring(smcmc_engine* h) {
     if (steps > (size_t)smcmc::kFoldMaxSrc) steps = smcmc::kFoldMaxSrc;   // one fold launch takes the whole ring
     if (steps < 2) { h->ring_steps = 0; return SMCMC_OK; }
     // no memory for the ring is no error: the one-step launches with a fold between them need none
-    if (hipMalloc(&h->d_ring, state * steps) != hipSuccess ||
-        hipMalloc(&h->d_ring_logl, sizeof(double) * (size_t)h->npad * steps) != hipSuccess) {
+    DeviceBuffer<double> ring, ring_logl;
+    if (ring.allocate(state / sizeof(double) * steps) != hipSuccess ||
+        ring_logl.allocate((size_t)h->npad * steps) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(h->d_ring); (void)hipFree(h->d_ring_logl);
-        h->d_ring = nullptr; h->d_ring_logl = nullptr;
         h->ring_steps = 0;
         return SMCMC_OK;
     }
+    h->d_ring = std::move(ring);
+    h->d_ring_logl = std::move(ring_logl);
     h->ring_steps = (int)steps;
     return SMCMC_OK;
 }
@@ -703,26 +654,30 @@ int fold_points(smcmc_engine* h, const double* const* pts, int n) {
 // ---- SMCMC_MODE_PER_CHAIN: every chain owns its adaptive state (smcmc_perchain_kernel.hip.h) --------------------
 bool per_chain(const smcmc_engine* h) { return h->mode == SMCMC_MODE_PER_CHAIN; }
 
+// every chain's adaptive state, allocated at the first Start in this mode: all of it or none
 int pc_alloc(smcmc_engine* h) {
     if (h->d_pc_cov) return SMCMC_OK;
     const size_t NP = (size_t)h->npad, D = (size_t)h->dim, npk = D * (D + 1) / 2;
     // the kernel reads both streams in whole chunks and primes its buffers unconditionally: padding behind the last tile
     const size_t pad = (size_t)smcmc::kPcPad * smcmc::kWave;
-    HIP_TRY(h, hipMalloc(&h->d_pc_cov, sizeof(double) * (npk * NP + pad)));
-    HIP_TRY(h, hipMalloc(&h->d_pc_ut, sizeof(double) * (D * D * NP + pad)));
-    HIP_TRY(h, hipMalloc(&h->d_pc_centre, sizeof(double) * D * NP));
-    HIP_TRY(h, hipMalloc(&h->d_pc_last, sizeof(double) * D * NP));
-    HIP_TRY(h, hipMalloc(&h->d_pc_tmpl, sizeof(double) * (npk + D * D + D)));
-    HIP_TRY(h, hipMalloc(&h->d_pc_flag, sizeof(int)));
-    HIP_TRY(h, hipMemset(h->d_pc_cov, 0, sizeof(double) * (npk * NP + pad)));
-    HIP_TRY(h, hipMemset(h->d_pc_ut, 0, sizeof(double) * (D * D * NP + pad)));
-    HIP_TRY(h, hipMemset(h->d_pc_centre, 0, sizeof(double) * D * NP));
-    HIP_TRY(h, hipMemset(h->d_pc_last, 0, sizeof(double) * D * NP));
-    HIP_TRY(h, hipMemset(h->d_pc_flag, 0, sizeof(int)));
-    if (!h->d_proposed) {   // the proposal's image: fProposed is always kept in this mode
-        HIP_TRY(h, hipMalloc(&h->d_proposed, sizeof(double) * NP * h->dp));
-        HIP_TRY(h, hipMemset(h->d_proposed, 0, sizeof(double) * NP * h->dp));
-    }
+    DeviceBuffer<double> cov, ut, centre, last, tmpl, proposed;
+    DeviceBuffer<int> flag;
+    HIP_TRY(h, cov.allocate(npk * NP + pad));
+    HIP_TRY(h, ut.allocate(D * D * NP + pad));
+    HIP_TRY(h, centre.allocate(D * NP));
+    HIP_TRY(h, last.allocate(D * NP));
+    HIP_TRY(h, tmpl.allocate(npk + D * D + D));
+    HIP_TRY(h, flag.allocate(1));
+    if (!h->d_proposed) HIP_TRY(h, proposed.allocate(NP * h->dp));   // the proposal's image: fProposed is always kept in this mode
+    HIP_TRY(h, hipMemset(cov, 0, sizeof(double) * (npk * NP + pad)));
+    HIP_TRY(h, hipMemset(ut, 0, sizeof(double) * (D * D * NP + pad)));
+    HIP_TRY(h, hipMemset(centre, 0, sizeof(double) * D * NP));
+    HIP_TRY(h, hipMemset(last, 0, sizeof(double) * D * NP));
+    HIP_TRY(h, hipMemset(flag, 0, sizeof(int)));
+    if (proposed) HIP_TRY(h, hipMemset(proposed, 0, sizeof(double) * NP * h->dp));
+    h->d_pc_cov = std::move(cov); h->d_pc_ut = std::move(ut); h->d_pc_centre = std::move(centre);
+    h->d_pc_last = std::move(last); h->d_pc_tmpl = std::move(tmpl); h->d_pc_flag = std::move(flag);
+    if (proposed) h->d_proposed = std::move(proposed);
     h->keep_proposed = true;
     return SMCMC_OK;
 }
@@ -821,9 +776,13 @@ int pc_host_ladder(smcmc_engine* h, bool explicit_update) {
     // the flagged chains in batches through one staging buffer: one gather launch, one copy each way, one scatter launch
     // per batch (chain by chain this was ten strided copies of 8-byte rows per chain)
     const size_t batch_max = std::max<size_t>(1, std::min<size_t>(4096, ((size_t)256 << 20) / (stride * sizeof(double))));
-    if (!h->d_pc_stage) {
-        HIP_TRY(h, hipMalloc(&h->d_pc_stage, batch_max * stride * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&h->d_pc_stage_chains, batch_max * sizeof(int32_t)));
+    if (!h->d_pc_stage) {   // both or neither
+        DeviceBuffer<double> records;
+        DeviceBuffer<int32_t> chains;
+        HIP_TRY(h, records.allocate(batch_max * stride));
+        HIP_TRY(h, chains.allocate(batch_max));
+        h->d_pc_stage = std::move(records);
+        h->d_pc_stage_chains = std::move(chains);
     }
     std::vector<double> stage, ut;
     for (size_t b0 = 0; b0 < flagged.size(); b0 += batch_max) {
@@ -993,7 +952,7 @@ StepParams make_params(smcmc_engine* h, int nsteps, int metropolis) {
     p.x = h->d_x; p.lane_f64 = h->d_lane_f64; p.lane_i32 = h->d_lane_i32;
     p.gacc = h->d_gacc;
     p.save_x = nullptr; p.save_logl = nullptr; p.save_stride = 1;
-    p.proposed = h->keep_proposed ? h->d_proposed : nullptr;
+    p.proposed = h->keep_proposed ? h->d_proposed.get() : nullptr;
     p.uniform = h->d_uniform;
     for (int d = 0; d < h->dim && d < 64; ++d)   // the register kernels (dim <= 63); larger dimensions carry theirs in d_uniform
         if (P.ptype[d] == 1) p.uniform_mask |= (uint64_t)1 << d;
@@ -1249,26 +1208,26 @@ int smcmc_create(int dim, int nchains, int likelihood, uint64_t seed, uint32_t c
     if (panel_w) HIP_TRY(h, smcmc::fold_ring_prepare(h->fold, dim, nchains, h->npad, h->fold_nslices, h->slice_chains));
     const size_t np = (size_t)h->npad;
     const size_t u_doubles = panel_w ? (size_t)panel_w * dim * kPanelCW : (size_t)dp * dp;
-    HIP_TRY(h, hipMalloc(&h->d_x, sizeof(double) * np * dp));        // rows >= dim stay zero
-    HIP_TRY(h, hipMalloc(&h->d_forced, sizeof(double) * np * dp));
-    HIP_TRY(h, hipMalloc(&h->d_lane_f64, sizeof(double) * np * SMCMC_LANE_F64_COUNT_));
-    HIP_TRY(h, hipMalloc(&h->d_lane_i32, sizeof(int32_t) * np * SMCMC_LANE_I32_COUNT_));
-    HIP_TRY(h, hipMalloc(&h->d_U, sizeof(double) * u_doubles));
+    HIP_TRY(h, h->d_x.allocate(np * dp));        // rows >= dim stay zero
+    HIP_TRY(h, h->d_forced.allocate(np * dp));
+    HIP_TRY(h, h->d_lane_f64.allocate(np * SMCMC_LANE_F64_COUNT_));
+    HIP_TRY(h, h->d_lane_i32.allocate(np * SMCMC_LANE_I32_COUNT_));
+    HIP_TRY(h, h->d_U.allocate(u_doubles));
     HIP_TRY(h, hipMemset(h->d_U, 0, sizeof(double) * u_doubles));
     if (panel_w) {
-        HIP_TRY(h, hipMalloc(&h->d_Uop, sizeof(double) * panel_mfma_uop_doubles(dim)));
+        HIP_TRY(h, h->d_Uop.allocate(panel_mfma_uop_doubles(dim)));
         HIP_TRY(h, hipMemset(h->d_Uop, 0, sizeof(double) * panel_mfma_uop_doubles(dim)));
     }
     const size_t like_doubles = std::max((size_t)dp * dp, panel_w ? panel_mfma_uop_doubles(dim) : (size_t)0);   // >= 2 + 2 dim
-    HIP_TRY(h, hipMalloc(&h->d_like, sizeof(double) * like_doubles));
-    HIP_TRY(h, hipMalloc(&h->d_c0, sizeof(double) * dp));
-    HIP_TRY(h, hipMalloc(&h->d_gacc, sizeof(double) * gacc_doubles(h)));
-    HIP_TRY(h, hipMalloc(&h->d_moments, sizeof(double) * npacked(h)));
-    HIP_TRY(h, hipHostMalloc((void**)&h->h_moments, sizeof(double) * npacked(h), hipHostMallocDefault));
-    HIP_TRY(h, hipMalloc(&h->d_chunks, sizeof(double) * npacked(h) * ((h->ngroups + kReduceChunk - 1) / kReduceChunk)));
+    HIP_TRY(h, h->d_like.allocate(like_doubles));
+    HIP_TRY(h, h->d_c0.allocate(dp));
+    HIP_TRY(h, h->d_gacc.allocate(gacc_doubles(h)));
+    HIP_TRY(h, h->d_moments.allocate(npacked(h)));
+    HIP_TRY(h, h->h_moments.allocate(npacked(h)));
+    HIP_TRY(h, h->d_chunks.allocate(npacked(h) * ((h->ngroups + kReduceChunk - 1) / kReduceChunk)));
     HIP_TRY(h, hipMemset(h->d_x, 0, sizeof(double) * np * dp));
     HIP_TRY(h, hipMemset(h->d_forced, 0, sizeof(double) * np * dp));
-    HIP_TRY(h, hipMalloc(&h->d_uniform, sizeof(double) * (2 * dp + 8)));
+    HIP_TRY(h, h->d_uniform.allocate(2 * dp + 8));
     HIP_TRY(h, hipMemset(h->d_uniform, 0, sizeof(double) * (2 * dp + 8)));
     HIP_TRY(h, hipMemset(h->d_lane_f64, 0, sizeof(double) * np * SMCMC_LANE_F64_COUNT_));
     HIP_TRY(h, hipMemset(h->d_lane_i32, 0, sizeof(int32_t) * np * SMCMC_LANE_I32_COUNT_));
@@ -1276,12 +1235,12 @@ int smcmc_create(int dim, int nchains, int likelihood, uint64_t seed, uint32_t c
     HIP_TRY(h, hipMemset(h->d_c0, 0, sizeof(double) * dp));
     HIP_TRY(h, hipMemset(h->d_gacc, 0, sizeof(double) * gacc_doubles(h)));
     HIP_TRY(h, hipMemset(h->d_moments, 0, sizeof(double) * npacked(h)));
-    HIP_TRY(h, hipMalloc(&h->d_centre, sizeof(double) * dim));
-    HIP_TRY(h, hipMalloc(&h->d_cov, sizeof(double) * (size_t)dim * dim));
-    HIP_TRY(h, hipMalloc(&h->d_decomp, sizeof(double) * (size_t)dim * dim));
-    HIP_TRY(h, hipMalloc(&h->d_scal, sizeof(double) * kPsCount));
+    HIP_TRY(h, h->d_centre.allocate(dim));
+    HIP_TRY(h, h->d_cov.allocate((size_t)dim * dim));
+    HIP_TRY(h, h->d_decomp.allocate((size_t)dim * dim));
+    HIP_TRY(h, h->d_scal.allocate(kPsCount));
     HIP_TRY(h, hipMemset(h->d_scal, 0, sizeof(double) * kPsCount));
-    HIP_TRY(h, hipHostMalloc((void**)&h->h_scal, sizeof(double) * kPsCount, hipHostMallocDefault));
+    HIP_TRY(h, h->h_scal.allocate(kPsCount));
     if (hipHostGetDevicePointer((void**)&h->h_scal_dev, h->h_scal, 0) != hipSuccess) {
         (void)hipGetLastError();
         h->h_scal_dev = nullptr;
@@ -1295,23 +1254,6 @@ int smcmc_destroy(smcmc_engine* h) {
     (void)smcmc_comm_destroy(h);
     ON_DEVICE(h);
     if (h->d_x) (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(h->d_x); (void)hipFree(h->d_forced); (void)hipFree(h->d_proposed); (void)hipFree(h->d_scratch); (void)hipFree(h->d_uniform); (void)hipFree(h->d_lane_f64); (void)hipFree(h->d_lane_i32);
-    (void)hipFree(h->d_U); (void)hipFree(h->d_Uop); (void)hipFree(h->d_like); (void)hipFree(h->d_like_rowptr); (void)hipFree(h->d_like_cols); (void)hipFree(h->d_like_vals); (void)hipFree(h->d_like_rows); (void)hipFree(h->d_c0); (void)hipFree(h->d_gacc);
-    (void)hipFree(h->d_moments); (void)hipFree(h->d_chunks); (void)hipHostFree(h->h_moments);
-    (void)hipFree(h->d_centre); (void)hipFree(h->d_cov); (void)hipFree(h->d_decomp); (void)hipFree(h->d_scal);
-    (void)hipFree(h->d_ring); (void)hipFree(h->d_ring_logl);
-    (void)hipFree(h->d_pc_cov); (void)hipFree(h->d_pc_ut); (void)hipFree(h->d_pc_centre); (void)hipFree(h->d_pc_last);
-    (void)hipFree(h->d_pc_tmpl); (void)hipFree(h->d_pc_flag); (void)hipFree(h->d_pc_stage); (void)hipFree(h->d_pc_stage_chains);
-    (void)hipFree(h->d_pc_rec);
-    h->d_pc_rec = nullptr;
-    for (int k = 0; k < 8; ++k) {
-        (void)hipFree(h->snap[k]);
-        h->snap[k] = nullptr;
-    }
-    smcmc::fold_ring_release(h->fold);
-    (void)hipHostFree(h->h_scal);
-    if (h->status_event) (void)hipEventDestroy(h->status_event);
-    delete h->prop;
     delete h;
     return SMCMC_OK;
 }
@@ -1467,7 +1409,7 @@ int smcmc_set_param(smcmc_engine* h, int which, double v) {
         case SMCMC_P_KEEP_PROPOSED:
             if (v != 0.0 && !h->d_proposed) {
                 const size_t bytes = sizeof(double) * (size_t)h->npad * h->dp;
-                HIP_TRY(h, hipMalloc(&h->d_proposed, bytes));
+                HIP_TRY(h, h->d_proposed.allocate((size_t)h->npad * h->dp));
                 // before the first step the proposed point is the start point (TSimpleMCMC.H:250-253)
                 HIP_TRY(h, hipMemcpyAsync(h->d_proposed, h->d_x, bytes, hipMemcpyDeviceToDevice, h->stream));
             }
@@ -1798,7 +1740,7 @@ int smcmc_snapshot(smcmc_engine* h) {
     int st = snap_arrays(h, arr, bytes);
     if (st) return st;
     for (int k = 0; k < 8; ++k) {
-        if (!h->snap[k]) HIP_TRY(h, hipMalloc(&h->snap[k], bytes[k]));
+        if (!h->snap[k]) HIP_TRY(h, h->snap[k].allocate(bytes[k]));
         HIP_TRY(h, hipMemcpyAsync(h->snap[k], arr[k], bytes[k], hipMemcpyDeviceToDevice, h->stream));
     }
     h->snap_total_steps = h->total_steps;
@@ -1831,12 +1773,7 @@ int smcmc_step_recorded(smcmc_engine* h, int nsteps, int metropolis, int chain, 
     if (chain < 0 || chain >= h->nchains) return fail(h, SMCMC_ERR_INVALID, "no such chain");
     const int stride = smcmc_record_stride(h);
     const size_t need = (size_t)nsteps * stride;
-    if (need > h->pc_rec_cap) {
-        (void)hipFree(h->d_pc_rec);
-        h->d_pc_rec = nullptr; h->pc_rec_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_pc_rec, need * sizeof(double)));
-        h->pc_rec_cap = need;
-    }
+    if (need > h->d_pc_rec.size()) HIP_TRY(h, h->d_pc_rec.allocate(need));
     h->pc_rec = smcmc::PerChainRecord{h->d_pc_rec, chain, stride};
     const int st = launch(h, nsteps, metropolis, 1, nullptr, nullptr);
     h->pc_rec = smcmc::PerChainRecord{nullptr, 0, 0};
@@ -2129,10 +2066,10 @@ int smcmc_read_chain(smcmc_engine* h, int chain, double* x, double* proposed, do
         return fail(h, SMCMC_ERR_LOGIC, "the proposed point is not kept: set SMCMC_P_KEEP_PROPOSED first");
     const size_t NP = (size_t)h->npad;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (x) HIP_TRY(h, pc_get_column(h->d_x, NP, chain, h->dim, x));
-    if (proposed) HIP_TRY(h, pc_get_column(h->d_proposed, NP, chain, h->dim, proposed));
-    if (lanes_f64) HIP_TRY(h, pc_get_column(h->d_lane_f64, NP, chain, SMCMC_LANE_F64_COUNT_, lanes_f64));
-    if (lanes_i32) HIP_TRY(h, pc_get_column(h->d_lane_i32, NP, chain, SMCMC_LANE_I32_COUNT_, lanes_i32));
+    if (x) HIP_TRY(h, pc_get_column(h->d_x.get(), NP, chain, h->dim, x));
+    if (proposed) HIP_TRY(h, pc_get_column(h->d_proposed.get(), NP, chain, h->dim, proposed));
+    if (lanes_f64) HIP_TRY(h, pc_get_column(h->d_lane_f64.get(), NP, chain, SMCMC_LANE_F64_COUNT_, lanes_f64));
+    if (lanes_i32) HIP_TRY(h, pc_get_column(h->d_lane_i32.get(), NP, chain, SMCMC_LANE_I32_COUNT_, lanes_i32));
     return SMCMC_OK;
 }
 
@@ -2151,7 +2088,7 @@ int smcmc_read_chain_proposal(smcmc_engine* h, int chain, double* centre, double
     const size_t NP = (size_t)h->npad;
     const int npk = D * (D + 1) / 2;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (centre) HIP_TRY(h, pc_get_column(h->d_pc_centre, NP, chain, D, centre));
+    if (centre) HIP_TRY(h, pc_get_column(h->d_pc_centre.get(), NP, chain, D, centre));
     if (covariance) {
         std::vector<double> packed(npk);
         HIP_TRY(h, pc_get_tiled(h->d_pc_cov, chain, npk, npk, packed.data()));

@@ -28,7 +28,6 @@ hipError_t go_fold_ring(const FoldRingParams& p, int nwg, hipStream_t stream) {
 }  // namespace
 
 hipError_t fold_ring_prepare(FoldRing& fr, int D, int nchains, int npad, int nslices, int slice_chains) {
-    fold_ring_release(fr);
     if ((D + 1 + 15) / 16 > kFrMaxFoot - 2) return hipErrorInvalidValue;
     int dev = 0, cus = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -37,26 +36,19 @@ hipError_t fold_ring_prepare(FoldRing& fr, int D, int nchains, int npad, int nsl
     if (e != hipSuccess) return e;
     const FoldPlan plan = fold_ring_plan(D, nchains, npad, nslices, slice_chains, cus > 0 ? cus : 256);
     if (plan.rounds < 0 || plan.max_tiles > kFrMaxT) return hipErrorInvalidValue;
-    e = hipMalloc(&fr.d_plan, sizeof(FoldPlanEntry) * plan.wg.size());
+    FoldRing f;
+    e = f.d_plan.allocate(plan.wg.size());
     if (e != hipSuccess) return e;
-    e = hipMemcpy(fr.d_plan, plan.wg.data(), sizeof(FoldPlanEntry) * plan.wg.size(), hipMemcpyHostToDevice);
+    e = hipMemcpy(f.d_plan, plan.wg.data(), sizeof(FoldPlanEntry) * plan.wg.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) return e;
-    e = hipMalloc(&fr.d_order, sizeof(uint16_t) * plan.order.size());
+    e = f.d_order.allocate(plan.order.size());
     if (e != hipSuccess) return e;
-    e = hipMemcpy(fr.d_order, plan.order.data(), sizeof(uint16_t) * plan.order.size(), hipMemcpyHostToDevice);
+    e = hipMemcpy(f.d_order, plan.order.data(), sizeof(uint16_t) * plan.order.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) return e;
-    fr.nwg = (int)plan.wg.size();
-    fr.rounds = plan.rounds;
+    f.nwg = (int)plan.wg.size();
+    f.rounds = plan.rounds;
+    fr = std::move(f);
     return hipSuccess;
-}
-
-void fold_ring_release(FoldRing& fr) {
-    if (fr.d_plan) (void)hipFree(fr.d_plan);
-    if (fr.d_order) (void)hipFree(fr.d_order);
-    fr.d_plan = nullptr;
-    fr.d_order = nullptr;
-    fr.nwg = 0;
-    fr.rounds = 0;
 }
 
 hipError_t launch_fold_ring(const FoldRing& fr, FoldRingParams p, hipStream_t stream) {

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "smcmc_fold_kernel.hip.h"
+#include "smcmc_host.hpp"
 #include "smcmc_kernels.hip.h"
 
 namespace smcmc {
@@ -476,13 +477,13 @@ static __global__ void __launch_bounds__(kFrWaves* kWave, 1) __attribute__((amdg
 
 // Host side (smcmc_fold_inst.hip): the plan of an engine on its device, and the launch.
 struct FoldRing {
-    FoldPlanEntry* d_plan = nullptr;
-    uint16_t* d_order = nullptr;
+    DeviceBuffer<FoldPlanEntry> d_plan;
+    DeviceBuffer<uint16_t> d_order;
     int nwg = 0;                      // workgroups of a launch = plan entries (a multiple of 8)
     int rounds = 0;                   // the staging-round class of the plan (the kernel instantiation)
 };
+// fr is replaced only when the whole plan is on the device
 hipError_t fold_ring_prepare(FoldRing& fr, int D, int nchains, int npad, int nslices, int slice_chains);
-void fold_ring_release(FoldRing& fr);
 // p.plan is taken from fr; p.nsrc points in p.src are folded in order (1 <= nsrc <= kFoldMaxSrc)
 hipError_t launch_fold_ring(const FoldRing& fr, FoldRingParams p, hipStream_t stream);
 

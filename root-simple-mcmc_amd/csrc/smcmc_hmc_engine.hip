@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "smcmc.h"
+#include "smcmc_host.hpp"
 #include "smcmc_hmc_kernel.hip.h"
 #include "smcmc_hmc_mfma_kernel.hip.h"
 #include "smcmc_fold_ring.hip.h"
@@ -40,9 +41,9 @@ struct smcmc_hmc {
     int leapfrog = 10;             // fLeapFrogSteps (:133); SetLeapFrog(n) stores -n (:190)
     hipStream_t stream = nullptr;
     std::vector<double> like_params;
-    double *d_q = nullptr, *d_pm = nullptr, *d_qn = nullptr, *d_pn = nullptr, *d_E = nullptr, *d_like = nullptr;
-    double* d_lane_f64 = nullptr;
-    int32_t* d_lane_i32 = nullptr;
+    DeviceBuffer<double> d_q, d_pm, d_qn, d_pn, d_E, d_like;
+    DeviceBuffer<double> d_lane_f64;
+    DeviceBuffer<int32_t> d_lane_i32;
     // pooled tuning (adaptive step length / leapfrog count, or track_cov)
     HmcShared* shared = nullptr;
     bool track_cov = false;        // keep the running covariance even with a fixed step and count
@@ -50,54 +51,29 @@ struct smcmc_hmc {
     int steps_reduced = 0;   // steps whose moments are in d_moments, waiting for hmc_apply (between reduce and apply)
     int fold_nslices = 0, slice_chains = 0;
     smcmc::FoldRing fold;   // the fold kernel's plan for this ensemble
-    double *d_p0 = nullptr, *d_qprev = nullptr, *d_gacc = nullptr, *d_moments = nullptr, *d_zero = nullptr;
-    double* h_moments = nullptr;   // pinned: the packed moments come back every sync
+    DeviceBuffer<double> d_p0, d_qprev, d_gacc, d_moments, d_zero;
+    PinnedBuffer<double> h_moments;   // the packed moments come back every sync
     // PotentialGradient types 2 / 3 / 5 (TSimpleHMC.H:467-532): the GENERIC instantiation of hmc_step_kernel
     int gradient_type = 0;
-    double *d_Eperm = nullptr;     // QUADFORM: Error in hmc_step_kernel's layout (d_E holds the matrix kernels')
-    double *d_covE = nullptr, *d_cov_avg = nullptr, *d_fd_grad = nullptr;
+    DeviceBuffer<double> d_Eperm;  // QUADFORM: Error in hmc_step_kernel's layout (d_E holds the matrix kernels')
+    DeviceBuffer<double> d_covE, d_cov_avg, d_fd_grad;
     bool cov_dirty = true;         // fEstimatedError / fAveragePoint changed since the last upload
     // the running average point / covariance on the device (hmc_absorb_* kernels): the host copy in *shared follows
     // on demand (hmc_pull) or when UpdateErrorMatrix decides to run
-    double *d_avg = nullptr, *d_exxt = nullptr, *d_hcov = nullptr, *d_hscal = nullptr;
-    double* h_hscal = nullptr;     // pinned: {n, average trials, covariance trials, trace}
+    DeviceBuffer<double> d_avg, d_exxt, d_hcov, d_hscal;
+    PinnedBuffer<double> h_hscal;  // {n, average trials, covariance trials, trace}
     bool host_stale = false;       // the device holds newer average / covariance than *shared
     bool shared_on_device = false; // hmc_push has run since the host last (re)initialised *shared
     // SMCMC_MODE_PER_CHAIN: every chain's own running average / covariance and tuning scalars (smcmc_hmc_perchain.hip.h)
     int mode = SMCMC_MODE_POOLED;
-    double *d_pc_avg = nullptr, *d_pc_exxt = nullptr, *d_pc_covdiag = nullptr, *d_pc_scal = nullptr, *d_pc_scratch = nullptr;
-    int32_t* d_pc_work = nullptr;
+    DeviceBuffer<double> d_pc_avg, d_pc_exxt, d_pc_covdiag, d_pc_scal, d_pc_scratch;
+    DeviceBuffer<int32_t> d_pc_work;
     int pc_grid = 0;               // workgroups of hmc_pc_error_kernel
     std::string error;
+    ~smcmc_hmc() { delete shared; }
 };
 
 namespace {
-
-int hfail(smcmc_hmc* h, int status, const std::string& msg) {
-    if (h) h->error = msg;
-    return status;
-}
-
-#define HMC_TRY(h, expr)                                                                     \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return hfail((h), SMCMC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-struct HmcDeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    explicit HmcDeviceGuard(int device) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != device) switched = (hipSetDevice(device) == hipSuccess);
-    }
-    ~HmcDeviceGuard() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-    HmcDeviceGuard(const HmcDeviceGuard&) = delete;
-    HmcDeviceGuard& operator=(const HmcDeviceGuard&) = delete;
-};
-#define HMC_ON_DEVICE(h) HmcDeviceGuard device_guard_((h)->device)
 
 size_t hmc_npacked(const smcmc_hmc* h) { return (size_t)(h->dim + 1) * (h->dim + 2) / 2; }
 size_t hmc_gacc_doubles(const smcmc_hmc* h) {
@@ -140,12 +116,6 @@ __global__ void hmc_retune_kernel(double* lane_f64, int32_t* lane_i32, int npad,
     lane_i32[(size_t)kHmcLaneLeapfrog * npad + c] = L;
 }
 
-template <typename T>
-__global__ void hmc_fill_lane_kernel(T* col, int nchains, T v) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < nchains) col[c] = v;
-}
-
 HmcParams hmc_params(smcmc_hmc* h, int nsteps, int init_only) {
     HmcParams p;
     std::memset(&p, 0, sizeof(p));
@@ -183,31 +153,38 @@ std::vector<double> hmc_permute(const smcmc_hmc* h, const double* M) {
 // average point go up again whenever the pooled update changed them
 int hmc_generic_buffers(smcmc_hmc* h) {
     const int D = h->dim;
-    const size_t perm_bytes = sizeof(double) * (size_t)h->W * D * kPanelCW;
+    const size_t perm_doubles = (size_t)h->W * D * kPanelCW, perm_bytes = sizeof(double) * perm_doubles;
     if (h->likelihood == SMCMC_LIKE_QUADFORM && !h->d_Eperm) {
-        HMC_TRY(h, hipMalloc(&h->d_Eperm, perm_bytes));
+        DeviceBuffer<double> eperm;
+        HIP_TRY(h, eperm.allocate(perm_doubles));
         const std::vector<double> perm = hmc_permute(h, h->like_params.data());
-        HMC_TRY(h, hipMemcpyAsync(h->d_Eperm, perm.data(), perm_bytes, hipMemcpyHostToDevice, h->stream));
-        HMC_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, hipMemcpyAsync(eperm, perm.data(), perm_bytes, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        h->d_Eperm = std::move(eperm);
     }
     if (h->gradient_type == 3 && !h->d_fd_grad) {
-        HMC_TRY(h, hipMalloc(&h->d_fd_grad, sizeof(double) * (size_t)h->npad * D));
-        HMC_TRY(h, hipMemsetAsync(h->d_fd_grad, 0, sizeof(double) * (size_t)h->npad * D, h->stream));
+        DeviceBuffer<double> fd;
+        HIP_TRY(h, fd.allocate((size_t)h->npad * D));
+        HIP_TRY(h, hipMemsetAsync(fd, 0, sizeof(double) * (size_t)h->npad * D, h->stream));
+        h->d_fd_grad = std::move(fd);
     }
     if (h->gradient_type == 2) {
         if (!h->d_covE) {
-            HMC_TRY(h, hipMalloc(&h->d_covE, perm_bytes));
-            HMC_TRY(h, hipMalloc(&h->d_cov_avg, sizeof(double) * D));
+            DeviceBuffer<double> covE, cov_avg;
+            HIP_TRY(h, covE.allocate(perm_doubles));
+            HIP_TRY(h, cov_avg.allocate(D));
+            h->d_covE = std::move(covE);
+            h->d_cov_avg = std::move(cov_avg);
             h->cov_dirty = true;
         }
         if (h->cov_dirty) {
             const std::vector<double> perm = hmc_permute(h, h->shared->error.data());
-            HMC_TRY(h, hipMemcpyAsync(h->d_covE, perm.data(), perm_bytes, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(h->d_covE, perm.data(), perm_bytes, hipMemcpyHostToDevice, h->stream));
             if (h->shared_on_device)   // the running average lives on the device
-                HMC_TRY(h, hipMemcpyAsync(h->d_cov_avg, h->d_avg, sizeof(double) * D, hipMemcpyDeviceToDevice, h->stream));
+                HIP_TRY(h, hipMemcpyAsync(h->d_cov_avg, h->d_avg, sizeof(double) * D, hipMemcpyDeviceToDevice, h->stream));
             else
-                HMC_TRY(h, hipMemcpyAsync(h->d_cov_avg, h->shared->average.data(), sizeof(double) * D, hipMemcpyHostToDevice, h->stream));
-            HMC_TRY(h, hipStreamSynchronize(h->stream));   // the staging vector goes out of scope
+                HIP_TRY(h, hipMemcpyAsync(h->d_cov_avg, h->shared->average.data(), sizeof(double) * D, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));   // the staging vector goes out of scope
             h->cov_dirty = false;
         }
     }
@@ -216,36 +193,41 @@ int hmc_generic_buffers(smcmc_hmc* h) {
 
 template <typename T>
 int hmc_fill_lane(smcmc_hmc* h, T* col, T v) {
-    const int threads = 256;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hmc_fill_lane_kernel<T>), dim3((h->nchains + threads - 1) / threads), dim3(threads), 0,
-                       h->stream, col, h->nchains, v);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hfail(h, SMCMC_ERR_HIP, std::string("lane fill launch: ") + hipGetErrorString(e));
+    const hipError_t e = fill<T>(col, (size_t)h->nchains, v, h->stream);
+    if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("lane fill launch: ") + hipGetErrorString(e));
     return SMCMC_OK;
 }
 
-// buffers of the pooled tuning, allocated when it is first needed
+// buffers of the pooled tuning, allocated when it is first needed: all of them or none
 int hmc_tracking_buffers(smcmc_hmc* h) {
     if (h->d_gacc) return SMCMC_OK;
-    const size_t vec = sizeof(double) * (size_t)h->npad * h->dim;
-    HMC_TRY(h, hipMalloc(&h->d_p0, vec));
-    HMC_TRY(h, hipMalloc(&h->d_qprev, vec));
-    HMC_TRY(h, hipMalloc(&h->d_gacc, sizeof(double) * hmc_gacc_doubles(h)));
-    HMC_TRY(h, smcmc::fold_ring_prepare(h->fold, h->dim, h->nchains, h->npad, h->fold_nslices, h->slice_chains));
-    HMC_TRY(h, hipMalloc(&h->d_moments, sizeof(double) * hmc_npacked(h)));
-    HMC_TRY(h, hipMalloc(&h->d_zero, sizeof(double) * h->dim));
-    HMC_TRY(h, hipHostMalloc((void**)&h->h_moments, sizeof(double) * hmc_npacked(h), hipHostMallocDefault));
-    HMC_TRY(h, hipMalloc(&h->d_avg, sizeof(double) * h->dim));
-    HMC_TRY(h, hipMalloc(&h->d_exxt, sizeof(double) * (size_t)h->dim * h->dim));
-    HMC_TRY(h, hipMalloc(&h->d_hcov, sizeof(double) * (size_t)h->dim * h->dim));
-    HMC_TRY(h, hipMalloc(&h->d_hscal, sizeof(double) * 8));
-    HMC_TRY(h, hipHostMalloc((void**)&h->h_hscal, sizeof(double) * 8, hipHostMallocDefault));
+    const size_t vec = (size_t)h->npad * h->dim;
+    DeviceBuffer<double> p0, qprev, gacc, moments, zero, avg, exxt, hcov, hscal;
+    PinnedBuffer<double> hmoments, hhscal;
+    smcmc::FoldRing fold;
+    HIP_TRY(h, p0.allocate(vec));
+    HIP_TRY(h, qprev.allocate(vec));
+    HIP_TRY(h, gacc.allocate(hmc_gacc_doubles(h)));
+    HIP_TRY(h, smcmc::fold_ring_prepare(fold, h->dim, h->nchains, h->npad, h->fold_nslices, h->slice_chains));
+    HIP_TRY(h, moments.allocate(hmc_npacked(h)));
+    HIP_TRY(h, zero.allocate(h->dim));
+    HIP_TRY(h, hmoments.allocate(hmc_npacked(h)));
+    HIP_TRY(h, avg.allocate(h->dim));
+    HIP_TRY(h, exxt.allocate((size_t)h->dim * h->dim));
+    HIP_TRY(h, hcov.allocate((size_t)h->dim * h->dim));
+    HIP_TRY(h, hscal.allocate(8));
+    HIP_TRY(h, hhscal.allocate(8));
+    HIP_TRY(h, hipMemsetAsync(p0, 0, sizeof(double) * vec, h->stream));
+    HIP_TRY(h, hipMemsetAsync(qprev, 0, sizeof(double) * vec, h->stream));
+    HIP_TRY(h, hipMemsetAsync(gacc, 0, sizeof(double) * hmc_gacc_doubles(h), h->stream));
+    HIP_TRY(h, hipMemsetAsync(moments, 0, sizeof(double) * hmc_npacked(h), h->stream));
+    HIP_TRY(h, hipMemsetAsync(zero, 0, sizeof(double) * h->dim, h->stream));
+    h->d_p0 = std::move(p0); h->d_qprev = std::move(qprev); h->d_gacc = std::move(gacc);
+    h->fold = std::move(fold);
+    h->d_moments = std::move(moments); h->d_zero = std::move(zero); h->h_moments = std::move(hmoments);
+    h->d_avg = std::move(avg); h->d_exxt = std::move(exxt); h->d_hcov = std::move(hcov);
+    h->d_hscal = std::move(hscal); h->h_hscal = std::move(hhscal);
     h->shared_on_device = false;
-    HMC_TRY(h, hipMemsetAsync(h->d_p0, 0, vec, h->stream));
-    HMC_TRY(h, hipMemsetAsync(h->d_qprev, 0, vec, h->stream));
-    HMC_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * hmc_gacc_doubles(h), h->stream));
-    HMC_TRY(h, hipMemsetAsync(h->d_moments, 0, sizeof(double) * hmc_npacked(h), h->stream));
-    HMC_TRY(h, hipMemsetAsync(h->d_zero, 0, sizeof(double) * h->dim, h->stream));
     return SMCMC_OK;
 }
 
@@ -307,11 +289,11 @@ int hmc_push(smcmc_hmc* h) {
     const HmcShared& S = *h->shared;
     const size_t D = (size_t)h->dim;
     double sc[kHsCount] = {0.0, S.averageTrials, S.covTrials, 0.0};
-    HMC_TRY(h, hipMemcpyAsync(h->d_avg, S.average.data(), D * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HMC_TRY(h, hipMemcpyAsync(h->d_exxt, S.exxt.data(), D * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HMC_TRY(h, hipMemcpyAsync(h->d_hcov, S.cov.data(), D * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HMC_TRY(h, hipMemcpyAsync(h->d_hscal, sc, sizeof(sc), hipMemcpyHostToDevice, h->stream));
-    HMC_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_avg, S.average.data(), D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_exxt, S.exxt.data(), D * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_hcov, S.cov.data(), D * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_hscal, sc, sizeof(sc), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->host_stale = false;
     return SMCMC_OK;
 }
@@ -321,10 +303,10 @@ int hmc_pull(smcmc_hmc* h) {
     if (!h->host_stale) return SMCMC_OK;
     HmcShared& S = *h->shared;
     const size_t D = (size_t)h->dim;
-    HMC_TRY(h, hipStreamSynchronize(h->stream));
-    HMC_TRY(h, hipMemcpy(S.average.data(), h->d_avg, D * sizeof(double), hipMemcpyDeviceToHost));
-    HMC_TRY(h, hipMemcpy(S.exxt.data(), h->d_exxt, D * D * sizeof(double), hipMemcpyDeviceToHost));
-    HMC_TRY(h, hipMemcpy(S.cov.data(), h->d_hcov, D * D * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(S.average.data(), h->d_avg, D * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(S.exxt.data(), h->d_exxt, D * D * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(S.cov.data(), h->d_hcov, D * D * sizeof(double), hipMemcpyDeviceToHost));
     h->host_stale = false;
     return SMCMC_OK;
 }
@@ -335,12 +317,12 @@ int hmc_reduce(smcmc_hmc* h) {
     // d_moments holds ONE reduction: a second one (an explicit smcmc_hmc_reduce_moments, or the sync a step triggers
     // between a caller's reduce / import and its apply) would overwrite moments that no update has absorbed yet
     if (h->steps_reduced > 0)
-        return hfail(h, SMCMC_ERR_LOGIC, "moments of an earlier smcmc_hmc_reduce_moments are waiting for smcmc_hmc_apply_moments");
+        return fail(h, SMCMC_ERR_LOGIC, "moments of an earlier smcmc_hmc_reduce_moments are waiting for smcmc_hmc_apply_moments");
     h->steps_reduced += h->steps_in_window;
     h->steps_in_window = 0;
     hipError_t e = launch_fold_reduce(h->d_gacc, h->dim, h->fold_nslices, h->d_moments, h->stream);
-    if (e != hipSuccess) return hfail(h, SMCMC_ERR_HIP, std::string("fold reduce launch: ") + hipGetErrorString(e));
-    HMC_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * hmc_gacc_doubles(h), h->stream));
+    if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("fold reduce launch: ") + hipGetErrorString(e));
+    HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * hmc_gacc_doubles(h), h->stream));
     return SMCMC_OK;
 }
 
@@ -375,9 +357,9 @@ int hmc_apply(smcmc_hmc* h) {
     hipLaunchKernelGGL(hmc_absorb_scalars_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)h->d_moments, D,
                        (const double*)h->d_hcov, h->d_hscal, S.covWindow);
     e = hipGetLastError();
-    if (e != hipSuccess) return hfail(h, SMCMC_ERR_HIP, std::string("absorb launch: ") + hipGetErrorString(e));
-    HMC_TRY(h, hipMemcpyAsync(h->h_hscal, h->d_hscal, sizeof(double) * kHsCount, hipMemcpyDeviceToHost, h->stream));
-    HMC_TRY(h, hipStreamSynchronize(h->stream));
+    if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("absorb launch: ") + hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(h->h_hscal, h->d_hscal, sizeof(double) * kHsCount, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (!(h->h_hscal[kHsN] > 0.0)) return SMCMC_OK;
     S.stepCount = (int)h->step_count;
     S.leapfrogZero = (h->leapfrog == 0);
@@ -398,7 +380,7 @@ int hmc_apply(smcmc_hmc* h) {
                            h->d_lane_f64, h->d_lane_i32, h->npad, h->nchains, S.maxScale, S.minScale, S.orbitLength,
                            h->dim);
         e = hipGetLastError();
-        if (e != hipSuccess) return hfail(h, SMCMC_ERR_HIP, std::string("retune launch: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("retune launch: ") + hipGetErrorString(e));
     }
     return SMCMC_OK;
 }
@@ -414,22 +396,29 @@ hipError_t hmc_dispatch(smcmc_hmc* h, const HmcParams& p) {
 // ---- SMCMC_MODE_PER_CHAIN ----
 bool hmc_per_chain(const smcmc_hmc* h) { return h->mode == SMCMC_MODE_PER_CHAIN; }
 
-// buffers of the per-chain tuning, allocated at the first Start in this mode
+// buffers of the per-chain tuning, allocated at the first Start in this mode: all of them or none
 int hmc_pc_buffers(smcmc_hmc* h) {
     if (h->d_pc_scal) return SMCMC_OK;
     const size_t D = (size_t)h->dim, NP = (size_t)h->npad;
     // the error kernel's grid: enough workgroups to cover the CUs a few times over; a D x D image each beyond LDS
     int grid = std::min(1024, h->nchains);
     if (h->dim > kPcLdsDim) grid = std::min<size_t>(grid, std::max<size_t>(1, ((size_t)256 << 20) / (D * D * sizeof(double))));
-    h->pc_grid = std::max(1, grid);
-    if (!h->d_p0) HMC_TRY(h, hipMalloc(&h->d_p0, sizeof(double) * D * NP));
-    if (!h->d_qprev) HMC_TRY(h, hipMalloc(&h->d_qprev, sizeof(double) * D * NP));
-    HMC_TRY(h, hipMalloc(&h->d_pc_avg, sizeof(double) * D * NP));
-    HMC_TRY(h, hipMalloc(&h->d_pc_exxt, sizeof(double) * pc_npacked(h->dim) * NP));
-    HMC_TRY(h, hipMalloc(&h->d_pc_covdiag, sizeof(double) * D * NP));
-    HMC_TRY(h, hipMalloc(&h->d_pc_work, sizeof(int32_t) * (NP + 1)));
-    if (h->dim > kPcLdsDim) HMC_TRY(h, hipMalloc(&h->d_pc_scratch, sizeof(double) * D * D * (size_t)h->pc_grid));
-    HMC_TRY(h, hipMalloc(&h->d_pc_scal, sizeof(double) * kPcCount * NP));
+    grid = std::max(1, grid);
+    DeviceBuffer<double> p0, qprev, avg, exxt, covdiag, scratch, scal;
+    DeviceBuffer<int32_t> work;
+    if (!h->d_p0) HIP_TRY(h, p0.allocate(D * NP));
+    if (!h->d_qprev) HIP_TRY(h, qprev.allocate(D * NP));
+    HIP_TRY(h, avg.allocate(D * NP));
+    HIP_TRY(h, exxt.allocate(pc_npacked(h->dim) * NP));
+    HIP_TRY(h, covdiag.allocate(D * NP));
+    HIP_TRY(h, work.allocate(NP + 1));
+    if (h->dim > kPcLdsDim) HIP_TRY(h, scratch.allocate(D * D * (size_t)grid));
+    HIP_TRY(h, scal.allocate(kPcCount * NP));
+    if (p0) h->d_p0 = std::move(p0);
+    if (qprev) h->d_qprev = std::move(qprev);
+    h->d_pc_avg = std::move(avg); h->d_pc_exxt = std::move(exxt); h->d_pc_covdiag = std::move(covdiag);
+    h->d_pc_work = std::move(work); h->d_pc_scratch = std::move(scratch); h->d_pc_scal = std::move(scal);
+    h->pc_grid = grid;
     return SMCMC_OK;
 }
 
@@ -441,15 +430,15 @@ int hmc_pc_start(smcmc_hmc* h, const std::vector<double>& x) {
         return st;
     }
     const size_t D = (size_t)h->dim, NP = (size_t)h->npad;
-    HMC_TRY(h, hipMemcpyAsync(h->d_pc_avg, x.data(), sizeof(double) * D * NP, hipMemcpyHostToDevice, h->stream));
-    HMC_TRY(h, hipMemsetAsync(h->d_pc_exxt, 0, sizeof(double) * pc_npacked(h->dim) * NP, h->stream));
-    HMC_TRY(h, hipMemsetAsync(h->d_pc_covdiag, 0, sizeof(double) * D * NP, h->stream));
-    HMC_TRY(h, hipMemsetAsync(h->d_pc_work, 0, sizeof(int32_t) * (NP + 1), h->stream));
-    HMC_TRY(h, hipMemsetAsync(h->d_qprev, 0, sizeof(double) * D * NP, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_pc_avg, x.data(), sizeof(double) * D * NP, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_pc_exxt, 0, sizeof(double) * pc_npacked(h->dim) * NP, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_pc_covdiag, 0, sizeof(double) * D * NP, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_pc_work, 0, sizeof(int32_t) * (NP + 1), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_qprev, 0, sizeof(double) * D * NP, h->stream));
     std::vector<double> scal((size_t)kPcCount * NP, 0.0);
     for (size_t c = 0; c < NP; ++c) scal[(size_t)kPcEstTrace * NP + c] = (double)D;   // fEstimatedCovarianceTrace = dim
-    HMC_TRY(h, hipMemcpyAsync(h->d_pc_scal, scal.data(), sizeof(double) * scal.size(), hipMemcpyHostToDevice, h->stream));
-    HMC_TRY(h, hipStreamSynchronize(h->stream));   // the staging vectors go out of scope
+    HIP_TRY(h, hipMemcpyAsync(h->d_pc_scal, scal.data(), sizeof(double) * scal.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // the staging vectors go out of scope
     return SMCMC_OK;
 }
 
@@ -472,23 +461,23 @@ int hmc_pc_update(smcmc_hmc* h) {
     hipLaunchKernelGGL(hmc_pc_decide_kernel, dim3((h->nchains + 255) / 256), dim3(256), 0, h->stream, q);
     hipLaunchKernelGGL(hmc_pc_error_kernel, dim3(h->pc_grid), dim3(kWave), 0, h->stream, q);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hfail(h, SMCMC_ERR_HIP, std::string("per-chain tuning launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("per-chain tuning launch: ") + hipGetErrorString(e));
     return SMCMC_OK;
 }
 
 // chain c's fAveragePoint, fEstimatedCovariance and tuning scalars (any pointer may be null)
 int hmc_pc_read(smcmc_hmc* h, int c, double* average, double* covariance, double* tuning) {
-    if (!h->started || !h->d_pc_scal) return hfail(h, SMCMC_ERR_LOGIC, "the per-chain tuning starts with Start");
+    if (!h->started || !h->d_pc_scal) return fail(h, SMCMC_ERR_LOGIC, "the per-chain tuning starts with Start");
     const int D = h->dim;
     const size_t NP = (size_t)h->npad;
-    HMC_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     double sc[kPcCount];
-    HMC_TRY(h, hipMemcpy2D(sc, sizeof(double), h->d_pc_scal + c, NP * sizeof(double), sizeof(double), kPcCount,
+    HIP_TRY(h, hipMemcpy2D(sc, sizeof(double), h->d_pc_scal + c, NP * sizeof(double), sizeof(double), kPcCount,
                            hipMemcpyDeviceToHost));
     if (tuning) std::copy(sc, sc + kPcTuningFields, tuning);
     std::vector<double> avg((size_t)D);
     if (average || covariance)
-        HMC_TRY(h, hipMemcpy2D(avg.data(), sizeof(double), h->d_pc_avg + c, NP * sizeof(double), sizeof(double), (size_t)D,
+        HIP_TRY(h, hipMemcpy2D(avg.data(), sizeof(double), h->d_pc_avg + c, NP * sizeof(double), sizeof(double), (size_t)D,
                                hipMemcpyDeviceToHost));
     if (average) std::copy(avg.begin(), avg.end(), average);
     if (!covariance) return SMCMC_OK;
@@ -497,13 +486,13 @@ int hmc_pc_read(smcmc_hmc* h, int c, double* average, double* covariance, double
             for (int j = 0; j < D; ++j) covariance[(size_t)i * D + j] = (i == j) ? 1.0 : 0.0;
     } else if (sc[kPcCovState] != 0.0) {                                 // what the repair loop left (:793-808)
         std::vector<double> dg((size_t)D);
-        HMC_TRY(h, hipMemcpy2D(dg.data(), sizeof(double), h->d_pc_covdiag + c, NP * sizeof(double), sizeof(double),
+        HIP_TRY(h, hipMemcpy2D(dg.data(), sizeof(double), h->d_pc_covdiag + c, NP * sizeof(double), sizeof(double),
                                (size_t)D, hipMemcpyDeviceToHost));
         for (int i = 0; i < D; ++i)
             for (int j = 0; j < D; ++j) covariance[(size_t)i * D + j] = (i == j) ? dg[i] : 0.0;
     } else {                                                             // :689
         std::vector<double> ex(pc_npacked(D));
-        HMC_TRY(h, hipMemcpy2D(ex.data(), sizeof(double), h->d_pc_exxt + c, NP * sizeof(double), sizeof(double), ex.size(),
+        HIP_TRY(h, hipMemcpy2D(ex.data(), sizeof(double), h->d_pc_exxt + c, NP * sizeof(double), sizeof(double), ex.size(),
                                hipMemcpyDeviceToHost));
         for (int i = 0; i < D; ++i)
             for (int j = 0; j <= i; ++j)
@@ -542,44 +531,32 @@ int smcmc_hmc_create(int dim, int nchains, int likelihood, uint64_t seed, uint32
     h->slice_chains = ((h->npad / kWave + h->fold_nslices - 1) / h->fold_nslices) * kWave;
     h->shared = new HmcShared(dim);
     *out = h;
-    HMC_ON_DEVICE(h);
+    ON_DEVICE(h);
     const size_t vec = sizeof(double) * (size_t)h->npad * dim;
-    HMC_TRY(h, hipMalloc(&h->d_q, vec));
-    HMC_TRY(h, hipMalloc(&h->d_pm, vec));
-    HMC_TRY(h, hipMalloc(&h->d_qn, vec));
-    HMC_TRY(h, hipMalloc(&h->d_pn, vec));
+    HIP_TRY(h, h->d_q.allocate((size_t)h->npad * dim));
+    HIP_TRY(h, h->d_pm.allocate((size_t)h->npad * dim));
+    HIP_TRY(h, h->d_qn.allocate((size_t)h->npad * dim));
+    HIP_TRY(h, h->d_pn.allocate((size_t)h->npad * dim));
     const size_t e_doubles = std::max({(size_t)h->W * dim * kPanelCW, hmc_mfma_eop_doubles(dim), hmc_exact_ex_doubles(dim)});
-    HMC_TRY(h, hipMalloc(&h->d_E, sizeof(double) * e_doubles));
-    HMC_TRY(h, hipMalloc(&h->d_like, sizeof(double) * hmc_like_doubles(dim)));
-    HMC_TRY(h, hipMalloc(&h->d_lane_f64, sizeof(double) * (size_t)h->npad * SMCMC_LANE_F64_COUNT_));
-    HMC_TRY(h, hipMalloc(&h->d_lane_i32, sizeof(int32_t) * (size_t)h->npad * SMCMC_LANE_I32_COUNT_));
-    HMC_TRY(h, hipMemset(h->d_q, 0, vec));
-    HMC_TRY(h, hipMemset(h->d_pm, 0, vec));
-    HMC_TRY(h, hipMemset(h->d_qn, 0, vec));
-    HMC_TRY(h, hipMemset(h->d_pn, 0, vec));
-    HMC_TRY(h, hipMemset(h->d_E, 0, sizeof(double) * e_doubles));
-    HMC_TRY(h, hipMemset(h->d_like, 0, sizeof(double) * hmc_like_doubles(dim)));
-    HMC_TRY(h, hipMemset(h->d_lane_f64, 0, sizeof(double) * (size_t)h->npad * SMCMC_LANE_F64_COUNT_));
-    HMC_TRY(h, hipMemset(h->d_lane_i32, 0, sizeof(int32_t) * (size_t)h->npad * SMCMC_LANE_I32_COUNT_));
+    HIP_TRY(h, h->d_E.allocate(e_doubles));
+    HIP_TRY(h, h->d_like.allocate(hmc_like_doubles(dim)));
+    HIP_TRY(h, h->d_lane_f64.allocate((size_t)h->npad * SMCMC_LANE_F64_COUNT_));
+    HIP_TRY(h, h->d_lane_i32.allocate((size_t)h->npad * SMCMC_LANE_I32_COUNT_));
+    HIP_TRY(h, hipMemset(h->d_q, 0, vec));
+    HIP_TRY(h, hipMemset(h->d_pm, 0, vec));
+    HIP_TRY(h, hipMemset(h->d_qn, 0, vec));
+    HIP_TRY(h, hipMemset(h->d_pn, 0, vec));
+    HIP_TRY(h, hipMemset(h->d_E, 0, sizeof(double) * e_doubles));
+    HIP_TRY(h, hipMemset(h->d_like, 0, sizeof(double) * hmc_like_doubles(dim)));
+    HIP_TRY(h, hipMemset(h->d_lane_f64, 0, sizeof(double) * (size_t)h->npad * SMCMC_LANE_F64_COUNT_));
+    HIP_TRY(h, hipMemset(h->d_lane_i32, 0, sizeof(int32_t) * (size_t)h->npad * SMCMC_LANE_I32_COUNT_));
     return SMCMC_OK;
 }
 
 int smcmc_hmc_destroy(smcmc_hmc* h) {
     if (!h) return SMCMC_OK;
-    HMC_ON_DEVICE(h);
+    ON_DEVICE(h);
     if (h->d_q) (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(h->d_q); (void)hipFree(h->d_pm); (void)hipFree(h->d_qn); (void)hipFree(h->d_pn);
-    (void)hipFree(h->d_E); (void)hipFree(h->d_like); (void)hipFree(h->d_lane_f64); (void)hipFree(h->d_lane_i32);
-    (void)hipFree(h->d_p0); (void)hipFree(h->d_qprev); (void)hipFree(h->d_gacc); (void)hipFree(h->d_moments);
-    smcmc::fold_ring_release(h->fold);
-    (void)hipFree(h->d_zero); (void)hipFree(h->d_Eperm); (void)hipFree(h->d_covE); (void)hipFree(h->d_cov_avg);
-    (void)hipFree(h->d_avg); (void)hipFree(h->d_exxt); (void)hipFree(h->d_hcov); (void)hipFree(h->d_hscal);
-    (void)hipHostFree(h->h_hscal);
-    (void)hipFree(h->d_fd_grad);
-    (void)hipHostFree(h->h_moments);
-    (void)hipFree(h->d_pc_avg); (void)hipFree(h->d_pc_exxt); (void)hipFree(h->d_pc_covdiag); (void)hipFree(h->d_pc_scal);
-    (void)hipFree(h->d_pc_scratch); (void)hipFree(h->d_pc_work);
-    delete h->shared;
     delete h;
     return SMCMC_OK;
 }
@@ -600,7 +577,7 @@ int smcmc_hmc_set_likelihood_params(smcmc_hmc* h, const double* params, int coun
 
 int smcmc_hmc_set_exact_arithmetic(smcmc_hmc* h, int exact) {
     if (!h) return SMCMC_ERR_INVALID;
-    if (h->started) return hfail(h, SMCMC_ERR_LOGIC, "choose the arithmetic before Start");
+    if (h->started) return fail(h, SMCMC_ERR_LOGIC, "choose the arithmetic before Start");
     h->exact = exact != 0;
     return SMCMC_OK;
 }
@@ -610,14 +587,14 @@ int smcmc_hmc_set_mean_epsilon(smcmc_hmc* h, double e) {
     if (!h) return SMCMC_ERR_INVALID;
     h->mean_epsilon = e;
     if (!h->started) return SMCMC_OK;
-    HMC_ON_DEVICE(h);
+    ON_DEVICE(h);
     return hmc_fill_lane<double>(h, h->d_lane_f64 + (size_t)kHmcLaneMeanEpsilon * h->npad, e);
 }
 int smcmc_hmc_set_leapfrog(smcmc_hmc* h, int n) {
     if (!h) return SMCMC_ERR_INVALID;
     h->leapfrog = -n;
     if (!h->started) return SMCMC_OK;
-    HMC_ON_DEVICE(h);
+    ON_DEVICE(h);
     return hmc_fill_lane<int32_t>(h, h->d_lane_i32 + (size_t)kHmcLaneLeapfrog * h->npad, (int32_t)-n);
 }
 // chain 0's fMeanEpsilon / fLeapFrogSteps (each chain retunes its own unless they are fixed)
@@ -625,19 +602,19 @@ int smcmc_hmc_get_mean_epsilon(smcmc_hmc* h, double* e) {
     if (!h || !e) return SMCMC_ERR_INVALID;
     *e = h->mean_epsilon;
     if (!h->started) return SMCMC_OK;
-    HMC_ON_DEVICE(h);
-    HMC_TRY(h, hipStreamSynchronize(h->stream));
-    HMC_TRY(h, hipMemcpy(e, h->d_lane_f64 + (size_t)kHmcLaneMeanEpsilon * h->npad, sizeof(double), hipMemcpyDeviceToHost));
+    ON_DEVICE(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(e, h->d_lane_f64 + (size_t)kHmcLaneMeanEpsilon * h->npad, sizeof(double), hipMemcpyDeviceToHost));
     return SMCMC_OK;
 }
 int smcmc_hmc_get_leapfrog(smcmc_hmc* h, int* steps) {
     if (!h || !steps) return SMCMC_ERR_INVALID;
     *steps = h->leapfrog;
     if (!h->started) return SMCMC_OK;
-    HMC_ON_DEVICE(h);
+    ON_DEVICE(h);
     int32_t v = 0;
-    HMC_TRY(h, hipStreamSynchronize(h->stream));
-    HMC_TRY(h, hipMemcpy(&v, h->d_lane_i32 + (size_t)kHmcLaneLeapfrog * h->npad, sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(&v, h->d_lane_i32 + (size_t)kHmcLaneLeapfrog * h->npad, sizeof(int32_t), hipMemcpyDeviceToHost));
     *steps = v;
     return SMCMC_OK;
 }
@@ -652,9 +629,9 @@ int smcmc_hmc_set_sync_interval(smcmc_hmc* h, int steps) {
 int smcmc_hmc_set_gradient_type(smcmc_hmc* h, int type) {
     if (!h || type < 0 || type > 5) return SMCMC_ERR_INVALID;
     if (!h->exact && (type == 2 || type == 3 || type == 5))
-        return hfail(h, SMCMC_ERR_UNSUPPORTED, "gradient types 2, 3 and 5 run in reference-order arithmetic only");
+        return fail(h, SMCMC_ERR_UNSUPPORTED, "gradient types 2, 3 and 5 run in reference-order arithmetic only");
     if (type == 2 && hmc_per_chain(h))
-        return hfail(h, SMCMC_ERR_UNSUPPORTED, "the covariant gradient (type 2) is not available in SMCMC_MODE_PER_CHAIN");
+        return fail(h, SMCMC_ERR_UNSUPPORTED, "the covariant gradient (type 2) is not available in SMCMC_MODE_PER_CHAIN");
     h->gradient_type = type;
     return SMCMC_OK;
 }
@@ -668,10 +645,10 @@ int smcmc_hmc_moment_group(const smcmc_hmc* h) { return h ? h->slice_chains : 0;
 int smcmc_hmc_set_mode(smcmc_hmc* h, int mode) {
     if (!h) return SMCMC_ERR_INVALID;
     if (mode != SMCMC_MODE_POOLED && mode != SMCMC_MODE_PER_CHAIN)
-        return hfail(h, SMCMC_ERR_INVALID, "HMC modes: SMCMC_MODE_POOLED, SMCMC_MODE_PER_CHAIN");
-    if (h->started) return hfail(h, SMCMC_ERR_LOGIC, "choose the mode before Start");
+        return fail(h, SMCMC_ERR_INVALID, "HMC modes: SMCMC_MODE_POOLED, SMCMC_MODE_PER_CHAIN");
+    if (h->started) return fail(h, SMCMC_ERR_LOGIC, "choose the mode before Start");
     if (mode == SMCMC_MODE_PER_CHAIN && h->gradient_type == 2)
-        return hfail(h, SMCMC_ERR_UNSUPPORTED, "the covariant gradient (type 2) is not available in SMCMC_MODE_PER_CHAIN");
+        return fail(h, SMCMC_ERR_UNSUPPORTED, "the covariant gradient (type 2) is not available in SMCMC_MODE_PER_CHAIN");
     h->mode = mode;
     return SMCMC_OK;
 }
@@ -685,7 +662,7 @@ int smcmc_hmc_read_chain_tuning(smcmc_hmc* h, int chain, double* average, double
         if (!st && tuning) st = smcmc_hmc_get_tuning(h, tuning);
         return st;
     }
-    HMC_ON_DEVICE(h);
+    ON_DEVICE(h);
     return hmc_pc_read(h, chain, average, covariance, tuning);
 }
 int smcmc_hmc_get_tuning(smcmc_hmc* h, double* out) {
@@ -714,12 +691,15 @@ int smcmc_hmc_get_covariance(smcmc_hmc* h, double* out) {
 
 int smcmc_hmc_start(smcmc_hmc* h, const double* x0, int broadcast) {
     if (!h || !x0) return SMCMC_ERR_INVALID;
-    HMC_ON_DEVICE(h);
+    ON_DEVICE(h);
     const int D = h->dim, N = h->nchains;
     const size_t NP = (size_t)h->npad;
+    // (HORRIFIC reads no parameters: this engine holds what it is given to the user likelihood's limit)
+    std::vector<double> prm;
+    int st = check_like_params(h, h->likelihood == SMCMC_LIKE_HORRIFIC ? (int)SMCMC_LIKE_USER : h->likelihood,
+                               hmc_like_doubles(D), "a user likelihood takes at most dim^2 + 2 dim + 8 parameters", prm);
+    if (st) return st;
     if (h->likelihood == SMCMC_LIKE_QUADFORM) {
-        if ((int)h->like_params.size() != D * D)
-            return hfail(h, SMCMC_ERR_INVALID, "QUADFORM needs dim*dim likelihood parameters (the Error matrix)");
         h->use_mfma = !h->exact && D <= kMfDimMax;
         h->use_matrix_exact = h->exact && D <= kMfDimMax;
         if (h->use_matrix_exact) {
@@ -733,8 +713,8 @@ int smcmc_hmc_start(smcmc_hmc* h, const double* x0, int broadcast) {
                             const int i = 16 * it + 4 * r + rq;
                             if (i < D) ex[((size_t)it * D + j) * 16 + 4 * rq + r] = h->like_params[(size_t)i * D + j];
                         }
-            HMC_TRY(h, hipMemcpyAsync(h->d_E, ex.data(), ex.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HMC_TRY(h, hipStreamSynchronize(h->stream));
+            HIP_TRY(h, hipMemcpyAsync(h->d_E, ex.data(), ex.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
         }
         if (h->use_mfma) {
             // Eop[(tile * nkq + kq) * 64 + lane] = Error(16 tile + (lane & 15), 4 kq + (lane >> 4)): the A operand
@@ -747,64 +727,52 @@ int smcmc_hmc_start(smcmc_hmc* h, const double* x0, int broadcast) {
                         const int i = 16 * it + (l & 15), j = 4 * kq + (l >> 4);
                         if (i < D && j < D) eop[((size_t)it * nkqp + kq) * 64 + l] = h->like_params[(size_t)i * D + j];
                     }
-            HMC_TRY(h, hipMemcpyAsync(h->d_E, eop.data(), eop.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HMC_TRY(h, hipStreamSynchronize(h->stream));
+            HIP_TRY(h, hipMemcpyAsync(h->d_E, eop.data(), eop.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
         }
         // Eperm[w][j][il] = Error(il*W + w, j): the rows a wavefront owns, contiguous per source column j
         const std::vector<double> perm = hmc_permute(h, h->like_params.data());
         if (h->d_Eperm) {
-            HMC_TRY(h, hipMemcpyAsync(h->d_Eperm, perm.data(), perm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HMC_TRY(h, hipStreamSynchronize(h->stream));
+            HIP_TRY(h, hipMemcpyAsync(h->d_Eperm, perm.data(), perm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
         }
         if (!h->use_mfma && !h->use_matrix_exact) {
-            HMC_TRY(h, hipMemcpyAsync(h->d_E, perm.data(), perm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HMC_TRY(h, hipStreamSynchronize(h->stream));
+            HIP_TRY(h, hipMemcpyAsync(h->d_E, perm.data(), perm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
         }
     } else {
         h->use_mfma = false;
         h->use_matrix_exact = false;
     }
     if (hmc_no_own_gradient(h->likelihood)) {
-        std::vector<double> prm = h->like_params;
-        if (h->likelihood == SMCMC_LIKE_ASYM) {
-            if (prm.empty()) prm = {-1.0, 100.0};                                  // TAsymLogLikelihood.H:17-18
-            if (prm.size() != 2) return hfail(h, SMCMC_ERR_INVALID, "ASYM takes {positiveSlope, negativeSlope}");
-        } else if (h->likelihood == SMCMC_LIKE_CONSTRAINED) {
-            if ((int)prm.size() != 2 + 2 * D)
-                return hfail(h, SMCMC_ERR_INVALID,
-                             "CONSTRAINED needs {SummedValues, SummedConstraint, ExpectedValues[dim], PriorConstraints[dim]}");
-        } else if (prm.size() > hmc_like_doubles(D)) {
-            return hfail(h, SMCMC_ERR_INVALID, "a user likelihood takes at most dim^2 + 2 dim + 8 parameters");
-        }
         if (!prm.empty())
-            HMC_TRY(h, hipMemcpyAsync(h->d_like, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HMC_TRY(h, hipStreamSynchronize(h->stream));
+            HIP_TRY(h, hipMemcpyAsync(h->d_like, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
     } else {
-        double b = 100.0;
-        if (h->likelihood == SMCMC_LIKE_ROSENBROCK && !h->like_params.empty()) b = h->like_params[0];
-        HMC_TRY(h, hipMemcpyAsync(h->d_like, &b, sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HMC_TRY(h, hipStreamSynchronize(h->stream));
+        const double b = prm.empty() ? 100.0 : prm[0];   // ROSENBROCK's, or the unused default of the others
+        HIP_TRY(h, hipMemcpyAsync(h->d_like, &b, sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     std::vector<double> x(NP * D, 0.0);
     for (int d = 0; d < D; ++d)
         for (int c = 0; c < N; ++c) x[(size_t)d * NP + c] = broadcast ? x0[d] : x0[(size_t)d * N + c];
-    HMC_TRY(h, hipMemcpyAsync(h->d_q, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HMC_TRY(h, hipMemsetAsync(h->d_pm, 0, sizeof(double) * NP * D, h->stream));
-    HMC_TRY(h, hipMemsetAsync(h->d_lane_f64, 0, sizeof(double) * NP * SMCMC_LANE_F64_COUNT_, h->stream));
-    HMC_TRY(h, hipMemsetAsync(h->d_lane_i32, 0, sizeof(int32_t) * NP * SMCMC_LANE_I32_COUNT_, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_q, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_pm, 0, sizeof(double) * NP * D, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_lane_f64, 0, sizeof(double) * NP * SMCMC_LANE_F64_COUNT_, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_lane_i32, 0, sizeof(int32_t) * NP * SMCMC_LANE_I32_COUNT_, h->stream));
     h->step_count = 0;                                   // :211
     h->mean_epsilon = 0.05;                              // :229
     HmcParams p = hmc_params(h, 0, 1);
     hipError_t e = hmc_dispatch(h, p);
-    if (e != hipSuccess) return hfail(h, SMCMC_ERR_HIP, std::string("hmc start launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("hmc start launch: ") + hipGetErrorString(e));
     // fCurrentAcceptance = fTargetAcceptance = 0.65 (:234-235)
     std::vector<double> acc(NP, 0.0);
     for (int c = 0; c < N; ++c) acc[c] = 0.65;
-    HMC_TRY(h, hipMemcpyAsync(h->d_lane_f64 + (size_t)SMCMC_LANE_ACCEPTANCE * NP, acc.data(), NP * sizeof(double),
+    HIP_TRY(h, hipMemcpyAsync(h->d_lane_f64 + (size_t)SMCMC_LANE_ACCEPTANCE * NP, acc.data(), NP * sizeof(double),
                               hipMemcpyHostToDevice, h->stream));
-    HMC_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     // every chain's own fMeanEpsilon = 0.05 (:229), fLeapFrogSteps as the constructor / SetLeapFrog left it, fReversalLen = 0
-    int st = hmc_fill_lane<double>(h, h->d_lane_f64 + (size_t)kHmcLaneMeanEpsilon * NP, h->mean_epsilon);
+    st = hmc_fill_lane<double>(h, h->d_lane_f64 + (size_t)kHmcLaneMeanEpsilon * NP, h->mean_epsilon);
     if (st) return st;
     st = hmc_fill_lane<int32_t>(h, h->d_lane_i32 + (size_t)kHmcLaneLeapfrog * NP, (int32_t)h->leapfrog);
     if (st) return st;
@@ -820,21 +788,21 @@ int smcmc_hmc_start(smcmc_hmc* h, const double* x0, int broadcast) {
     h->host_stale = false;
     h->cov_dirty = true;
     h->steps_in_window = 0;
-    if (h->d_gacc) HMC_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * hmc_gacc_doubles(h), h->stream));
+    if (h->d_gacc) HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * hmc_gacc_doubles(h), h->stream));
     h->started = true;
     return SMCMC_OK;
 }
 
 int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
     if (!h) return SMCMC_ERR_INVALID;
-    if (!h->started) return hfail(h, SMCMC_ERR_INVALID, "Must initialize starting point");   // :280-284
+    if (!h->started) return fail(h, SMCMC_ERR_INVALID, "Must initialize starting point");   // :280-284
     if (nsteps <= 0) return SMCMC_OK;
-    HMC_ON_DEVICE(h);
+    ON_DEVICE(h);
     if (hmc_no_own_gradient(h->likelihood) && !hmc_generic_gradient(h))
-        return hfail(h, SMCMC_ERR_RUNTIME, "the likelihood has no gradient (TSimpleHMC.H:85-89: its functor returns false): "
+        return fail(h, SMCMC_ERR_RUNTIME, "the likelihood has no gradient (TSimpleHMC.H:85-89: its functor returns false): "
                                            "choose gradient type 2 (covariant), 3 (finite differences) or 5 (none)");
     if (hmc_generic_gradient(h)) {
-        if (!h->exact) return hfail(h, SMCMC_ERR_UNSUPPORTED, "gradient types 2, 3 and 5 run in reference-order arithmetic only");
+        if (!h->exact) return fail(h, SMCMC_ERR_UNSUPPORTED, "gradient types 2, 3 and 5 run in reference-order arithmetic only");
         int gst = hmc_generic_buffers(h);
         if (gst) return gst;
     }
@@ -844,7 +812,7 @@ int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
             HmcParams p = hmc_params(h, 1, 0);
             p.adaptive = 1;
             hipError_t e = hmc_dispatch(h, p);
-            if (e != hipSuccess) return hfail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
+            if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
             h->step_count += 1u;
             int st = hmc_pc_update(h);
             if (st) return st;
@@ -855,7 +823,7 @@ int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
         // fixed step length and leapfrog count: the chains share nothing, one launch runs all the steps
         HmcParams p = hmc_params(h, nsteps, 0);
         hipError_t e = hmc_dispatch(h, p);
-        if (e != hipSuccess) return hfail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
         h->step_count += (uint32_t)nsteps;
         return SMCMC_OK;
     }
@@ -869,7 +837,7 @@ int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
         HmcParams p = hmc_params(h, 1, 0);
         p.adaptive = 1;
         hipError_t e = hmc_dispatch(h, p);
-        if (e != hipSuccess) return hfail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
         h->step_count += 1u;
         // UpdateCovariance (:338): the point each chain stood on, if its proposal's potential was finite (:336)
         {
@@ -880,7 +848,7 @@ int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
             fp.gacc = h->d_gacc; fp.mask = h->d_lane_i32 + (size_t)kHmcLaneContributes * h->npad;
             e = smcmc::launch_fold_ring(h->fold, fp, h->stream);
         }
-        if (e != hipSuccess) return hfail(h, SMCMC_ERR_HIP, std::string("fold launch: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("fold launch: ") + hipGetErrorString(e));
         if (++h->steps_in_window >= h->sync_every) {
             st = hmc_sync(h);
             if (st) return st;
@@ -894,7 +862,7 @@ int smcmc_hmc_sync(smcmc_hmc* h) {
     if (!h) return SMCMC_ERR_INVALID;
     if (hmc_per_chain(h)) return SMCMC_OK;   // nothing is pooled
     if (!h->started) return SMCMC_ERR_INVALID;
-    HMC_ON_DEVICE(h);
+    ON_DEVICE(h);
     if (!h->d_gacc) return SMCMC_OK;
     return hmc_sync(h);
 }
@@ -904,58 +872,58 @@ int smcmc_hmc_moments_size(const smcmc_hmc* h) { return h ? (int)(((size_t)h->di
 
 int smcmc_hmc_reduce_moments(smcmc_hmc* h) {
     if (!h) return SMCMC_ERR_INVALID;
-    if (hmc_per_chain(h)) return hfail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN pools no moments: shard by chain_offset");
+    if (hmc_per_chain(h)) return fail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN pools no moments: shard by chain_offset");
     if (!h->started) return SMCMC_ERR_INVALID;
-    HMC_ON_DEVICE(h);
+    ON_DEVICE(h);
     int st = hmc_tracking_buffers(h);
     if (st) return st;
     return hmc_reduce(h);
 }
 
 int smcmc_hmc_export_moments(smcmc_hmc* h, double* dst_device) {
-    if (h && hmc_per_chain(h)) return hfail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN pools no moments: shard by chain_offset");
+    if (h && hmc_per_chain(h)) return fail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN pools no moments: shard by chain_offset");
     if (!h || !dst_device || !h->d_moments) return SMCMC_ERR_INVALID;
-    HMC_ON_DEVICE(h);
-    HMC_TRY(h, hipMemcpyAsync(dst_device, h->d_moments, sizeof(double) * (size_t)smcmc_hmc_moments_size(h), hipMemcpyDeviceToDevice,
+    ON_DEVICE(h);
+    HIP_TRY(h, hipMemcpyAsync(dst_device, h->d_moments, sizeof(double) * (size_t)smcmc_hmc_moments_size(h), hipMemcpyDeviceToDevice,
                               h->stream));
     return SMCMC_OK;
 }
 
 int smcmc_hmc_import_moments(smcmc_hmc* h, const double* src_device) {
-    if (h && hmc_per_chain(h)) return hfail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN pools no moments: shard by chain_offset");
+    if (h && hmc_per_chain(h)) return fail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN pools no moments: shard by chain_offset");
     if (!h || !src_device || !h->d_moments) return SMCMC_ERR_INVALID;
-    HMC_ON_DEVICE(h);
-    HMC_TRY(h, hipMemcpyAsync(h->d_moments, src_device, sizeof(double) * (size_t)smcmc_hmc_moments_size(h), hipMemcpyDeviceToDevice,
+    ON_DEVICE(h);
+    HIP_TRY(h, hipMemcpyAsync(h->d_moments, src_device, sizeof(double) * (size_t)smcmc_hmc_moments_size(h), hipMemcpyDeviceToDevice,
                               h->stream));
     return SMCMC_OK;
 }
 
 int smcmc_hmc_apply_moments(smcmc_hmc* h) {
-    if (h && hmc_per_chain(h)) return hfail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN pools no moments: shard by chain_offset");
+    if (h && hmc_per_chain(h)) return fail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN pools no moments: shard by chain_offset");
     if (!h || !h->started || !h->d_moments) return SMCMC_ERR_INVALID;
-    HMC_ON_DEVICE(h);
+    ON_DEVICE(h);
     return hmc_apply(h);
 }
 
 int smcmc_hmc_read_state(smcmc_hmc* h, double* q, double* momentum, double* logl) {
     if (!h) return SMCMC_ERR_INVALID;
-    HMC_ON_DEVICE(h);
+    ON_DEVICE(h);
     const int D = h->dim, N = h->nchains;
     const size_t NP = (size_t)h->npad;
-    HMC_TRY(h, hipStreamSynchronize(h->stream));
-    if (q) HMC_TRY(h, hipMemcpy2D(q, (size_t)N * sizeof(double), h->d_q, NP * sizeof(double), (size_t)N * sizeof(double),
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (q) HIP_TRY(h, hipMemcpy2D(q, (size_t)N * sizeof(double), h->d_q, NP * sizeof(double), (size_t)N * sizeof(double),
                                   (size_t)D, hipMemcpyDeviceToHost));
-    if (momentum) HMC_TRY(h, hipMemcpy2D(momentum, (size_t)N * sizeof(double), h->d_pm, NP * sizeof(double),
+    if (momentum) HIP_TRY(h, hipMemcpy2D(momentum, (size_t)N * sizeof(double), h->d_pm, NP * sizeof(double),
                                          (size_t)N * sizeof(double), (size_t)D, hipMemcpyDeviceToHost));
-    if (logl) HMC_TRY(h, hipMemcpy(logl, h->d_lane_f64 + (size_t)SMCMC_LANE_LOGL * NP, (size_t)N * sizeof(double),
+    if (logl) HIP_TRY(h, hipMemcpy(logl, h->d_lane_f64 + (size_t)SMCMC_LANE_LOGL * NP, (size_t)N * sizeof(double),
                                    hipMemcpyDeviceToHost));
     return SMCMC_OK;
 }
 
 int smcmc_hmc_copy_positions(smcmc_hmc* h, double* dst_device) {
     if (!h || !dst_device || !h->started) return SMCMC_ERR_INVALID;
-    HMC_ON_DEVICE(h);
-    HMC_TRY(h, hipMemcpyAsync(dst_device, h->d_q, sizeof(double) * (size_t)h->dim * h->npad, hipMemcpyDeviceToDevice, h->stream));
+    ON_DEVICE(h);
+    HIP_TRY(h, hipMemcpyAsync(dst_device, h->d_q, sizeof(double) * (size_t)h->dim * h->npad, hipMemcpyDeviceToDevice, h->stream));
     return SMCMC_OK;
 }
 
@@ -963,18 +931,18 @@ int smcmc_hmc_nchains_padded(const smcmc_hmc* h) { return h ? h->npad : 0; }
 
 int smcmc_hmc_read_lane_f64(smcmc_hmc* h, int field, double* out) {
     if (!h || !out || field < 0 || field >= SMCMC_LANE_F64_COUNT_) return SMCMC_ERR_INVALID;
-    HMC_ON_DEVICE(h);
-    HMC_TRY(h, hipStreamSynchronize(h->stream));
-    HMC_TRY(h, hipMemcpy(out, h->d_lane_f64 + (size_t)field * h->npad, (size_t)h->nchains * sizeof(double),
+    ON_DEVICE(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(out, h->d_lane_f64 + (size_t)field * h->npad, (size_t)h->nchains * sizeof(double),
                          hipMemcpyDeviceToHost));
     return SMCMC_OK;
 }
 
 int smcmc_hmc_read_lane_i32(smcmc_hmc* h, int field, int32_t* out) {
     if (!h || !out || field < 0 || field >= SMCMC_LANE_I32_COUNT_) return SMCMC_ERR_INVALID;
-    HMC_ON_DEVICE(h);
-    HMC_TRY(h, hipStreamSynchronize(h->stream));
-    HMC_TRY(h, hipMemcpy(out, h->d_lane_i32 + (size_t)field * h->npad, (size_t)h->nchains * sizeof(int32_t),
+    ON_DEVICE(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(out, h->d_lane_i32 + (size_t)field * h->npad, (size_t)h->nchains * sizeof(int32_t),
                          hipMemcpyDeviceToHost));
     return SMCMC_OK;
 }
@@ -1002,21 +970,15 @@ extern "C" int smcmc_selftest_hmc_error_matrix(int device, int dim, double est_t
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device >= ndev) return SMCMC_ERR_NO_DEVICE;
-    HmcDeviceGuard guard(device);
-    double *d_cov = nullptr, *d_out = nullptr, *d_scratch = nullptr;
-    int st = SMCMC_OK;
-    if (hipMalloc(&d_cov, sizeof(double) * D * D) != hipSuccess || hipMalloc(&d_out, sizeof(double) * nout) != hipSuccess ||
-        hipMalloc(&d_scratch, sizeof(double) * D * D) != hipSuccess) {
-        st = SMCMC_ERR_HIP;
-    } else if (hipMemcpy(d_cov, cov, sizeof(double) * D * D, hipMemcpyHostToDevice) != hipSuccess) {
-        st = SMCMC_ERR_HIP;
-    } else {
-        hipLaunchKernelGGL(hmc_pc_selftest_kernel, dim3(1), dim3(kWave), 0, nullptr, dim, est_trace, (const double*)d_cov,
-                           d_scratch, d_out);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            hipMemcpy(out, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost) != hipSuccess)
-            st = SMCMC_ERR_HIP;
-    }
-    (void)hipFree(d_cov); (void)hipFree(d_out); (void)hipFree(d_scratch);
-    return st;
+    DeviceGuard guard(device);
+    DeviceBuffer<double> d_cov, d_out, d_scratch;
+    if (d_cov.allocate(D * D) != hipSuccess || d_out.allocate(nout) != hipSuccess || d_scratch.allocate(D * D) != hipSuccess)
+        return SMCMC_ERR_HIP;
+    if (hipMemcpy(d_cov, cov, sizeof(double) * D * D, hipMemcpyHostToDevice) != hipSuccess) return SMCMC_ERR_HIP;
+    hipLaunchKernelGGL(hmc_pc_selftest_kernel, dim3(1), dim3(kWave), 0, nullptr, dim, est_trace, (const double*)d_cov,
+                       d_scratch.get(), d_out.get());
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(out, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost) != hipSuccess)
+        return SMCMC_ERR_HIP;
+    return SMCMC_OK;
 }

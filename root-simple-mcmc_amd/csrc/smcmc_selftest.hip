@@ -12,6 +12,7 @@
 
 #include "smcmc.h"
 #include "smcmc_detmath.h"
+#include "smcmc_host.hpp"
 
 namespace {
 
@@ -71,74 +72,54 @@ __global__ void __launch_bounds__(64) mfma_strip_kernel(int K, const double* __r
 
 }  // namespace
 
-#define ST_TRY(expr)                                   \
-    do {                                               \
-        if ((expr) != hipSuccess) { rc = SMCMC_ERR_HIP; goto done; } \
-    } while (0)
+using smcmc::DeviceBuffer;
 
 extern "C" int smcmc_selftest_detmath(int device, int kind, int n, const double* x, const double* y, double* out) {
     if (n <= 0 || !x || !out || kind < 0 || kind > 9) return SMCMC_ERR_INVALID;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return SMCMC_ERR_NO_DEVICE;
-    int rc = SMCMC_OK;
-    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
+    smcmc::DeviceGuard guard(device);
+    DeviceBuffer<double> dx, dy, dout;
     const size_t bytes = sizeof(double) * (size_t)n;
-    ST_TRY(hipSetDevice(device));
-    ST_TRY(hipMalloc(&dx, bytes));
-    ST_TRY(hipMalloc(&dout, bytes));
-    ST_TRY(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice));
-    if (y) {
-        ST_TRY(hipMalloc(&dy, bytes));
-        ST_TRY(hipMemcpy(dy, y, bytes, hipMemcpyHostToDevice));
-    }
-    hipLaunchKernelGGL(detmath_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, kind, n, dx, dy, dout);
-    ST_TRY(hipGetLastError());
-    ST_TRY(hipDeviceSynchronize());
-    ST_TRY(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
-done:
-    (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
-    return rc;
+    if (dx.allocate(n) != hipSuccess || dout.allocate(n) != hipSuccess) return SMCMC_ERR_HIP;
+    if (hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice) != hipSuccess) return SMCMC_ERR_HIP;
+    if (y && (dy.allocate(n) != hipSuccess || hipMemcpy(dy, y, bytes, hipMemcpyHostToDevice) != hipSuccess)) return SMCMC_ERR_HIP;
+    hipLaunchKernelGGL(detmath_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, kind, n, dx.get(), dy.get(), dout.get());
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return SMCMC_ERR_HIP;
+    if (hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost) != hipSuccess) return SMCMC_ERR_HIP;
+    return SMCMC_OK;
 }
 
 extern "C" int smcmc_selftest_mfma(int device, int K, const double* a, const double* b, double* c) {
     if (K <= 0 || (K & 3) || !a || !b || !c) return SMCMC_ERR_INVALID;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return SMCMC_ERR_NO_DEVICE;
-    int rc = SMCMC_OK;
-    double *da = nullptr, *db = nullptr, *dc = nullptr;
-    const size_t ab = sizeof(double) * 16 * (size_t)K;
-    ST_TRY(hipSetDevice(device));
-    ST_TRY(hipMalloc(&da, ab));
-    ST_TRY(hipMalloc(&db, ab));
-    ST_TRY(hipMalloc(&dc, sizeof(double) * 256));
-    ST_TRY(hipMemcpy(da, a, ab, hipMemcpyHostToDevice));
-    ST_TRY(hipMemcpy(db, b, ab, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(mfma_chain_kernel, dim3(1), dim3(64), 0, nullptr, K, da, db, dc);
-    ST_TRY(hipGetLastError());
-    ST_TRY(hipDeviceSynchronize());
-    ST_TRY(hipMemcpy(c, dc, sizeof(double) * 256, hipMemcpyDeviceToHost));
-done:
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dc);
-    return rc;
+    smcmc::DeviceGuard guard(device);
+    DeviceBuffer<double> da, db, dc;
+    const size_t ab = 16 * (size_t)K;
+    if (da.allocate(ab) != hipSuccess || db.allocate(ab) != hipSuccess || dc.allocate(256) != hipSuccess) return SMCMC_ERR_HIP;
+    if (hipMemcpy(da, a, sizeof(double) * ab, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(db, b, sizeof(double) * ab, hipMemcpyHostToDevice) != hipSuccess)
+        return SMCMC_ERR_HIP;
+    hipLaunchKernelGGL(mfma_chain_kernel, dim3(1), dim3(64), 0, nullptr, K, da.get(), db.get(), dc.get());
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return SMCMC_ERR_HIP;
+    if (hipMemcpy(c, dc, sizeof(double) * 256, hipMemcpyDeviceToHost) != hipSuccess) return SMCMC_ERR_HIP;
+    return SMCMC_OK;
 }
 
 extern "C" int smcmc_selftest_mfma_strip(int device, int K, const double* a, const double* b, double* c) {
     if (K <= 0 || (K & 3) || !a || !b || !c) return SMCMC_ERR_INVALID;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return SMCMC_ERR_NO_DEVICE;
-    int rc = SMCMC_OK;
-    double *da = nullptr, *db = nullptr, *dc = nullptr;
-    ST_TRY(hipSetDevice(device));
-    ST_TRY(hipMalloc(&da, sizeof(double) * 4 * (size_t)K));
-    ST_TRY(hipMalloc(&db, sizeof(double) * 16 * (size_t)K));
-    ST_TRY(hipMalloc(&dc, sizeof(double) * 64));
-    ST_TRY(hipMemcpy(da, a, sizeof(double) * 4 * (size_t)K, hipMemcpyHostToDevice));
-    ST_TRY(hipMemcpy(db, b, sizeof(double) * 16 * (size_t)K, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(mfma_strip_kernel, dim3(1), dim3(64), 0, nullptr, K, da, db, dc);
-    ST_TRY(hipGetLastError());
-    ST_TRY(hipDeviceSynchronize());
-    ST_TRY(hipMemcpy(c, dc, sizeof(double) * 64, hipMemcpyDeviceToHost));
-done:
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dc);
-    return rc;
+    smcmc::DeviceGuard guard(device);
+    DeviceBuffer<double> da, db, dc;
+    if (da.allocate(4 * (size_t)K) != hipSuccess || db.allocate(16 * (size_t)K) != hipSuccess || dc.allocate(64) != hipSuccess)
+        return SMCMC_ERR_HIP;
+    if (hipMemcpy(da, a, sizeof(double) * 4 * (size_t)K, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(db, b, sizeof(double) * 16 * (size_t)K, hipMemcpyHostToDevice) != hipSuccess)
+        return SMCMC_ERR_HIP;
+    hipLaunchKernelGGL(mfma_strip_kernel, dim3(1), dim3(64), 0, nullptr, K, da.get(), db.get(), dc.get());
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return SMCMC_ERR_HIP;
+    if (hipMemcpy(c, dc, sizeof(double) * 64, hipMemcpyDeviceToHost) != hipSuccess) return SMCMC_ERR_HIP;
+    return SMCMC_OK;
 }

@@ -279,20 +279,78 @@ def test_refusals(gpu):
         e._check(e._lib.smcmc_set_mode(e._h, gpu.MODE_PER_CHAIN))  # not asked for: refused as before
 
 
-def test_destroyed_engines_return_their_snapshot_memory(gpu):
+def _perchain_wg_snapshot(gpu):
+    dim = _max_dim(gpu)
+    e = gpu.Engine(dim, 64, mode=gpu.MODE_PER_CHAIN, perchain_workgroup=True)
+    assert e.Start(np.zeros(dim))
+    e.Step(2)
+    e.snapshot()
+    e.sync()
+    return e
+
+
+def _pooled_fold_ring(gpu):
+    # the ring of per-step states (8 x 100 x 8 192 doubles, 52 MB) behind the fold of a multi-step launch
+    e = gpu.Engine(100, 8192, mode=gpu.MODE_POOLED)
+    assert e.Start(np.zeros(100))
+    e.Step(16)
+    e.sync()
+    return e
+
+
+def _perchain_record_ladder(gpu):
+    # every chain's adaptive state (10 MB of decompositions), a 5 000-step record (6 MB) and the ladder's staging buffer
+    dim = 50
+    e = gpu.Engine(dim, 512, mode=gpu.MODE_PER_CHAIN)
+    assert e.Start(np.zeros(dim))
+    e.StepRecorded(5000, chain=1)
+    _bad_covariance(e, {}, dim)
+    e.Step(60)
+    assert np.all(e.lane("last_update_path") >= 1), "the ladder must have run in every chain"
+    return e
+
+
+def _hmc_pooled(gpu):
+    # the pooled tuning's buffers: two 100 x 8 192 images (6.5 MB each), the moments and the fold plan
+    e = gpu.HmcEngine(100, 8192)
+    e.Start(np.zeros(100))
+    e.Step(4)
+    e.sync()
+    return e
+
+
+def _hmc_per_chain(gpu):
+    # every chain's running covariance: 1 275 x 4 096 doubles (42 MB)
+    e = gpu.HmcEngine(50, 4096, mode=gpu.MODE_PER_CHAIN)
+    e.Start(np.zeros(50))
+    e.Step(2)
+    return e
+
+
+def _vaat(gpu):
+    # per-dimension widths, acceptances, trials and queues: 50 x 16 384 each (6.5 MB the widths)
+    e = gpu.VaatEngine(50, 16384)
+    e.Start(np.zeros(50))
+    e.Step(10)
+    return e
+
+
+LIFECYCLES = {"perchain_wg_snapshot": _perchain_wg_snapshot, "pooled_d100_fold_ring": _pooled_fold_ring,
+              "perchain_d50_record_ladder": _perchain_record_ladder, "hmc_pooled": _hmc_pooled,
+              "hmc_per_chain": _hmc_per_chain, "vaat": _vaat}
+
+
+@pytest.mark.parametrize("case", list(LIFECYCLES))
+def test_destroyed_engines_return_their_memory(gpu, case):
+    """create -> Start -> steps -> destroy, five times: every buffer an engine allocated, lazily or not, goes back."""
+    import gc
     import torch
-    dim, n = _max_dim(gpu), 64
 
     def one():
-        e = gpu.Engine(dim, n, mode=gpu.MODE_PER_CHAIN, perchain_workgroup=True)
-        assert e.Start(np.zeros(dim))
-        e.Step(2)
-        e._check(e._lib.smcmc_snapshot(e._h))
-        e.sync()
-        e.close() if hasattr(e, "close") else None
+        e = LIFECYCLES[case](gpu)
+        e.close()
         del e
 
-    import gc
     one()
     gc.collect()
     torch.cuda.synchronize()
@@ -302,5 +360,6 @@ def test_destroyed_engines_return_their_snapshot_memory(gpu):
         gc.collect()
     torch.cuda.synchronize()
     free1 = torch.cuda.mem_get_info()[0]
-    # one snapshot of this engine is ~2 x 12 246 x 64 doubles (13 MB) and more: five leaked ones would be > 64 MB
+    # every case holds at least one group of > 5 MB (the snapshot of the first is ~2 x 12 246 x 64 doubles, 13 MB, and
+    # more): five leaked ones would be > 24 MB
     assert free0 - free1 < 24 << 20, f"{(free0 - free1) / 2**20:.1f} MiB not returned"

@@ -112,7 +112,7 @@ static void run_case(const char* name, int D, int nchains, int nsrc, bool masked
                 name, D, nchains, nsrc, (int)masked, nslices, slice_chains, used, maxt, plan.band, foot, plan.max_foot, T, plan.rounds, bad, gacc_n, nonzero,
                 1e3 * ms_old / reps / nsrc, 1e3 * ms_new / reps / nsrc, floor_us);
     std::fflush(stdout);
-    CK(hipFree(dx)); CK(hipFree(dc0)); CK(hipFree(ga)); CK(hipFree(gb)); CK(hipFree(dmask)); fold_ring_release(fr);
+    CK(hipFree(dx)); CK(hipFree(dc0)); CK(hipFree(ga)); CK(hipFree(gb)); CK(hipFree(dmask));
     CK(hipStreamDestroy(s));
 }
 
