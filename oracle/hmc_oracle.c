@@ -658,10 +658,48 @@ void oracle_hmc_ensemble_get_shared(const oracle_hmc_ensemble* e, double* out) {
     out[4] = s->average_trials; out[5] = s->steps_remaining; out[6] = s->steps_since_update; out[7] = s->max_scale;
     out[8] = s->min_scale; out[9] = s->est_trace;
 }
-void oracle_hmc_gradient(int kind, int dim, const double* p, const double* params, double* g) {
+/* The gradient functors on their own (tests/test_truth_cpu.py).  Returns 1 like the reference functors, 0 where the
+ * functor is not defined: THardLogLikelihood.H:40-41 defines the hard likelihood "for two or more dimensions" only
+ * (its :73 reads p[1], :84 p[i-1]), so dim < 2 is refused before anything is read and g is left alone. */
+int oracle_hmc_gradient(int kind, int dim, const double* p, const double* params, double* g) {
     switch (kind) {
-        case ORACLE_LIKE_ISO: hmc_grad_iso(dim, g, p); break;
-        case ORACLE_LIKE_QUADFORM: hmc_grad_quadform(dim, g, p, params); break;
-        default: hmc_grad_rosenbrock(dim, g, p, params ? params[0] : 100.0); break;
+        case ORACLE_LIKE_ISO: return hmc_grad_iso(dim, g, p);
+        case ORACLE_LIKE_QUADFORM: return hmc_grad_quadform(dim, g, p, params);
+        case ORACLE_LIKE_ROSENBROCK:
+            if (dim < 2) return 0;
+            return hmc_grad_rosenbrock(dim, g, p, params ? params[0] : 100.0);
+        default: return 0;
     }
+}
+/* the engine's fused order of the quadratic-form gradient */
+int oracle_hmc_gradient_fused(int dim, const double* p, const double* error, double* g) {
+    return hmc_grad_quadform_fused(dim, g, p, error);
+}
+/* A bare chain has no buffers and no shared state: only dim, like_kind, like_params (read, never written or freed), the
+ * two association flags, gradient_type and the counters are valid.  hmc_potential and hmc_potential_gradient of types
+ * 0 / 1 / 3 / 4 / 5 read nothing else; type 2 reads h->shared and is refused before it gets here.
+ * hmc_potential / hmc_potential_gradient of a chain that is configured and never started: the potential in the
+ * association the flags select, and PotentialGradient of the given type (3: FiniteDifferenceGradient :417-444). */
+static void hmc_bare_chain(oracle_hmc* h, int kind, int dim, const double* params, int potential_from_gradient,
+                           int fused_gradient, int gradient_type) {
+    memset(h, 0, sizeof(*h));
+    h->dim = dim; h->like_kind = kind; h->like_params = (double*)params;
+    h->potential_from_gradient = potential_from_gradient; h->fused_gradient = fused_gradient;
+    h->gradient_type = gradient_type;
+}
+double oracle_hmc_potential(int kind, int dim, const double* p, const double* params, int potential_from_gradient,
+                            int fused_gradient) {
+    oracle_hmc h;
+    hmc_bare_chain(&h, kind, dim, params, potential_from_gradient, fused_gradient, 0);
+    return hmc_potential(&h, p);
+}
+int oracle_hmc_potential_gradient(int kind, int dim, const double* p, const double* params, int gradient_type,
+                                  int potential_from_gradient, int fused_gradient, double* grad) {
+    if (gradient_type == 2) return 0;                        /* the covariant gradient needs a running chain */
+    if (kind == ORACLE_LIKE_ROSENBROCK && dim < 2) return 0;
+    if (kind >= ORACLE_LIKE_ASYM && gradient_type != 3 && gradient_type != 5) return 0;   /* no gradient functor */
+    oracle_hmc h;
+    hmc_bare_chain(&h, kind, dim, params, potential_from_gradient, fused_gradient, gradient_type);
+    hmc_potential_gradient(&h, grad, p);
+    return 1;
 }

@@ -192,7 +192,16 @@ def _declare(L):
         f = getattr(L, "oracle_hmc_get_" + name)
         f.restype = None
         f.argtypes = [C.c_void_p, _dp]
+    L.oracle_hmc_gradient.restype = C.c_int
     L.oracle_hmc_gradient.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp]
+    L.oracle_hmc_gradient_fused.restype = C.c_int
+    L.oracle_hmc_gradient_fused.argtypes = [C.c_int, _dp, _dp, _dp]
+    L.oracle_hmc_potential.restype = C.c_double
+    L.oracle_hmc_potential.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int]
+    L.oracle_hmc_potential_gradient.restype = C.c_int
+    L.oracle_hmc_potential_gradient.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp]
+    L.oracle_loglike_order.restype = C.c_double
+    L.oracle_loglike_order.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int]
     L.oracle_hmc_set_gradient_type.argtypes = [C.c_void_p, C.c_int]
     for name in ("average", "covariance"):
         f = getattr(L, "oracle_hmc_get_" + name)
@@ -703,10 +712,38 @@ class Vaat:
         return out
 
 
-def hmc_gradient(kind, p, params=None):
+def loglike_order(kind, p, params=None, exact=True, rowwise=False):
+    """The likelihood in the engine's arithmetic orders: exact = the reference's (loglike), else the kernels' fused
+    order; rowwise = the matrix-pipe association of the quadratic form (fused order only)."""
+    p = _f64(p); prm = like_params(kind, p.size, params)
+    return lib().oracle_loglike_order(kind, p.size, _p(p), _p(prm) if prm.size else None, int(exact), int(rowwise))
+
+
+def hmc_gradient(kind, p, params=None, fused=False):
+    """grad log L of the smooth likelihoods (the functors' `bool operator()(Vector& g, const Vector& p)`); fused = the
+    engine's fused order of the quadratic form.  None where the functor is not defined (Rosenbrock below two
+    dimensions, THardLogLikelihood.H:40-41; the stress likelihoods have no gradient)."""
     p = _f64(p); prm = like_params(kind, p.size, params); g = np.zeros_like(p)
-    lib().oracle_hmc_gradient(kind, p.size, _p(p), _p(prm) if prm.size else None, _p(g))
-    return g
+    if fused and kind == LIKE_QUADFORM:
+        ok = lib().oracle_hmc_gradient_fused(p.size, _p(p), _p(prm), _p(g))
+    else:
+        ok = lib().oracle_hmc_gradient(kind, p.size, _p(p), _p(prm) if prm.size else None, _p(g))
+    return g if ok else None
+
+
+def hmc_potential(kind, p, params=None, potential_from_gradient=False, fused_gradient=False):
+    """TSimpleHMC's potential -log L (:411-414) in the association the two flags select (see class Hmc)."""
+    p = _f64(p); prm = like_params(kind, p.size, params)
+    return lib().oracle_hmc_potential(kind, p.size, _p(p), _p(prm) if prm.size else None, int(potential_from_gradient),
+                                      int(fused_gradient))
+
+
+def hmc_potential_gradient(kind, p, params=None, gradient_type=0, potential_from_gradient=False, fused_gradient=False):
+    """PotentialGradient (TSimpleHMC.H:467-532) of a bare chain: type 0 the functor's, 3 finite differences, 5 zero."""
+    p = _f64(p); prm = like_params(kind, p.size, params); g = np.zeros_like(p)
+    ok = lib().oracle_hmc_potential_gradient(kind, p.size, _p(p), _p(prm) if prm.size else None, int(gradient_type),
+                                             int(potential_from_gradient), int(fused_gradient), _p(g))
+    return g if ok else None
 
 
 # ---- autocorrelation of a saved trace (MakeAutocorrelation.C:108-148) ------------------------------

@@ -218,6 +218,11 @@ void oracle_step_draws(uint64_t seed, uint32_t chain, uint64_t step, int dim, do
 int oracle_cholesky(int n, const double* A, double* U) { return oracle_cholesky_upper(n, A, U); }
 void oracle_eigen(int n, const double* A, double* vec, double* val) { oracle_sym_eigen(n, A, vec, val); }
 double oracle_loglike(int kind, int dim, const double* p, const double* params) { return oracle_like(kind, dim, p, params); }
+/* the engine's two arithmetic orders (oracle_like_order): exact = the reference's, else the fused one; quadform_rowwise
+ * = the matrix-pipe kernel's association of the quadratic form */
+double oracle_loglike_order(int kind, int dim, const double* p, const double* params, int exact, int quadform_rowwise) {
+    return oracle_like_order(kind, dim, p, params, exact, quadform_rowwise);
+}
 
 /* TDummyLogLikelihood::Init() (TDummyLogLikelihood.H:44-142) for a general
  * dimension: unit variances, VERY_CORRELATED 0.999999 which the std::abs(d) <
