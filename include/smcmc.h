@@ -491,6 +491,43 @@ int smcmc_selftest_hmc_error_matrix(int device, int dim, double est_trace, const
 int smcmc_autocorrelation_sums(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
                                int nchains_padded, const double* centre, double* sum, double* lagged, void* stream);
 
+/* ---- posterior reducer: marginal and pair histograms of a saved trace ----------
+ * TestMarginalization.C says WHAT is histogrammed, in three passes over the entries (here: every slot of every live
+ * chain of trace_device[slot][dim_stride][nchains_padded], as smcmc_step_save, smcmc_vaat_step_save or
+ * smcmc_hmc_copy_positions wrote it; padding lanes and rows >= dim are never read into a result):
+ *   :45-63        ranges: lo[d], hi[d] = min / max of dimension d over a subsample of the entries (the loop's
+ *                 `entry += 0.001*entries` visits every (1 + (int)(0.001 * entries))-th one); absMin = min(1E+20, lo[d]),
+ *                 absMax = max(-1E+20, hi[d]) over all d follow on the host.  Comparisons as std::min / std::max:
+ *                 a NaN never replaces a value (a dimension without any comparable value returns lo = +inf, hi = -inf).
+ *   :66-76, 97-98 a 1-D histogram of 100 bins over [absMin, absMax) for every dimension;
+ *   :78-92, 99-103 for the first min(dim, 10) dimensions and every ordered pair (i, j), (i, i) included, a 50 x 50 histogram,
+ *                 x = dimension i, y = dimension j, each over its own range widened by 5 % of its width on both sides.
+ * Here the bins, the axes and the list of pair dimensions are the caller's.  The binning is ROOT's fixed-width axis
+ * (TAxis::FindBin for equal bins), stated here because ROOT is not available to check it against -- this rule IS the
+ * engine's definition and is NOT pinned against ROOT:
+ *   bin(x; n, lo, hi) = 0                                    if x < lo          (underflow)
+ *                     = n + 1                                if !(x < hi)       (overflow; NaN lands here)
+ *                     = 1 + (int)(n * (x - lo) / (hi - lo))  otherwise
+ * in IEEE double, un-fused, the division correctly rounded.  A value just below hi whose quotient rounds up to n gets
+ * n + 1: the formula's behaviour, kept.  An axis has n + 2 counters, 0 and n + 1 being under- and overflow (ROOT's
+ * layout).  Counters are unsigned 64-bit integers: the macro's TH1F holds floats and stops counting at 2^24, which is
+ * NOT reproduced.  An axis needs finite ends with lo < hi (SMCMC_ERR_INVALID otherwise; the range pass returns an
+ * infinite end when the trace holds one, and the fill then refuses it).
+ *   counts1[d][b]        b = bin(x[t][d][c]; n1, lo1[d], hi1[d])                                    d < dim
+ *   counts2[p][q][a][b]  a = bin(x[t][pair_dims[p]][c]; n2, lo2[p], hi2[p]), b = the same for q     p, q < npair_dims
+ * Host outputs and raw results so that ranks can combine theirs: min / max for ranges, integer addition for counts
+ * (exact: the same counts on every run).  n1 = 0 or counts1 = NULL skips the 1-D part, npair_dims = 0 the pair part;
+ * one of them must be asked for.  `stream` is a hipStream_t or NULL. */
+#define SMCMC_MARGINAL_MAX_BINS1 1000       /* n1: sixteen private copies of the histogram in 64 KB of LDS */
+#define SMCMC_MARGINAL_MAX_BINS2 126        /* n2: two tables of 128 x 128 counters in LDS */
+#define SMCMC_MARGINAL_MAX_PAIR_DIMS 32     /* npair_dims */
+int smcmc_trace_ranges(const double* trace_device, int nslots, int dim, int dim_stride, int nchains, int nchains_padded,
+                       int sample_stride, double* lo, double* hi, void* stream);
+int smcmc_marginal_histograms(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
+                              int nchains_padded, int n1, const double* lo1, const double* hi1, uint64_t* counts1,
+                              int npair_dims, const int32_t* pair_dims, int n2, const double* lo2, const double* hi2,
+                              uint64_t* counts2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

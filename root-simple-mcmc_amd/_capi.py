@@ -45,6 +45,7 @@ HMC_TUNING = ["trace", "orbit", "updates", "cov_trials", "average_trials", "step
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+_up = C.POINTER(C.c_uint64)
 _H = C.c_void_p
 
 class SavedState(C.Structure):
@@ -180,8 +181,12 @@ SIGNATURES = {
     "smcmc_selftest_hmc_error_matrix": (C.c_int, [C.c_int, C.c_int, C.c_double, _dp, _dp]),
     "smcmc_autocorrelation_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                              C.c_void_p]),
+    "smcmc_trace_ranges": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_void_p]),
+    "smcmc_marginal_histograms": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, _dp, _dp, _up, C.c_int, _ip, C.c_int, _dp, _dp, _up, C.c_void_p]),
 }
 AUTOCORR_LAGS = 64
+MARGINAL_MAX_BINS1, MARGINAL_MAX_BINS2, MARGINAL_MAX_PAIR_DIMS = 1000, 126, 32   # SMCMC_MARGINAL_MAX_* of include/smcmc.h
 COMM_ID_BYTES = 128
 
 _lib = None

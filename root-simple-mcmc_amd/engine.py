@@ -269,6 +269,15 @@ class Engine:
                                                          _ptr(s), _ptr(lagged), C.c_void_p(int(stream))))
         return Autocorrelation(s, lagged, int(nslots), self.nchains)
 
+    def Marginals(self, trace_ptr, nslots, n1=100, n2=50, pair_dims=None, sample_stride=None, ranges=None, stream=0):
+        """The histograms of TestMarginalization.C over a trace StepSave wrote, counted on the device: the ranges of the
+        dimensions over every sample_stride-th slot (default: the macro's stride; skipped when `ranges` = (lo, hi) is
+        given, e.g. the merged ranges of several ranks), then n1 bins over [absMin, absMax) for every dimension and
+        n2 x n2 bins for every ordered pair of pair_dims (default: the first min(dim, 10) dimensions) over the
+        dimensions' ranges widened by 5 %.  Returns a Marginals."""
+        return _marginals(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim_padded, self.nchains,
+                          self.nchains_padded, n1, n2, pair_dims, sample_stride, ranges, stream)
+
     def GetAccepted(self):
         x = np.zeros((self.dim, self.nchains))
         self._check(self._lib.smcmc_read_state(self._h, _ptr(x), None))
@@ -409,6 +418,151 @@ class Autocorrelation:
                     break
                 out[d] += 2.0 * pair
         return out
+
+
+class Marginals:
+    """The marginal distributions of a trace as TestMarginalization.C histograms them, from the device counts of
+    smcmc_trace_ranges / smcmc_marginal_histograms (include/smcmc.h has the bin rule):
+      lo, hi [dim]                 the ranges of the dimensions over the sampled slots (macro :45-63)
+      n1, lo1, hi1 [dim]; counts1 [dim][n1 + 2]               the 1-D axes and counts (0 / n1 + 1: under- / overflow)
+      pair_dims [P]; n2, lo2, hi2 [P]; counts2 [P][P][n2 + 2][n2 + 2]   table (p, q): x = pair_dims[p], y = pair_dims[q]
+    Counts are unsigned 64-bit integers and exact.  Counts of several ranks filled on identical axes add (`+`); their
+    ranges combine beforehand with merge_ranges.  Everything derived here is host-side numpy."""
+
+    def __init__(self, lo, hi, nslots, nchains, lo1=None, hi1=None, counts1=None, pair_dims=None, lo2=None, hi2=None,
+                 counts2=None):
+        self.lo, self.hi, self.nslots, self.nchains = _f64(lo), _f64(hi), int(nslots), int(nchains)
+        self.lo1 = None if lo1 is None else _f64(lo1)
+        self.hi1 = None if hi1 is None else _f64(hi1)
+        self.counts1 = None if counts1 is None else np.array(counts1, dtype=np.uint64)
+        self.pair_dims = None if pair_dims is None else np.array(pair_dims, dtype=np.int32)
+        self.lo2 = None if lo2 is None else _f64(lo2)
+        self.hi2 = None if hi2 is None else _f64(hi2)
+        self.counts2 = None if counts2 is None else np.array(counts2, dtype=np.uint64)
+
+    @property
+    def n1(self): return 0 if self.counts1 is None else self.counts1.shape[1] - 2
+
+    @property
+    def n2(self): return 0 if self.counts2 is None else self.counts2.shape[2] - 2
+
+    @staticmethod
+    def _edges(lo, hi, n):
+        return lo[:, None] + (hi - lo)[:, None] * (np.arange(n + 1) / float(n))[None, :]
+
+    @property
+    def edges1(self):
+        """[dim][n1 + 1]: the bin edges of every 1-D axis (for plotting; the counting used the bin rule, not these)."""
+        return None if self.counts1 is None else self._edges(self.lo1, self.hi1, self.n1)
+
+    @property
+    def edges2(self):
+        """[P][n2 + 1]: the bin edges of the axis of every pair dimension."""
+        return None if self.counts2 is None else self._edges(self.lo2, self.hi2, self.n2)
+
+    @staticmethod
+    def _same(a, b):
+        return (a is None and b is None) or (a is not None and b is not None and a.shape == b.shape and np.array_equal(a, b))
+
+    def __add__(self, other):
+        if self.nslots != other.nslots:
+            raise ValueError("traces of different lengths do not pool")
+        for name in ("lo", "hi", "lo1", "hi1", "pair_dims", "lo2", "hi2"):
+            if not self._same(getattr(self, name), getattr(other, name)):
+                raise ValueError("histograms add only on identical bins and ranges (%s differs)" % name)
+        if (self.n1, self.n2) != (other.n1, other.n2):
+            raise ValueError("histograms add only on identical bins and ranges (the numbers of bins differ)")
+        return Marginals(self.lo, self.hi, self.nslots, self.nchains + other.nchains, self.lo1, self.hi1,
+                         None if self.counts1 is None else self.counts1 + other.counts1, self.pair_dims, self.lo2, self.hi2,
+                         None if self.counts2 is None else self.counts2 + other.counts2)
+
+    @staticmethod
+    def merge_ranges(ranges):
+        """(lo, hi) over several ranks' (lo, hi) pairs (or Marginals): the ranges of the whole ensemble."""
+        pairs = [(r.lo, r.hi) if isinstance(r, Marginals) else (_f64(r[0]), _f64(r[1])) for r in ranges]
+        lo, hi = pairs[0][0].copy(), pairs[0][1].copy()
+        for a, b in pairs[1:]:
+            lo, hi = np.minimum(lo, a), np.maximum(hi, b)
+        return lo, hi
+
+    @staticmethod
+    def macro_sample_stride(nslots):
+        """The stride of the macro's range loop (`entry += 0.001*entries` on an int, then ++entry; :54-62)."""
+        return 1 + int(0.001 * int(nslots))
+
+    @staticmethod
+    def macro_axes(lo, hi, pair_dims):
+        """The macro's axes from per-dimension ranges: ((absMin, absMax) of :52-53, 59-60, (lo2, hi2) of the pair
+        dimensions: the dimension's range widened by 5 % of its width on both sides, :85-89)."""
+        lo, hi = _f64(lo), _f64(hi)
+        abs_min = min(1e20, float(np.min(lo)))
+        abs_max = max(-1e20, float(np.max(hi)))
+        p = np.asarray(pair_dims, dtype=np.int64)
+        r = 0.05 * (hi[p] - lo[p])
+        return (abs_min, abs_max), (lo[p] - r, hi[p] + r)
+
+    def macro_ranges(self, pair_dims=None):
+        """macro_axes of this object's ranges (pair_dims: its own, or the macro's first min(dim, 10) dimensions)."""
+        if pair_dims is None:
+            pair_dims = self.pair_dims if self.pair_dims is not None else np.arange(min(self.lo.size, 10))
+        return self.macro_axes(self.lo, self.hi, pair_dims)
+
+    def density(self, d):
+        """[n1]: the in-range counts of dimension d over (all points x bin width): a density that integrates to the
+        in-range fraction."""
+        c = self.counts1[d].astype(np.float64)
+        return c[1:-1] / (c.sum() * (self.hi1[d] - self.lo1[d]) / self.n1)
+
+    def quantile(self, d, q):
+        """The q-quantile of dimension d from its histogram: linear interpolation inside the bin where the cumulative
+        count crosses q x (all points); underflow counts as sitting on lo1[d], overflow on hi1[d].  The resolution is
+        one bin."""
+        c = self.counts1[d].astype(np.float64)
+        n, lo, hi = self.n1, float(self.lo1[d]), float(self.hi1[d])
+        target = float(q) * c.sum()
+        cum = np.cumsum(c[:-1])                 # cum[k]: points below edge k (the underflow included)
+        if target <= cum[0]:
+            return lo
+        if target > cum[n]:
+            return hi
+        k = int(np.searchsorted(cum, target, side="left"))     # first edge with cum >= target: inside bin k
+        return lo + (hi - lo) * ((k - 1) + (target - cum[k - 1]) / c[k]) / n
+
+    def interval(self, d, level=0.68):
+        """The central credible interval of dimension d holding `level` of the points (to one bin)."""
+        return self.quantile(d, 0.5 * (1.0 - level)), self.quantile(d, 0.5 * (1.0 + level))
+
+
+def _marginals(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchains_padded, n1, n2, pair_dims, sample_stride,
+               ranges, stream):
+    """Ranges (unless given) and then the fill with the macro's axes: the body of the engines' Marginals methods."""
+    up = C.POINTER(C.c_uint64)
+    trace, nslots, st = C.c_void_p(int(trace_ptr)), int(nslots), C.c_void_p(int(stream))
+    if pair_dims is None:
+        pair_dims = np.arange(min(dim, 10))                        # the macro's "only doing 10" (:39-43)
+    pair_dims = np.ascontiguousarray(pair_dims, dtype=np.int32)
+    if ranges is None:
+        if sample_stride is None:
+            sample_stride = Marginals.macro_sample_stride(nslots)
+        lo, hi = np.zeros(dim), np.zeros(dim)
+        check(lib.smcmc_trace_ranges(trace, nslots, dim, dim_stride, nchains, nchains_padded, int(sample_stride), _ptr(lo),
+                                     _ptr(hi), st))
+    else:
+        lo, hi = _f64(ranges[0]), _f64(ranges[1])
+        if lo.shape != (dim,) or hi.shape != (dim,):
+            raise ValueError("ranges must be (lo[dim], hi[dim])")
+    (abs_min, abs_max), (lo2, hi2) = Marginals.macro_axes(lo, hi, pair_dims)
+    lo1, hi1 = np.full(dim, abs_min), np.full(dim, abs_max)
+    lo2, hi2 = _f64(lo2), _f64(hi2)
+    P = int(pair_dims.size)
+    counts1 = np.zeros((dim, n1 + 2), dtype=np.uint64) if n1 else None
+    counts2 = np.zeros((P, P, n2 + 2, n2 + 2), dtype=np.uint64) if P else None
+    check(lib.smcmc_marginal_histograms(trace, nslots, dim, dim_stride, nchains, nchains_padded, int(n1), _ptr(lo1), _ptr(hi1),
+                                        counts1.ctypes.data_as(up) if n1 else None, P,
+                                        pair_dims.ctypes.data_as(C.POINTER(C.c_int32)), int(n2), _ptr(lo2), _ptr(hi2),
+                                        counts2.ctypes.data_as(up) if P else None, st))
+    return Marginals(lo, hi, nslots, nchains, lo1 if n1 else None, hi1 if n1 else None, counts1,
+                     pair_dims if P else None, lo2 if P else None, hi2 if P else None, counts2)
 
 
 class PosteriorMoments:
@@ -649,6 +803,11 @@ class HmcEngine:
                                                          C.c_void_p(int(stream))))
         return Autocorrelation(s, lagged, int(nslots), self.nchains)
 
+    def Marginals(self, trace_ptr, nslots, n1=100, n2=50, pair_dims=None, sample_stride=None, ranges=None, stream=0):
+        """As Engine.Marginals, over a trace of copy_positions slots ([slot][dim][nchains_padded])."""
+        return _marginals(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains, self.nchains_padded,
+                          n1, n2, pair_dims, sample_stride, ranges, stream)
+
     def lane(self, name):
         if name in _capi.HMC_LANE_F64:
             out = np.zeros(self.nchains)
@@ -750,6 +909,11 @@ class VaatEngine:
     def step_save(self, nsteps, stride, save_x_ptr, save_logl_ptr=None):
         self._check(self._lib.smcmc_vaat_step_save(self._h, int(nsteps), int(stride), C.c_void_p(int(save_x_ptr)),
                                                    C.c_void_p(int(save_logl_ptr)) if save_logl_ptr else None))
+
+    def Marginals(self, trace_ptr, nslots, n1=100, n2=50, pair_dims=None, sample_stride=None, ranges=None, stream=0):
+        """As Engine.Marginals, over a trace step_save wrote ([slot][dim][nchains_padded])."""
+        return _marginals(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains, self.nchains_padded,
+                          n1, n2, pair_dims, sample_stride, ranges, stream)
 
     @property
     def total_steps(self): return self._lib.smcmc_vaat_total_steps(self._h)
