@@ -323,6 +323,12 @@ int smcmc_read_chain_proposal(smcmc_engine* h, int chain, double* centre, double
 /* device pointers for zero-copy consumers (x: [dim_padded][nchains_padded], logl: [nchains_padded]) */
 int smcmc_state_device_ptr(smcmc_engine* h, double** x, double** logl);
 
+/* Development aid: a device buffer of smcmc_nchains_padded() / 64 * 7 * 64 unsigned 64-bit words, zeroed by the caller, to
+ * which a library built with -DSMCMC_STEP_PROFILE (tools/micro/build_stepprof.sh) adds the cycles its step kernel spent per
+ * section (tools/micro/stepprof.py reads it).  The shipped library takes no stamps and never touches the buffer.  NULL
+ * (the default) turns it off; the buffer must outlive every later step launch. */
+int smcmc_set_step_profile(smcmc_engine* h, void* device_buffer);
+
 /* ---- Hamiltonian Monte Carlo (sMCMC::TSimpleHMC, reference TSimpleHMC.H:119-973) ------ */
 /* Every chain is a TSimpleHMC chain with the analytic gradient of the device likelihood.
  * SetMeanEpsilon(negative value) keeps |epsilon| fixed (every update of fMeanEpsilon is

@@ -112,6 +112,7 @@ SIGNATURES = {
     "smcmc_set_covariance": (C.c_int, [_H, _dp]),
     "smcmc_get_decomposition": (C.c_int, [_H, _dp]),
     "smcmc_state_device_ptr": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "smcmc_set_step_profile": (C.c_int, [_H, C.c_void_p]),
     "smcmc_read_chain": (C.c_int, [_H, C.c_int, _dp, _dp, _dp, _ip]),
     "smcmc_read_chain_proposal": (C.c_int, [_H, C.c_int, _dp, _dp, _dp]),
     "smcmc_hmc_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(_H)]),

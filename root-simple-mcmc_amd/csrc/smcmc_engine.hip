@@ -106,6 +106,7 @@ struct smcmc_engine {
     int comm_ranks = 0;
     DeviceBuffer<double> d_proposed;  // [dp][npad], allocated by SMCMC_P_KEEP_PROPOSED
     bool keep_proposed = false;
+    void* d_step_prof = nullptr;      // smcmc_set_step_profile: the caller's buffer, handed to the step kernels (StepParams::prof)
     DeviceBuffer<double> d_uniform;   // [2][dp] bounds of the uniform dimensions
     int scan_dim = -1;             // fScanDimension
     // the pooled update on the device (smcmc_pooled_update.hip.h): the device copy of the shared proposal's numbers
@@ -953,6 +954,7 @@ StepParams make_params(smcmc_engine* h, int nsteps, int metropolis) {
     p.gacc = h->d_gacc;
     p.save_x = nullptr; p.save_logl = nullptr; p.save_stride = 1;
     p.proposed = h->keep_proposed ? h->d_proposed.get() : nullptr;
+    p.prof = static_cast<unsigned long long*>(h->d_step_prof);
     p.uniform = h->d_uniform;
     for (int d = 0; d < h->dim && d < 64; ++d)   // the register kernels (dim <= 63); larger dimensions carry theirs in d_uniform
         if (P.ptype[d] == 1) p.uniform_mask |= (uint64_t)1 << d;
@@ -2169,6 +2171,12 @@ int smcmc_get_decomposition(smcmc_engine* h, double* out) {
     ON_DEVICE(h);
     { int sst_ = sync_shared_to_host(h, false); if (sst_) return sst_; }
     std::copy(h->prop->decomp.begin(), h->prop->decomp.end(), out);
+    return SMCMC_OK;
+}
+
+int smcmc_set_step_profile(smcmc_engine* h, void* device_buffer) {
+    if (!h) return SMCMC_ERR_INVALID;
+    h->d_step_prof = device_buffer;
     return SMCMC_OK;
 }
 

@@ -290,7 +290,55 @@ struct StepParams {
                                // the SPECIAL instantiation and the fused-order kernels look at it
     int zero;                  // always 0; makes table addresses depend on the step so that the
                                // compiler does not hoist (and then spill) whole tables out of the loop
+    unsigned long long* prof;  // section profile (SMCMC_STEP_PROFILE builds only): [group][kProfSlots][64] cycle sums, added to
 };
+
+// ---- Section profile of the step loop: -DSMCMC_STEP_PROFILE=1 (sections) or 2 (sections and every piece) ----
+// Never in the shipped library (tools/micro/build_stepprof.sh builds a second one with one object replaced).  The step
+// loop takes s_memtime stamps at section boundaries; the cycles since the previous stamp go to the section that ends
+// there.  The sums live in lanes of vector registers -- lane k of slot 0 is section k, lane g & 63 of slots 1 .. 6 is
+// piece g (its read drain, its arithmetic, its matrix part; two slots each: pieces 0-63, 64-127; the full-matrix kernels'
+// later pieces fold onto these) -- and leave through
+// ordinary stores at the end of the launch.  A stamp waits for its own value (lgkmcnt(0)), which also drains the LDS
+// queue: behind a stamp nothing is in flight, so a section never pays for the one before it, and what a piece's reads
+// cost from issue to arrival shows in the piece's "drain" figure instead of hiding under the arithmetic.  The stamp's
+// own cost is section PROF_STAMP (two stamps back to back, once per step); tools/micro/stepprof.py subtracts it.
+constexpr int kProfSlots = 7;
+enum { PROF_LOOP, PROF_STAMP, PROF_A, PROF_TOP, PROF_NORMALS, PROF_PIECES, PROF_TAIL, PROF_RMS, PROF_LIKE, PROF_TEST,
+       PROF_COMMIT, PROF_ENDWAIT, PROF_COUNT };
+enum { PROF_PIECE_DRAIN, PROF_PIECE_VALU, PROF_PIECE_MATRIX };
+#ifdef SMCMC_STEP_PROFILE
+struct StepProf {
+    uint64_t last, slot[kProfSlots];
+    __device__ __forceinline__ static uint64_t stamp() {
+        uint64_t t;
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t));
+        __builtin_amdgcn_sched_barrier(0);
+        return t;
+    }
+    __device__ __forceinline__ void start() {
+#pragma unroll
+        for (int q = 0; q < kProfSlots; ++q) slot[q] = 0;
+        last = stamp();
+    }
+    template <int S>
+    __device__ __forceinline__ void add(int k, int lane) {
+        const uint64_t t = stamp();
+        slot[S] += (lane == k) ? t - last : 0;
+        last = t;
+    }
+};
+#define SMCMC_PROF_MARK(k) prof.add<0>(k, lane)
+#if SMCMC_STEP_PROFILE >= 2
+#define SMCMC_PROF_PIECE(kind, g) prof.add<1 + 2 * (kind) + (((g) >> 6) & 1)>((g) & 63, lane)
+#else
+#define SMCMC_PROF_PIECE(kind, g)
+#endif
+#else
+#define SMCMC_PROF_MARK(k)
+#define SMCMC_PROF_PIECE(kind, g)
+#endif
 
 __device__ __forceinline__ double dmin(double a, double b) { return __builtin_fmin(a, b); }
 __device__ __forceinline__ double dmax(double a, double b) { return __builtin_fmax(a, b); }
@@ -602,13 +650,33 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
 
     double xp[DP];
     const uint32_t aw = smcmc_accept_word((uint32_t)D);
+#ifdef SMCMC_STEP_PROFILE
+    StepProf prof;
+    prof.start();
+#endif
+
+    // QUADFORM: the proposal and the accepted point trade places -- the likelihood reads the proposal from
+    // the LDS column, the registers keep the accepted point to put back on a reject
+    constexpr bool SWAP = (LIKE == SMCMC_LIKE_QUADFORM);
+
+    // The step boundary without its waits (BOUNDARY; profiles/step_issue_notes.md): the StepRMS rows read in one batch,
+    // coordinate 0 of the accepted point carried in a register, no wait for the commit's writes.  Only the instantiations
+    // it was measured on have it: the headline's (D = 50 family, iso-Gaussian, reference order, triangular decomposition,
+    // no uniform dimensions / scan; with and without the moment fold), whose lone wavefront per SIMD has the registers
+    // for the 50 extra rows.  The fused-order and SPECIAL kernels of the family sit at 512 registers and spill already,
+    // the families below 47 share a SIMD between two wavefronts, and the other likelihoods and the 47-dimension family
+    // have no timing yet.  Every other instantiation keeps the step boundary it had, instruction for instruction.
+    constexpr bool BOUNDARY = EXACT && !SWAP && !FULLU && !SPECIAL && DP == 50 && LIKE == SMCMC_LIKE_ISO_GAUSS;
+
+    // Coordinate 0 of the accepted point, which UpdateState compares with the step before.  BOUNDARY: carried in a register
+    // from commit to commit (read back from LDS at the top of a step it was a read and a full wait behind the commit's
+    // writes); otherwise read at the top of every step.
+    double x0 = 0.0;
+    if constexpr (BOUNDARY) x0 = xcol[0];
 
     // StepRMS window, likelihood, Metropolis test and accept copy of one step
     // (TSimpleMCMC.H:391-406, 410-491) for the proposal held in xp.
     auto finish_step = [&](int s, uint32_t uword) {
-        // QUADFORM: the proposal and the accepted point trade places -- the likelihood reads the proposal from
-        // the LDS column, the registers keep the accepted point to put back on a reject
-        constexpr bool SWAP = (LIKE == SMCMC_LIKE_QUADFORM);
         if constexpr (SPECIAL || !EXACT) {
             // GetProposed() (TSimpleMCMC.H:514): the proposal of the latest step, accepted or not (in the reference
             // order only the SPECIAL instantiation carries the store; the fused kernels all do)
@@ -625,11 +693,32 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
                 xp[d] = t;
             }
         }
+        // The StepRMS sum needs the accepted point next to the proposal: DP rows of the LDS column.  Read where they
+        // are used, every term is a read, a full wait and its arithmetic -- the LDS latency DP / 2 times per step, in a
+        // lone wavefront that has nothing else to issue.  In the BOUNDARY kernels (the likelihood works on registers alone) the
+        // rows are all read first, in one batch, and the terms wait with counted waits as the rows come in.  The likelihood
+        // is written between the reads and the sum (two independent sums, each in its own order) so that it could run
+        // under the reads; the compiler merges the two `step_rms_window > 0` blocks and puts it behind the sum in that
+        // path, so one LDS latency is still exposed (profiles/step_issue_notes.md).
+        constexpr bool RMS_AHEAD = BOUNDARY;
+        double xold[RMS_AHEAD ? DP : 1];
+        if constexpr (RMS_AHEAD) {
+            if (p.step_rms_window > 0) {
+#pragma unroll
+                for (int d = 0; d < DP; ++d) xold[d] = xcol[d * kXStride];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            logl_prop = loglike<DP, LIKE, EXACT>(xp, likep + p.zero * (s + 1), D);
+            __builtin_amdgcn_sched_barrier(0);
+            SMCMC_PROF_MARK(PROF_LIKE);
+        }
         if (p.step_rms_window > 0) {
             double sqr = 0.0;
 #pragma unroll
             for (int d = 0; d < DP; ++d) {
-                double t = SWAP ? xcol[d * kXStride] - xp[d] : xp[d] - xcol[d * kXStride];
+                double t;
+                if constexpr (RMS_AHEAD) t = xp[d] - xold[d];
+                else t = SWAP ? xcol[d * kXStride] - xp[d] : xp[d] - xcol[d * kXStride];
                 if constexpr (EXACT) sqr += t * t;
                 else sqr = SMCMC_FMA(t, t, sqr);
             }
@@ -640,6 +729,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
             rms_trials = (p.step_rms_window < rms_trials + 1) ? p.step_rms_window : rms_trials + 1;
             step_rms = __builtin_sqrt(ms);
         }
+        SMCMC_PROF_MARK(PROF_RMS);
         if constexpr (SWAP) {
             bool dense = p.like_rowptr == nullptr;
             if (!dense) {
@@ -649,7 +739,8 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
             }
             if (dense) logl_prop = loglike_quadform_lds<DP, EXACT>(xcol, likep + p.zero * (s + 1));
         }
-        else logl_prop = loglike<DP, LIKE, EXACT>(xp, likep + p.zero * (s + 1), D);
+        else if constexpr (!RMS_AHEAD) logl_prop = loglike<DP, LIKE, EXACT>(xp, likep + p.zero * (s + 1), D);
+        if constexpr (!RMS_AHEAD) SMCMC_PROF_MARK(PROF_LIKE);
         bool take;
         if (p.metropolis == 2) {
             take = true;
@@ -672,11 +763,21 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
             logl = logl_prop;
             ++naccept;
         }
+        SMCMC_PROF_MARK(PROF_TEST);
         if (take != SWAP) {   // plain: commit the proposal on accept; swapped: put the accepted point back on reject
 #pragma unroll
             for (int d = 0; d < DP; ++d) xcol[d * kXStride] = xp[d];
         }
-        if constexpr (MOMENTS) __syncthreads();   // the next step's operand reads see this step's accepts
+        SMCMC_PROF_MARK(PROF_COMMIT);
+        if constexpr (BOUNDARY) x0 = take ? xp[0] : x0;
+        // The next step's operand reads (inline assembly) must see this step's accepts.  The workgroup is ONE wavefront
+        // and its LDS operations execute in issue order: all that is needed is that the compiler keeps the order, not a
+        // barrier and not a wait for the writes -- they drain under the next step's scalar half.  The compiler keeps it
+        // because this statement clobbers memory and because the operand reads (fetch_operands, fetch_operand) are
+        // `asm volatile`, which are never reordered among each other: those reads must stay volatile.
+        if constexpr (MOMENTS && BOUNDARY) asm volatile("" ::: "memory");
+        else if constexpr (MOMENTS) __syncthreads();   // the next step's operand reads see this step's accepts
+        SMCMC_PROF_MARK(PROF_ENDWAIT);
         if (p.save_x != nullptr && ((s + 1) % p.save_stride) == 0 && active) {
             const size_t slot = (size_t)((s + 1) / p.save_stride - 1);
 #pragma unroll
@@ -722,10 +823,12 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
 
     for (int s = s0; s < p.nsteps; ++s) {
         const uint64_t step = (uint64_t)(p.step0 + (uint32_t)s + 1u);   // ++fTotalSteps, :376
+        SMCMC_PROF_MARK(PROF_LOOP);
+        SMCMC_PROF_MARK(PROF_STAMP);
 
         // ---- A: UpdateState, scalar half (TSimpleMCMC.H:1723-1776) ----
         ++trials;
-        const double x0 = xcol[0];
+        if constexpr (!BOUNDARY) x0 = xcol[0];
         const bool moved = (logl != last_value) || (x0 != last_x0);
         if (moved) ++succ;
         acc_rate *= acc_trials;
@@ -760,6 +863,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         }
         last_value = logl;
         last_x0 = x0;
+        SMCMC_PROF_MARK(PROF_A);
 
         // ---- B: proposal (TSimpleMCMC.H:709-724) ----
         if constexpr (OPF) {
@@ -790,6 +894,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
                 tabs[b1 & 1][1] = normal_tables_fetch<kAsmReads<DP>>(blks[b1 & 1].v[2], blks[b1 & 1].v[3], ltab, atab);
         };
         if constexpr (PIPE) draw_and_fetch(std::integral_constant<int, 0>{});
+        SMCMC_PROF_MARK(PROF_TOP);
         static_for<NB>([&](auto bc) {
             constexpr int b = decltype(bc)::value;
             // U rows 4b..4b+3 are consumed in pieces of kPiece columns; the LDS reads of a
@@ -821,16 +926,21 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) sr[q] = sigma * n[q];
             __builtin_amdgcn_sched_barrier(0);
+            SMCMC_PROF_MARK(PROF_NORMALS);
 
             static_for<PC::COUNT>([&](auto rc) {
                 constexpr int r = decltype(rc)::value;
                 constexpr int i = PC::row(r), c = PC::col(r);
+                constexpr int g = PC::first_global() + r;          // piece number within the step
+                (void)g;
                 if constexpr (r + 1 < PC::COUNT) {
                     constexpr int i1 = PC::row(r + 1), c1 = PC::col(r + 1);
                     load_piece<DP, FULLU, i1, c1>(up, nxt);
                     piece_ready<piece_reads<DP, FULLU, c1>(), piece_reads<DP, FULLU, c>(), kAsmReads<DP>>(cur);
+                    SMCMC_PROF_PIECE(PROF_PIECE_DRAIN, g);
                 } else {
                     piece_ready<0, piece_reads<DP, FULLU, c>(), kAsmReads<DP>>(cur);
+                    SMCMC_PROF_PIECE(PROF_PIECE_DRAIN, g);
                     // the last piece of the block: the next block's random words and its table reads
                     if constexpr (PIPE && b + 1 < NB) draw_and_fetch(std::integral_constant<int, b + 1>{});
                 }
@@ -848,6 +958,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
                         asm volatile("" : "+v"(xp[j]));
                     }
                 }
+                SMCMC_PROF_PIECE(PROF_PIECE_VALU, g);
                 if constexpr (MOMENTS) {
                     // The group's second moments: the 16 x NT matrix instructions of the 64-chain contraction are
                     // dealt out over the pieces of the step (1-2 per piece) and pinned BEHIND the piece's vector work.
@@ -856,7 +967,6 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
                     // operands of the next k-quad, then the next piece's eight reads and its wait -- and runs in
                     // its shadow.  (Left to the scheduler it goes to the top of the piece, in front of 32 vector
                     // instructions that then wait for it.)  Chains fold in ascending order.
-                    constexpr int g = PC::first_global() + r;          // piece number within the step
                     constexpr int G = UPieces<DP, FULLU, NB - 1>::first_global() + UPieces<DP, FULLU, NB - 1>::COUNT;
                     constexpr int NM = 16 * NT;
                     constexpr int m_lo = (int)(((long)g * NM) / G), m_hi = (int)(((long)(g + 1) * NM) / G);
@@ -898,12 +1008,14 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
                         }
                     });
                 }
+                SMCMC_PROF_PIECE(PROF_PIECE_MATRIX, g);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (r + 1 < PC::COUNT) {
 #pragma unroll
                     for (int k = 0; k < kPiece / 2; ++k) cur[k] = nxt[k];
                 }
             });
+            SMCMC_PROF_MARK(PROF_PIECES);
         });
         if ((aw >> 2) >= (uint32_t)NB) {
             smcmc_u32x4 blk = smcmc_draw_block(p.seed, gid, step, aw >> 2, SMCMC_STREAM_STEP);
@@ -925,9 +1037,16 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
                 for (int d = 0; d < DP; ++d) xp[d] = ((uint32_t)d == ud) ? val : xp[d];
             }
         }
+        SMCMC_PROF_MARK(PROF_TAIL);
         finish_step(s, uword);
     }
 
+#ifdef SMCMC_STEP_PROFILE
+    if (p.prof != nullptr) {
+#pragma unroll
+        for (int q = 0; q < kProfSlots; ++q) p.prof[((size_t)group * kProfSlots + q) * kWave + lane] += prof.slot[q];
+    }
+#endif
     if constexpr (MOMENTS) {
 #pragma unroll
         for (int t = 0; t < NT16; ++t)
