@@ -534,6 +534,39 @@ int smcmc_marginal_histograms(const double* trace_device, int nslots, int dim, i
                               int npair_dims, const int32_t* pair_dims, int n2, const double* lo2, const double* hi2,
                               uint64_t* counts2, void* stream);
 
+/* ---- posterior reducer: mean and covariance of a saved trace -------------------
+ * MakeCovariance.C:63-89 adds up, over the entries of the tree, avg[i] += x_i and cov(i, j) += x_i x_j, then takes
+ * cov / entries - avg_i avg_j (:84).  This takes the two sums on the device, over every slot of every live chain of
+ * trace_device[slot][dim_stride][nchains_padded] (as smcmc_step_save, smcmc_vaat_step_save or smcmc_hmc_copy_positions
+ * wrote it; padding lanes and rows >= dim are never read into a result), about the reference point `centre` ([dim]
+ * host; NULL = the origin is the macro's definition; the covariance does not depend on it and E[yy] - E[y]E[y] cancels
+ * less about a point near the mean): with y = x[t][d][c] - centre[d],
+ *   sum[d]      = sum_{t, c} y_d
+ *   sumsq[i][j] = sum_{t, c} y_i y_j       dim x dim, row-major, exactly symmetric (the lower triangle, mirrored)
+ * Host outputs and raw sums so that ranks can add theirs; the number of terms is nslots * nchains.  The products run
+ * on the matrix pipe (one fused multiply-add per term, k over the chains); the summation order is fixed
+ * (smcmc_trace_moments.hip states it): the same bits on every run.  Arguments as smcmc_autocorrelation_sums, and
+ * dim <= smcmc_max_dim().  `stream` is a hipStream_t or NULL. */
+int smcmc_trace_moments(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
+                        int nchains_padded, const double* centre, double* sum, double* sumsq, void* stream);
+
+/* ---- the Gaussian stand-in chain of a mean and a covariance ---------------------
+ * CholeskyChain.C:18-66: covariance = U^T U with U upper triangular (:39-46; here the row-ordered routine the adaptive
+ * proposal uses, a pivot that is not positive and finite is SMCMC_ERR_RUNTIME and nothing is launched or written, where
+ * the macro exits), then every entry is
+ *   accepted = mean;  for i ascending: r_i = Gaus(0, 1), accepted[j] += r_i * U(i, j) for all j       (:53-60)
+ * with an un-fused multiply and add.  Every (slot, chain < nchains) of trace_device[slot][dim_stride][nchains_padded]
+ * gets one entry; rows >= dim and lanes >= nchains are not written.  The normals of an entry are laid out as a
+ * chain-step's: Philox block b of counter (b, chain_offset + chain, slot) on stream SMCMC_STREAM_CHOLESKY gives the
+ * normals 4b .. 4b + 3, words (0, 1) and (2, 3) one pair of the engine's normal transform each
+ * (include/smcmc_detmath.h).  The draws are keyed on the global chain number, so a fill with a chain_offset is a slice
+ * of the whole fill.  mean[dim] and covariance[dim*dim] (its upper triangle is read) are host arrays; `decomposition`
+ * is an optional [dim*dim] host output, U row-major.  dim <= smcmc_max_dim(), nchains_padded a multiple of 64.  The
+ * result is a trace the reducers above take as it is.  `stream` is a hipStream_t or NULL. */
+int smcmc_cholesky_chain(const double* mean, const double* covariance, int dim, int nslots, int nchains,
+                         int nchains_padded, int dim_stride, uint64_t seed, uint32_t chain_offset,
+                         double* trace_device, double* decomposition, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,8 @@ SMCMC_HD smcmc_u32x4 smcmc_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2,
 #define SMCMC_STREAM_VAAT  3u   /* TProposeVAATStep chains: words 0,1 the normal pair of the step's Gaus (first normal
                                  * used), word 2 its Uniform(a,b), word 3 the Metropolis uniform, words 4+i the i-th
                                  * Uniform() of a queue shuffle made during that step (TProposeVAATStep.H:190-193) */
+#define SMCMC_STREAM_CHOLESKY 4u /* smcmc_cholesky_chain: the normals of a draw, laid out as a chain-step's (block b of
+                                 * (chain, slot) gives normals 4b .. 4b+3), CholeskyChain.C:56 */
 
 /* Every draw of the engine is a block of Philox4x32-7: seven rounds is the count Salmon et al. (SC'11, table 2) report
  * as the fewest that pass BigCrush ("Crush-resistant"), ten their default with a safety margin.  The headline kernel

@@ -185,6 +185,9 @@ SIGNATURES = {
     "smcmc_trace_ranges": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_void_p]),
     "smcmc_marginal_histograms": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_int, _dp, _dp, _up, C.c_int, _ip, C.c_int, _dp, _dp, _up, C.c_void_p]),
+    "smcmc_trace_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_void_p]),
+    "smcmc_cholesky_chain": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
+                                       C.c_void_p, _dp, C.c_void_p]),
 }
 AUTOCORR_LAGS = 64
 MARGINAL_MAX_BINS1, MARGINAL_MAX_BINS2, MARGINAL_MAX_PAIR_DIMS = 1000, 126, 32   # SMCMC_MARGINAL_MAX_* of include/smcmc.h

@@ -173,6 +173,10 @@ public:
         covTrials = std::min(covWindow, covTrials + n);
     }
 
+    // The plain decomposition alone (`decomp` = U of cov = U^T U, false at a pivot that is not positive and finite),
+    // without the repair ladder of update(): what TDecompChol gives CholeskyChain.C:39-46 (smcmc_trace_moments.hip).
+    bool choleskyOnly() { return cholesky(); }
+
 private:
     bool cholesky() {
         // row-ordered A = U^T U; a pivot that is not a positive finite number fails

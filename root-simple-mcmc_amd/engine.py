@@ -278,6 +278,13 @@ class Engine:
         return _marginals(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim_padded, self.nchains,
                           self.nchains_padded, n1, n2, pair_dims, sample_stride, ranges, stream)
 
+    def TraceMoments(self, trace_ptr, nslots, centre=None, stream=0):
+        """The sums behind the mean and covariance of a trace StepSave wrote (MakeCovariance.C:63-89), taken on the
+        device over every slot of every chain about `centre` (default: the origin, as the macro has it; the mean of
+        the run conditions the covariance better).  Returns a TraceMoments."""
+        return _trace_moments(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim_padded, self.nchains,
+                              self.nchains_padded, centre, stream)
+
     def GetAccepted(self):
         x = np.zeros((self.dim, self.nchains))
         self._check(self._lib.smcmc_read_state(self._h, _ptr(x), None))
@@ -565,6 +572,99 @@ def _marginals(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchains_
                      pair_dims if P else None, lo2 if P else None, hi2 if P else None, counts2)
 
 
+class TraceMoments:
+    """The mean and covariance of a saved trace as MakeCovariance.C:63-89 takes them, from the raw sums of
+    smcmc_trace_moments about `centre`: sum[d] = sum y_d, sumsq[i][j] = sum y_i y_j, y = x - centre, over
+    n = nslots * nchains points.
+      mean         centre + sum / n
+      covariance   sumsq / n - (sum / n)(sum / n)^T: the macro's :84 taken about the centre (a covariance does not
+                   depend on the point it is taken about; about a point near the mean the difference cancels less)
+      spread       sqrt(diag covariance): the errors of the macro's TProfile in its "S" option (:58-60)
+      correlation  covariance / (spread_i spread_j)
+    Sums of several ranks add (`+`): the right operand is re-centred on the left one's centre first."""
+
+    def __init__(self, total, sumsq, nslots, nchains, centre=None):
+        self.sum, self.sumsq = _f64(total).copy(), _f64(sumsq).copy()
+        self.nslots, self.nchains = int(nslots), int(nchains)
+        self.centre = np.zeros(self.sum.size) if centre is None else _f64(centre).copy()
+        if self.sumsq.shape != (self.sum.size, self.sum.size) or self.centre.shape != self.sum.shape:
+            raise ValueError("sum[dim], sumsq[dim][dim] and centre[dim] do not fit together")
+
+    @property
+    def n(self):
+        return float(self.nslots) * float(self.nchains)
+
+    def about(self, centre):
+        """The same sums taken about another point: with s = old centre - new centre, y' = y + s."""
+        centre = _f64(centre)
+        s, n = self.centre - centre, self.n
+        total = self.sum + n * s
+        sumsq = self.sumsq + np.outer(s, self.sum) + np.outer(self.sum, s) + n * np.outer(s, s)
+        return TraceMoments(total, sumsq, self.nslots, self.nchains, centre)
+
+    def __add__(self, other):
+        if self.nslots != other.nslots:
+            raise ValueError("traces of different lengths do not pool")
+        o = other if np.array_equal(other.centre, self.centre) else other.about(self.centre)
+        return TraceMoments(self.sum + o.sum, self.sumsq + o.sumsq, self.nslots, self.nchains + o.nchains, self.centre)
+
+    @property
+    def mean(self):
+        return self.centre + self.sum / self.n
+
+    @property
+    def covariance(self):
+        m = self.sum / self.n
+        return self.sumsq / self.n - np.outer(m, m)
+
+    @property
+    def spread(self):
+        return np.sqrt(np.diag(self.covariance))
+
+    @property
+    def correlation(self):
+        s = self.spread
+        return self.covariance / np.outer(s, s)
+
+
+def _trace_moments(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchains_padded, centre, stream):
+    """The body of the engines' TraceMoments methods."""
+    c = None if centre is None else _f64(centre)
+    if c is not None and c.shape != (dim,):
+        raise ValueError("centre must be [dim]")
+    total, sumsq = np.zeros(dim), np.zeros((dim, dim))
+    check(lib.smcmc_trace_moments(C.c_void_p(int(trace_ptr)), int(nslots), dim, dim_stride, nchains, nchains_padded,
+                                  None if c is None else _ptr(c), _ptr(total), _ptr(sumsq), C.c_void_p(int(stream))))
+    return TraceMoments(total, sumsq, nslots, nchains, c)
+
+
+def cholesky_chain(mean, covariance, nslots, nchains, seed=20240607, chain_offset=0, dim_stride=None, stream=0):
+    """The Gaussian stand-in chain of CholeskyChain.C:18-66, filled on the device: covariance = U^T U, every
+    (slot, chain) one draw mean + sum_i r_i U(i, :) on the random stream (seed, chain_offset + chain, slot).  Returns
+    (trace, U): a torch tensor [nslots][dim_stride][nchains_padded] on the current device (rows >= dim and lanes >=
+    nchains are NaN), which the reducers take as it is through trace.data_ptr(), and the decomposition [dim][dim].
+    A covariance that is not positive definite raises SmcmcError (SMCMC_ERR_RUNTIME)."""
+    import torch
+    lib = _capi.load()
+    mean, covariance = _f64(mean), _f64(covariance)
+    dim = mean.size
+    if mean.ndim != 1 or covariance.shape != (dim, dim):
+        raise ValueError("mean must be [dim] and covariance [dim][dim]")
+    dim_stride = dim if dim_stride is None else int(dim_stride)
+    nchains, nslots = int(nchains), int(nslots)
+    npad = (nchains + 63) // 64 * 64
+    if not torch.cuda.is_available():   # the fill is a device kernel: there is no host version of it
+        raise SmcmcError(_capi.ERR_NO_DEVICE, lib.smcmc_status_string(_capi.ERR_NO_DEVICE).decode())
+    trace = torch.full((nslots, dim_stride, npad), float("nan"), dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    U = np.zeros((dim, dim))
+    st = lib.smcmc_cholesky_chain(_ptr(mean), _ptr(covariance), dim, nslots, nchains, npad, dim_stride, int(seed),
+                                  int(chain_offset), C.c_void_p(trace.data_ptr()), _ptr(U), C.c_void_p(int(stream)))
+    if st != _capi.OK:
+        raise SmcmcError(st, lib.smcmc_status_string(st).decode())
+    return trace, U
+
+
 class PosteriorMoments:
     """Posterior mean / covariance of everything the ensemble visits (the reducers of
     MakeCovariance.C:63-89), fed by the pooled moment sums the device already forms:
@@ -808,6 +908,11 @@ class HmcEngine:
         return _marginals(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains, self.nchains_padded,
                           n1, n2, pair_dims, sample_stride, ranges, stream)
 
+    def TraceMoments(self, trace_ptr, nslots, centre=None, stream=0):
+        """As Engine.TraceMoments, over a trace of copy_positions slots ([slot][dim][nchains_padded])."""
+        return _trace_moments(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains,
+                              self.nchains_padded, centre, stream)
+
     def lane(self, name):
         if name in _capi.HMC_LANE_F64:
             out = np.zeros(self.nchains)
@@ -914,6 +1019,11 @@ class VaatEngine:
         """As Engine.Marginals, over a trace step_save wrote ([slot][dim][nchains_padded])."""
         return _marginals(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains, self.nchains_padded,
                           n1, n2, pair_dims, sample_stride, ranges, stream)
+
+    def TraceMoments(self, trace_ptr, nslots, centre=None, stream=0):
+        """As Engine.TraceMoments, over a trace step_save wrote ([slot][dim][nchains_padded])."""
+        return _trace_moments(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains,
+                              self.nchains_padded, centre, stream)
 
     @property
     def total_steps(self): return self._lib.smcmc_vaat_total_steps(self._h)
