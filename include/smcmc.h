@@ -371,6 +371,26 @@ int smcmc_hmc_set_sync_interval(smcmc_hmc* h, int steps);
  * (:417-444); 5: zero.  Types 2, 3, 5 need reference-order arithmetic (SMCMC_ERR_UNSUPPORTED otherwise). */
 int smcmc_hmc_set_gradient_type(smcmc_hmc* h, int type);
 int smcmc_hmc_get_gradient_type(const smcmc_hmc* h);
+/* The caller's own gradient (the OptionalGradient argument of TSimpleHMC<UserLikelihood, OptionalGradient>, TSimpleHMC.H:79-89,
+ * 119-128; BadGrad.C is the reference's driver).  HMC stays correct with a wrong gradient as long as the leapfrog is
+ * reversible (:101-108), so the gradient of types 0 / 1 / 4 need not be the gradient of the likelihood.  Two ways:
+ *  - compiled in: a user likelihood header (SMCMC_LIKE_USER, build.py --user-likelihood) that also defines
+ *        #define SMCMC_USER_GRADIENT 1
+ *        template <class Point> __device__ double smcmc_user_gradient_at(const Point& p, const double* params, int D, int i);
+ *    returns component i of grad log L at p (what the reference functor writes to g[i]; the engine negates it, :486).
+ *    It needs SMCMC_USER_LIKELIHOOD_ANY_DIM (the build fails otherwise) and runs in reference-order arithmetic.  Whether a
+ *    library has a gradient is fixed when it is compiled: a gradient that declines per call (the bool the reference's
+ *    functor returns, :87) is not supported.  The HMC engine takes up to 2 dim^2 + 2 dim + 8 user parameters, so that the
+ *    likelihood and the gradient can each carry a matrix (examples/user_likelihood_quadgrad.hip.h).
+ *  - at run time, for SMCMC_LIKE_QUADFORM: smcmc_hmc_set_gradient_matrix(h, G, dim*dim) makes types 0 / 1 / 4 compute
+ *    g_i = -sum_j G(i,j) q_j (j ascending) while the potential stays 1/2 sum_i q_i (Error q)_i, which costs one more
+ *    contraction per step.  (NULL, 0) clears it.  It takes effect at the next step, before or after Start.  Any other
+ *    likelihood is SMCMC_ERR_INVALID; the fused order (smcmc_hmc_set_exact_arithmetic(h, 0)) is SMCMC_ERR_UNSUPPORTED,
+ *    whichever of the two is set first.  Types 2 / 3 / 5 are unaffected.
+ * smcmc_hmc_has_gradient: 1 when types 0 / 1 / 4 are served (ISO_GAUSS, QUADFORM, ROSENBROCK, a user library with a
+ * gradient), 0 when they are SMCMC_ERR_RUNTIME (the stress targets, a user library without one; NULL). */
+int smcmc_hmc_has_gradient(const smcmc_hmc* h);
+int smcmc_hmc_set_gradient_matrix(smcmc_hmc* h, const double* G, int count);
 int smcmc_hmc_set_track_covariance(smcmc_hmc* h, int on);
 int smcmc_hmc_moment_group(const smcmc_hmc* h);
 int smcmc_hmc_sync(smcmc_hmc* h);                                        /* the pooled update now (end of a run) */

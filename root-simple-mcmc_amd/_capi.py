@@ -130,6 +130,8 @@ SIGNATURES = {
     "smcmc_hmc_set_track_covariance": (C.c_int, [_H, C.c_int]),
     "smcmc_hmc_set_gradient_type": (C.c_int, [_H, C.c_int]),
     "smcmc_hmc_get_gradient_type": (C.c_int, [_H]),
+    "smcmc_hmc_has_gradient": (C.c_int, [_H]),
+    "smcmc_hmc_set_gradient_matrix": (C.c_int, [_H, _dp, C.c_int]),
     "smcmc_hmc_moment_group": (C.c_int, [_H]),
     "smcmc_hmc_sync": (C.c_int, [_H]),
     "smcmc_hmc_moments_size": (C.c_int, [_H]),
@@ -203,7 +205,7 @@ class SmcmcError(RuntimeError):
         self.status = status
 
 
-def _bind(path):
+def _bind(path, optional=()):
     # One HIP runtime per process: PyTorch-ROCm carries its own libamdhip64 and the library is linked against /opt/rocm's
     # (same SONAME).  Whichever is loaded first serves both -- but if this library came first and torch then initialised
     # its own copy, the process would hold two runtimes and the second sees no device ("no HIP device").  So torch, when
@@ -214,15 +216,18 @@ def _bind(path):
         pass
     lib = C.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
+        if name in optional and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)   # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
     return lib
 
 
-def load(path=None):
+def load(path=None, optional=()):
     """Load the in-tree HIP library (or, with `path`, a build of it that carries a user likelihood:
-    `build.py --user-likelihood`).  Raises if it has not been built."""
+    `build.py --user-likelihood`).  Raises if it has not been built.  optional: entry points a library at
+    `path` may lack (a build of an earlier commit that a timing tool compares against); every other one is required."""
     global _lib
     if path is not None:
         path = os.path.abspath(path)
@@ -230,7 +235,7 @@ def load(path=None):
             if not os.path.exists(path):
                 raise ImportError(f"{path} is missing: build it with `python root-simple-mcmc_amd/build.py "
                                   "--user-likelihood <header>`.  There is no CPU fallback.")
-            _libs[path] = _bind(path)
+            _libs[path] = _bind(path, optional)
         return _libs[path]
     if _lib is None:
         if not os.path.exists(LIB_PATH):

@@ -43,15 +43,18 @@ def _headers():
     return sorted(hs)
 
 
-def _units(user_flag=None):
-    """(source, defines, object name).  With a user likelihood only the two engines and the SMCMC_LIKE_USER
-    instances are compiled with it; every other object is shared with the plain build."""
-    engine = ("smcmc_engine.hip", [user_flag], "engine_user") if user_flag else ("smcmc_engine.hip", [], "engine")
-    vaat = ("smcmc_vaat_engine.hip", [user_flag], "vaat_engine_user") if user_flag else ("smcmc_vaat_engine.hip", [], "vaat_engine")
-    hmc = ("smcmc_hmc_engine.hip", [user_flag], "hmc_engine_user") if user_flag else ("smcmc_hmc_engine.hip", [], "hmc_engine")
-    wave = (("smcmc_perchain_wave_inst.hip", [user_flag], "perchain_wave_user") if user_flag
+def _units(user_flag=None, name="user"):
+    """(source, defines, object name).  With a user likelihood only the engines and the SMCMC_LIKE_USER
+    instances are compiled with it; every other object is shared with the plain build.  `name` tells the objects of
+    one user library from those of another (libsmcmc_amd_<name>.so; the default keeps the names they always had)."""
+    tag = "_" + name
+    l3 = "" if name == "user" else tag
+    engine = ("smcmc_engine.hip", [user_flag], "engine" + tag) if user_flag else ("smcmc_engine.hip", [], "engine")
+    vaat = ("smcmc_vaat_engine.hip", [user_flag], "vaat_engine" + tag) if user_flag else ("smcmc_vaat_engine.hip", [], "vaat_engine")
+    hmc = ("smcmc_hmc_engine.hip", [user_flag], "hmc_engine" + tag) if user_flag else ("smcmc_hmc_engine.hip", [], "hmc_engine")
+    wave = (("smcmc_perchain_wave_inst.hip", [user_flag], "perchain_wave" + tag) if user_flag
             else ("smcmc_perchain_wave_inst.hip", [], "perchain_wave"))
-    wg = (("smcmc_perchain_wg_inst.hip", [user_flag], "perchain_wg_user") if user_flag
+    wg = (("smcmc_perchain_wg_inst.hip", [user_flag], "perchain_wg" + tag) if user_flag
           else ("smcmc_perchain_wg_inst.hip", [], "perchain_wg"))
     units = [engine, ("smcmc_selftest.hip", [], "selftest"), ("smcmc_autocorr.hip", [], "autocorr"),
              ("smcmc_marginals.hip", [], "marginals"), ("smcmc_trace_moments.hip", [], "trace_moments"),
@@ -69,14 +72,14 @@ def _units(user_flag=None):
     for w in (4, 8):
         units.append(("smcmc_panel_inst.hip", [f"-DSMCMC_PANEL_W={w}"], f"panel_w{w}"))
         if user_flag:   # a user likelihood as an HMC target (finite-difference / covariant gradient)
-            units.append(("smcmc_hmc_inst.hip", [f"-DSMCMC_PANEL_W={w}", user_flag], f"hmc_w{w}_user"))
+            units.append(("smcmc_hmc_inst.hip", [f"-DSMCMC_PANEL_W={w}", user_flag], f"hmc_w{w}{tag}"))
         else:
             units.append(("smcmc_hmc_inst.hip", [f"-DSMCMC_PANEL_W={w}"], f"hmc_w{w}"))
     if user_flag:
         for dp in dp_list():   # SMCMC_LIKE_USER = 3
-            units.append(("smcmc_inst.hip", [f"-DSMCMC_DP={dp}", "-DSMCMC_LIKE=3", user_flag], f"inst_dp{dp}_l3"))
+            units.append(("smcmc_inst.hip", [f"-DSMCMC_DP={dp}", "-DSMCMC_LIKE=3", user_flag], f"inst_dp{dp}_l3{l3}"))
         for w in (4, 8):       # 63 < dim <= 512 (served when the header defines SMCMC_USER_LIKELIHOOD_ANY_DIM)
-            units.append(("smcmc_user_large.hip", [f"-DSMCMC_PANEL_W={w}", user_flag], f"user_large_w{w}"))
+            units.append(("smcmc_user_large.hip", [f"-DSMCMC_PANEL_W={w}", user_flag], f"user_large_w{w}{l3}"))
     return units
 
 
@@ -227,25 +230,29 @@ def _link(objs, lib_path):
         raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
 
 
-def build(jobs=None, verbose=False, user_likelihood=None, output=None, with_plain=False):
+def build(jobs=None, verbose=False, user_likelihood=None, output=None, with_plain=False, output_name=None):
     """Compile every HIP translation unit for gfx950 and link the shared library.
 
     user_likelihood: a header defining smcmc_user_loglike<DP> (see smcmc_kernels.hip.h and
     examples/user_likelihood_asym.hip.h); the library built with it (default
     lib/libsmcmc_amd_user.so, or `output`) additionally serves SMCMC_LIKE_USER.  with_plain: also
-    (re)build lib/libsmcmc_amd.so in the same pass, all units in one pool."""
+    (re)build lib/libsmcmc_amd.so in the same pass, all units in one pool.  output_name: build
+    lib/libsmcmc_amd_<output_name>.so from objects of its own, so that the libraries of several user
+    likelihoods exist side by side (only the objects that include the user's header are per library)."""
     user_flag, user_lib = None, None
+    if output_name is not None and not re.fullmatch(r"[A-Za-z0-9_]+", output_name):
+        raise ValueError("output_name: letters, digits and underscores")
     if user_likelihood:
         user_likelihood = os.path.abspath(user_likelihood)
         user_flag = f'-DSMCMC_USER_LIKELIHOOD="{user_likelihood}"'
         _EXTRA["files"] = [user_likelihood]
-        user_lib = output or os.path.join(LIB_DIR, "libsmcmc_amd_user.so")
+        user_lib = output or os.path.join(LIB_DIR, f"libsmcmc_amd_{output_name or 'user'}.so")
     else:
         _EXTRA["files"] = []
     os.makedirs(OBJ_DIR, exist_ok=True)
     os.makedirs(LIB_DIR, exist_ok=True)
     plain_units = _units(None)
-    user_units = _units(user_flag) if user_flag else []
+    user_units = _units(user_flag, output_name or "user") if user_flag else []
     want_plain = with_plain or not user_flag
     todo, seen = [], set()
     for u in (plain_units if want_plain else []) + user_units:
@@ -319,5 +326,6 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--user-likelihood", help="header defining smcmc_user_loglike<DP>: build a library that serves SMCMC_LIKE_USER")
     ap.add_argument("--output", help="path of the library built with --user-likelihood")
+    ap.add_argument("--output-name", help="build lib/libsmcmc_amd_<name>.so from objects of its own: several user libraries side by side")
     a = ap.parse_args()
-    print(build(verbose=True, user_likelihood=a.user_likelihood, output=a.output))
+    print(build(verbose=True, user_likelihood=a.user_likelihood, output=a.output, output_name=a.output_name))

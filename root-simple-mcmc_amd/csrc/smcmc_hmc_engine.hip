@@ -58,6 +58,11 @@ struct smcmc_hmc {
     DeviceBuffer<double> d_Eperm;  // QUADFORM: Error in hmc_step_kernel's layout (d_E holds the matrix kernels')
     DeviceBuffer<double> d_covE, d_cov_avg, d_fd_grad;
     bool cov_dirty = true;         // fEstimatedError / fAveragePoint changed since the last upload
+    // the caller's gradient matrix of the quadratic form (smcmc_hmc_set_gradient_matrix): gradient types 0 / 1 / 4 contract
+    // with it instead of Error, in the kernel that runs the quadratic form without it
+    std::vector<double> grad_matrix;   // [dim][dim] row-major; empty = none
+    DeviceBuffer<double> d_Gperm;      // in the layout that kernel reads Error in (hmc_kernel_layout)
+    bool grad_dirty = false;           // grad_matrix changed since the last upload
     // the running average point / covariance on the device (hmc_absorb_* kernels): the host copy in *shared follows
     // on demand (hmc_pull) or when UpdateErrorMatrix decides to run
     DeviceBuffer<double> d_avg, d_exxt, d_hcov, d_hscal;
@@ -85,11 +90,22 @@ size_t hmc_gacc_doubles(const smcmc_hmc* h) {
 bool hmc_adaptive(const smcmc_hmc* h) { return h->mean_epsilon > 0.0 || h->leapfrog > 0; }
 // likelihoods without a gradient of their own (the reference's functors throw / return false, TAsymLogLikelihood.H:34-36,
 // TSimpleHMC.H:85-89): HMC targets through PotentialGradient types 2 / 3 / 5 only
+// (a user library whose header defines SMCMC_USER_GRADIENT has one: smcmc_user_gradient_at)
 bool hmc_no_own_gradient(int like) {
+#ifdef SMCMC_USER_GRADIENT
+    if (like == SMCMC_LIKE_USER) return false;
+#endif
     return like == SMCMC_LIKE_USER || like == SMCMC_LIKE_ASYM || like == SMCMC_LIKE_HORRIFIC || like == SMCMC_LIKE_CONSTRAINED;
 }
-size_t hmc_like_doubles(int dim) { return (size_t)dim * dim + 2 * (size_t)dim + 8; }
+// likelihoods whose device function reads the parameter array as the caller gave it
+bool hmc_reads_params(int like) {
+    return like == SMCMC_LIKE_USER || like == SMCMC_LIKE_ASYM || like == SMCMC_LIKE_HORRIFIC || like == SMCMC_LIKE_CONSTRAINED;
+}
+// room for a matrix of the likelihood's and one of the gradient's
+size_t hmc_like_doubles(int dim) { return 2 * (size_t)dim * dim + 2 * (size_t)dim + 8; }
 bool hmc_generic_gradient(const smcmc_hmc* h) { return h->gradient_type == 2 || h->gradient_type == 3 || h->gradient_type == 5; }
+// gradient types 0 / 1 / 4 of the quadratic form with the caller's matrix (reference order only)
+bool hmc_gradient_matrix(const smcmc_hmc* h) { return !h->grad_matrix.empty() && !hmc_generic_gradient(h); }
 // the covariant gradient reads the running covariance: it has to be kept
 bool hmc_tracking(const smcmc_hmc* h) { return hmc_adaptive(h) || h->track_cov || h->gradient_type == 2; }
 
@@ -133,6 +149,10 @@ HmcParams hmc_params(smcmc_hmc* h, int nsteps, int init_only) {
         p.Eperm = h->d_Eperm;
         p.cov_Eperm = h->d_covE; p.cov_average = h->d_cov_avg; p.fd_grad = h->d_fd_grad;
     }
+    if (hmc_gradient_matrix(h) && !init_only) {
+        if (!h->use_matrix_exact) p.Eperm = h->d_Eperm;
+        p.Gperm = h->d_Gperm;
+    }
     return p;
 }
 
@@ -149,18 +169,50 @@ std::vector<double> hmc_permute(const smcmc_hmc* h, const double* M) {
     return perm;
 }
 
+// M [dim][dim] row-major -> the matrix layout of hmc_mfma_kernel<TI, false>:
+// out[(tile * D + j) * 16 + 4 rq + r] = M(16 tile + 4 r + rq, j)
+std::vector<double> hmc_exact_layout(const smcmc_hmc* h, const double* M) {
+    const int D = h->dim, ntiles = (D + 15) / 16;
+    std::vector<double> ex(hmc_exact_ex_doubles(D), 0.0);
+    for (int it = 0; it < ntiles; ++it)
+        for (int j = 0; j < D; ++j)
+            for (int rq = 0; rq < 4; ++rq)
+                for (int r = 0; r < 4; ++r) {
+                    const int i = 16 * it + 4 * r + rq;
+                    if (i < D) ex[((size_t)it * D + j) * 16 + 4 * rq + r] = M[(size_t)i * D + j];
+                }
+    return ex;
+}
+
+// the layout the reference-order kernel of this engine's quadratic form reads a matrix in
+std::vector<double> hmc_kernel_layout(const smcmc_hmc* h, const double* M) {
+    return h->use_matrix_exact ? hmc_exact_layout(h, M) : hmc_permute(h, M);
+}
+
 // buffers of the GENERIC gradient types, allocated when one is first asked for; the estimated error matrix and the
 // average point go up again whenever the pooled update changed them
 int hmc_generic_buffers(smcmc_hmc* h) {
     const int D = h->dim;
     const size_t perm_doubles = (size_t)h->W * D * kPanelCW, perm_bytes = sizeof(double) * perm_doubles;
-    if (h->likelihood == SMCMC_LIKE_QUADFORM && !h->d_Eperm) {
+    const bool step_kernel = hmc_generic_gradient(h) || !h->use_matrix_exact;   // (a gradient matrix alone: d_E serves)
+    if (h->likelihood == SMCMC_LIKE_QUADFORM && !h->d_Eperm && step_kernel) {
         DeviceBuffer<double> eperm;
         HIP_TRY(h, eperm.allocate(perm_doubles));
         const std::vector<double> perm = hmc_permute(h, h->like_params.data());
         HIP_TRY(h, hipMemcpyAsync(eperm, perm.data(), perm_bytes, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         h->d_Eperm = std::move(eperm);
+    }
+    if (hmc_gradient_matrix(h) && (h->grad_dirty || !h->d_Gperm)) {
+        const std::vector<double> perm = hmc_kernel_layout(h, h->grad_matrix.data());
+        if (!h->d_Gperm) {
+            DeviceBuffer<double> gperm;
+            HIP_TRY(h, gperm.allocate(perm.size()));
+            h->d_Gperm = std::move(gperm);
+        }
+        HIP_TRY(h, hipMemcpyAsync(h->d_Gperm, perm.data(), perm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // the staging vector goes out of scope; earlier steps are done with the old matrix
+        h->grad_dirty = false;
     }
     if (h->gradient_type == 3 && !h->d_fd_grad) {
         DeviceBuffer<double> fd;
@@ -578,6 +630,8 @@ int smcmc_hmc_set_likelihood_params(smcmc_hmc* h, const double* params, int coun
 int smcmc_hmc_set_exact_arithmetic(smcmc_hmc* h, int exact) {
     if (!h) return SMCMC_ERR_INVALID;
     if (h->started) return fail(h, SMCMC_ERR_LOGIC, "choose the arithmetic before Start");
+    if (!exact && !h->grad_matrix.empty())
+        return fail(h, SMCMC_ERR_UNSUPPORTED, "a gradient matrix runs in reference-order arithmetic only");
     h->exact = exact != 0;
     return SMCMC_OK;
 }
@@ -636,6 +690,23 @@ int smcmc_hmc_set_gradient_type(smcmc_hmc* h, int type) {
     return SMCMC_OK;
 }
 int smcmc_hmc_get_gradient_type(const smcmc_hmc* h) { return h ? h->gradient_type : -1; }
+int smcmc_hmc_has_gradient(const smcmc_hmc* h) { return (h && !hmc_no_own_gradient(h->likelihood)) ? 1 : 0; }
+// GradientError of BadGrad.C:33-41 for the built-in quadratic form; applied by the next step (hmc_generic_buffers)
+int smcmc_hmc_set_gradient_matrix(smcmc_hmc* h, const double* G, int count) {
+    if (!h || count < 0 || (count > 0 && !G)) return SMCMC_ERR_INVALID;
+    if (h->likelihood != SMCMC_LIKE_QUADFORM)
+        return fail(h, SMCMC_ERR_INVALID, "a gradient matrix belongs to SMCMC_LIKE_QUADFORM");
+    if (count == 0) {
+        h->grad_matrix.clear();
+        h->grad_dirty = false;
+        return SMCMC_OK;
+    }
+    if ((size_t)count != (size_t)h->dim * h->dim) return fail(h, SMCMC_ERR_INVALID, "the gradient matrix has dim*dim entries");
+    if (!h->exact) return fail(h, SMCMC_ERR_UNSUPPORTED, "a gradient matrix runs in reference-order arithmetic only");
+    h->grad_matrix.assign(G, G + count);
+    h->grad_dirty = true;
+    return SMCMC_OK;
+}
 int smcmc_hmc_set_track_covariance(smcmc_hmc* h, int on) {
     if (!h) return SMCMC_ERR_INVALID;
     h->track_cov = on != 0;
@@ -697,22 +768,13 @@ int smcmc_hmc_start(smcmc_hmc* h, const double* x0, int broadcast) {
     // (HORRIFIC reads no parameters: this engine holds what it is given to the user likelihood's limit)
     std::vector<double> prm;
     int st = check_like_params(h, h->likelihood == SMCMC_LIKE_HORRIFIC ? (int)SMCMC_LIKE_USER : h->likelihood,
-                               hmc_like_doubles(D), "a user likelihood takes at most dim^2 + 2 dim + 8 parameters", prm);
+                               hmc_like_doubles(D), "a user likelihood takes at most 2 dim^2 + 2 dim + 8 parameters", prm);
     if (st) return st;
     if (h->likelihood == SMCMC_LIKE_QUADFORM) {
         h->use_mfma = !h->exact && D <= kMfDimMax;
         h->use_matrix_exact = h->exact && D <= kMfDimMax;
         if (h->use_matrix_exact) {
-            // Ex[(tile * D + j) * 16 + 4 rq + r] = Error(16 tile + 4 r + rq, j)
-            const int ntiles = (D + 15) / 16;
-            std::vector<double> ex(hmc_exact_ex_doubles(D), 0.0);
-            for (int it = 0; it < ntiles; ++it)
-                for (int j = 0; j < D; ++j)
-                    for (int rq = 0; rq < 4; ++rq)
-                        for (int r = 0; r < 4; ++r) {
-                            const int i = 16 * it + 4 * r + rq;
-                            if (i < D) ex[((size_t)it * D + j) * 16 + 4 * rq + r] = h->like_params[(size_t)i * D + j];
-                        }
+            const std::vector<double> ex = hmc_exact_layout(h, h->like_params.data());
             HIP_TRY(h, hipMemcpyAsync(h->d_E, ex.data(), ex.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, hipStreamSynchronize(h->stream));
         }
@@ -744,7 +806,7 @@ int smcmc_hmc_start(smcmc_hmc* h, const double* x0, int broadcast) {
         h->use_mfma = false;
         h->use_matrix_exact = false;
     }
-    if (hmc_no_own_gradient(h->likelihood)) {
+    if (hmc_reads_params(h->likelihood)) {
         if (!prm.empty())
             HIP_TRY(h, hipMemcpyAsync(h->d_like, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -804,6 +866,9 @@ int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
     if (hmc_generic_gradient(h)) {
         if (!h->exact) return fail(h, SMCMC_ERR_UNSUPPORTED, "gradient types 2, 3 and 5 run in reference-order arithmetic only");
         int gst = hmc_generic_buffers(h);
+        if (gst) return gst;
+    } else if (hmc_gradient_matrix(h)) {
+        int gst = hmc_generic_buffers(h);   // the gradient matrix in the layout of the kernel that runs
         if (gst) return gst;
     }
     if (hmc_per_chain(h)) {

@@ -44,7 +44,10 @@ hipError_t launch_hmc<SMCMC_PANEL_W, kPanelCW>(const HmcParams& p, int like, hip
         case SMCMC_LIKE_ASYM: return go_hmc_no_gradient<W, CW, SMCMC_LIKE_ASYM>(p, s);
         case SMCMC_LIKE_HORRIFIC: return go_hmc_no_gradient<W, CW, SMCMC_LIKE_HORRIFIC>(p, s);
         case SMCMC_LIKE_CONSTRAINED: return go_hmc_no_gradient<W, CW, SMCMC_LIKE_CONSTRAINED>(p, s);
-#ifdef SMCMC_USER_LIKELIHOOD_ANY_DIM
+#if defined(SMCMC_USER_LIKELIHOOD_ANY_DIM) && defined(SMCMC_USER_GRADIENT)
+        // a user likelihood with a gradient of its own (smcmc_user_gradient_at): types 0 / 1 / 4 in the plain instantiation
+        case SMCMC_LIKE_USER: return go_hmc<W, CW, SMCMC_LIKE_USER>(p, s);
+#elif defined(SMCMC_USER_LIKELIHOOD_ANY_DIM)
         case SMCMC_LIKE_USER: return go_hmc_no_gradient<W, CW, SMCMC_LIKE_USER>(p, s);
 #endif
         default: return hipErrorInvalidValue;

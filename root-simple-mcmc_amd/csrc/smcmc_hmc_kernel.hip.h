@@ -90,6 +90,9 @@ struct HmcParams {
     double* pn;            // proposed momentum   [dim][npad]
     double* lane_f64;      // LOGL = -accepted potential, LOGL_PROPOSED = -proposed potential, ACCEPTANCE
     int32_t* lane_i32;     // NACCEPT, LAST_ACCEPT, TRIALS = step count
+    const double* Gperm;   // QUADFORM, gradient types 0 / 1 / 4: the caller's gradient matrix in the layout of Eperm
+                           // (smcmc_hmc_set_gradient_matrix); nullptr = the likelihood's own, Eperm.  Set: the gradient is
+                           // no longer Error q, and the potential contracts with Eperm once more
 };
 
 template <int W, int CW, int LIKE, bool GENERIC = false>
@@ -210,10 +213,29 @@ __global__ void __launch_bounds__(W * kWave) hmc_step_kernel(const HmcParams p) 
     };
 
     // the likelihood's own potential gradient at qn for the owned components -> gr[]  (PotentialGradient type 0
-    // with the user gradient, TSimpleHMC.H:467-492: the negated gradient of log L)
-    auto like_gradient = [&]() {
+    // with the user gradient, TSimpleHMC.H:467-492: the negated gradient of log L).  quad_matrix: the quadratic form's
+    // operand, Eperm or the caller's gradient matrix.
+    auto like_gradient = [&](const double* quad_matrix) {
         __syncthreads();   // every owner has written its part of qn
-        if constexpr (LIKE == SMCMC_LIKE_ISO_GAUSS) {
+        if constexpr (LIKE == SMCMC_LIKE_USER) {
+#ifdef SMCMC_USER_GRADIENT
+            // the user's OptionalGradient (TSimpleHMC.H:79-89), one owned component at a time, every chain in its lane
+            const ChainColumn point{p.qn + chain, NP};
+#pragma unroll
+            for (int il = 0; il < CW; ++il) {
+                const int i = il * W + w;
+                const double g = (i < D) ? smcmc_user_gradient_at(point, p.like, D, i) : 0.0;
+                gr[il] = -g;       // TSimpleHMC.H:486
+            }
+            __syncthreads();       // every owner has read the whole point before anyone moves its part of it
+#else
+            // A library without a user gradient has no instantiation that runs types 0 / 1 / 4: only GENERIC exists, and
+            // go_hmc_no_gradient refuses every launch of it whose type is not 2 / 3 / 5, so this statement is never executed.
+            static_assert(GENERIC, "a user likelihood without SMCMC_USER_GRADIENT has no plain HMC instantiation");
+#pragma unroll
+            for (int il = 0; il < CW; ++il) gr[il] = 0.0;
+#endif
+        } else if constexpr (LIKE == SMCMC_LIKE_ISO_GAUSS) {
 #pragma unroll
             for (int il = 0; il < CW; ++il) {
                 const int i = il * W + w;
@@ -247,9 +269,11 @@ __global__ void __launch_bounds__(W * kWave) hmc_step_kernel(const HmcParams p) 
             }
         } else {
             // TDummyLogLikelihood.H:34-42: g[i] = 0; g[i] -= Error(i,j)*p[j], j ascending; then TSimpleHMC.H:486
-            contract(p.Eperm, nullptr);
+            contract(quad_matrix, nullptr);
         }
     };
+    // the gradient's operand of the quadratic form: the caller's matrix (BadGrad.C:33-41, GradientError) or Error itself
+    const double* const grad_matrix = (p.Gperm != nullptr) ? p.Gperm : p.Eperm;
 
     // log L at qn (valid in wavefront 0) and, on the way, the kinetic energy of pn
     auto log_likelihood_at_qn = [&](bool gradient_is_current, double& ke) {
@@ -284,7 +308,7 @@ __global__ void __launch_bounds__(W * kWave) hmc_step_kernel(const HmcParams p) 
             // log L = -1/2 q^T Error q.  The gradient at the final position is still in gr[]
             // (gr = Error q): the potential is folded from it in dimension order instead of
             // re-running the D^2-term sum of TDummyLogLikelihood.H:24-28 serially.
-            if (!gradient_is_current) like_gradient();
+            if (!gradient_is_current) like_gradient(p.Eperm);
             double usum = 0.0;
             gather([&](int il, double& a, double& b) {
                        const int i = il * W + w;
@@ -300,7 +324,7 @@ __global__ void __launch_bounds__(W * kWave) hmc_step_kernel(const HmcParams p) 
     // PotentialGradient (:467-532) at qn -> gr[]
     auto gradient = [&]() {
         if constexpr (!GENERIC) {
-            like_gradient();
+            like_gradient(grad_matrix);
         } else {
             if (p.gradient_type == 2) {
                 // CovariantGradient (:447-454): grad[i] += fEstimatedError(i,j) * (point[j] - fAveragePoint[j])
@@ -341,12 +365,14 @@ __global__ void __launch_bounds__(W * kWave) hmc_step_kernel(const HmcParams p) 
 #pragma unroll
                 for (int il = 0; il < CW; ++il) gr[il] = 0.0;
             } else {
-                like_gradient();
+                like_gradient(grad_matrix);
             }
         }
     };
-    // is gr[] the likelihood's own gradient after gradient()?  (the quadratic form folds its potential from it)
-    const bool own_gradient = !GENERIC || !(p.gradient_type == 2 || p.gradient_type == 3 || p.gradient_type == 5);
+    // is gr[] the likelihood's own gradient after gradient()?  (the quadratic form folds its potential from it; with a
+    // gradient matrix of the caller's it is not Error q)
+    const bool own_gradient = (!GENERIC || !(p.gradient_type == 2 || p.gradient_type == 3 || p.gradient_type == 5)) &&
+                              p.Gperm == nullptr;
 
     if (p.init_only) {
         // Start (:210-269): SetPosition's Potential(start) for every chain

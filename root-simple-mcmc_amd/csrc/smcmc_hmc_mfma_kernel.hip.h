@@ -48,7 +48,9 @@ inline size_t hmc_exact_ex_doubles(int dim) { return (size_t)((dim + 15) / 16) *
 
 // TI = 16-component tiles a wavefront owns: dim <= 128 TI.
 // FUSED = false: the reference's order, g[i] -= Error(i,j) * q[j] as an un-fused multiply and subtract, j
-// ascending (TDummyLogLikelihood.H:34-42), on the vector pipe in the same layout (p.Eperm = Ex).
+// ascending (TDummyLogLikelihood.H:34-42), on the vector pipe in the same layout (p.Eperm = Ex).  With the caller's
+// gradient matrix (p.Gperm, in the layout of Ex) the leapfrog contracts with it instead, and the potential of the
+// proposal with Error once more: L + 2 passes of the same loop per step instead of L + 1.
 template <int kMfTI, bool FUSED = true>
 __global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParams p) {
     __shared__ double qs[16 * kMfW * kMfTI * kMfCT];   // [component][chain]: the published vector
@@ -140,9 +142,10 @@ __global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParam
         return sacc;
     };
 
-    // gr = Error q for the owned components, q = the positions in qs (PotentialGradient,
-    // TSimpleHMC.H:467-492, for the quadratic form of TDummyLogLikelihood.H:34-42)
-    auto gradient = [&]() {
+    // gr = M q for the owned components, q = the positions in qs (PotentialGradient,
+    // TSimpleHMC.H:467-492, for the quadratic form of TDummyLogLikelihood.H:34-42); M = Error or, in the reference's
+    // order, the caller's gradient matrix
+    auto gradient = [&](const double* matrix) {
         __syncthreads();   // every owner has written its positions
 #pragma unroll
         for (int t = 0; t < kMfTI; ++t)
@@ -153,10 +156,10 @@ __global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParam
 #pragma unroll
             for (int t = 0; t < kMfTI; ++t) {
                 if (!owns(t)) continue;
-                pm_contract(p.Eperm + lane + (size_t)(t * kMfW + w) * nkqp * 64, qs_lane, nkqp, gr[t][0], gr[t][1]);
+                pm_contract(matrix + lane + (size_t)(t * kMfW + w) * nkqp * 64, qs_lane, nkqp, gr[t][0], gr[t][1]);
             }
         } else {
-            const double* ex = p.Eperm + 4 * rq;
+            const double* ex = matrix + 4 * rq;
             const double* qv = qs + c;
             f64x4v en[kMfTI];   // column j + 1 of Error is fetched while column j is consumed
 #pragma unroll
@@ -237,7 +240,7 @@ __global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParam
     if (p.init_only) {
         // Start (:210-269): SetPosition's Potential(start) for every chain
         load_q();
-        gradient();
+        gradient(p.Eperm);
         const double u0 = potential();
         if (summer && mychain < p.nchains) {
             p.lane_f64[SMCMC_LANE_LOGL * NP + mychain] = -u0;
@@ -255,6 +258,9 @@ __global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParam
         reversal = p.lane_f64[kHmcLaneReversalLen * NP + mychain];
         lfrog = p.lane_i32[kHmcLaneLeapfrog * NP + mychain];
     }
+
+    // what the leapfrog contracts with: Error, or the caller's gradient matrix (smcmc_hmc_set_gradient_matrix)
+    const double* const grad_matrix = (!FUSED && p.Gperm != nullptr) ? p.Gperm : p.Eperm;
 
     for (int s = 0; s < p.nsteps; ++s) {
         const uint64_t step = (uint64_t)(p.step0 + (uint32_t)s + 1u);   // ++fStepCount, :286
@@ -361,13 +367,13 @@ __global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParam
                         if (comp(t, r) < D) qs[slot(t, ct, r)] = qs[slot(t, ct, r)] + eps[ct] * (m + m) / 2.0;
                     }
             }
-            gradient();                                                 // for the potential below
+            gradient(p.Eperm);                                          // for the potential below
         } else {
-            gradient();                                                 // :615
+            gradient(grad_matrix);                                      // :615
             kick(-1);                                                   // :618-620
             for (int ls = 0; ls < Lmax; ++ls) {
                 drift(ls);
-                gradient();
+                gradient(grad_matrix);
                 kick(ls);
                 if (reversal_wanted && ls < Lmax - 1) {
                     // has the direction reversed (:633-638)?  inner += pNew[j]*momentum[j], dimension order; the
@@ -378,6 +384,8 @@ __global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParam
                     if (summer && ls < Lmine - 1 && !(inner >= 0.0)) status = 2;
                 }
             }
+            // the last gradient is not Error q: the potential (the engine's association) needs that one
+            if (grad_matrix != p.Eperm) gradient(p.Eperm);
         }
         if (summer && p.adaptive) {
             const double my_eps = (lane < 16) ? eps[0] : eps[1];        // chain base + lane is this lane's chain tile lane >> 4

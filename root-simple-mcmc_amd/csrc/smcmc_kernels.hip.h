@@ -352,10 +352,21 @@ __device__ __forceinline__ double dmax(double a, double b) { return __builtin_fm
 //     template <class Point> __device__ double smcmc_user_loglike_at(const Point& p, const double* params, int D);
 // (p[i], 0 <= i < D, reads coordinate i of the chain's point from its [dim][chain] image in device memory) is served at
 // those dimensions too, in reference-order arithmetic.
+// A header with the any-dimension form may also give the HMC engine a gradient of its own (the OptionalGradient of
+// TSimpleHMC<UserLikelihood, OptionalGradient>, TSimpleHMC.H:79-89):
+//     #define SMCMC_USER_GRADIENT 1
+//     template <class Point> __device__ double smcmc_user_gradient_at(const Point& p, const double* params, int D, int i);
+// returns component i of grad log L at p (what the reference functor writes to g[i]; the engine negates it, :486).  One
+// component per call, because in hmc_step_kernel every wavefront owns a slice of the components of its 64 chains: all
+// owners compute theirs at once, each lane reading its chain's point through the same view as smcmc_user_loglike_at.
+// Bit parity with a host functor is a matter of keeping that functor's operation order inside one component.
 #ifdef SMCMC_USER_LIKELIHOOD
 }  // namespace smcmc
 #include SMCMC_USER_LIKELIHOOD
 namespace smcmc {
+#if defined(SMCMC_USER_GRADIENT) && !defined(SMCMC_USER_LIKELIHOOD_ANY_DIM)
+#error "SMCMC_USER_GRADIENT needs SMCMC_USER_LIKELIHOOD_ANY_DIM: HMC runs a user likelihood through smcmc_user_loglike_at"
+#endif
 #endif
 
 // log-likelihood of the point p[0..D) held in registers.

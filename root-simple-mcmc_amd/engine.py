@@ -759,7 +759,8 @@ class HmcEngine:
 
     def __init__(self, dim, nchains=1, likelihood=LIKE_ISO_GAUSS, likelihood_params=None, seed=20240607,
                  chain_offset=0, device=0, stream=None, exact=True, library=None, mode=MODE_POOLED):
-        # library: path of a build that carries a user likelihood (LIKE_USER as an HMC target through gradient type 2 / 3 / 5)
+        # library: path of a build that carries a user likelihood (LIKE_USER as an HMC target through gradient type 2 / 3 / 5,
+        # and through 0 / 1 / 4 when its header has a gradient: has_gradient)
         self._lib = _capi.load(library)
         self.dim, self.nchains = int(dim), int(nchains)
         h = C.c_void_p()
@@ -821,6 +822,21 @@ class HmcEngine:
         self._check(self._lib.smcmc_hmc_set_gradient_type(self._h, int(gradient_type)))
 
     def GetGradientType(self): return int(self._lib.smcmc_hmc_get_gradient_type(self._h))
+
+    @property
+    def has_gradient(self):
+        """Are gradient types 0 / 1 / 4 served?  True for ISO_GAUSS, QUADFORM, ROSENBROCK and for a user library whose header
+        defines smcmc_user_gradient_at; False for the stress targets and a user library without a gradient."""
+        return bool(self._lib.smcmc_hmc_has_gradient(self._h))
+
+    def SetGradientMatrix(self, G=None):
+        """LIKE_QUADFORM: gradient types 0 / 1 / 4 compute g = -G q instead of -Error q from the next step on (BadGrad.C's
+        GradientError; the potential stays that of Error).  None clears it.  Reference-order arithmetic only."""
+        if G is None:
+            self._check(self._lib.smcmc_hmc_set_gradient_matrix(self._h, None, 0))
+            return
+        g = _f64(G).ravel()
+        self._check(self._lib.smcmc_hmc_set_gradient_matrix(self._h, _ptr(g), g.size))
     def sync(self): self._check(self._lib.smcmc_hmc_sync(self._h))
 
     def SetMode(self, mode):
