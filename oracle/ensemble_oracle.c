@@ -397,7 +397,7 @@ static void ens_reset_lanes(oracle_ensemble* e) {
     memset(e->acc, 0, sizeof(double) * (size_t)e->ngroups * (size_t)ens_npacked(D));
 }
 
-/* The consequences of an UpdateProposal on the shared proposal for the chains (the engine's update_shared):
+/* The consequences of an UpdateProposal on the shared proposal for the chains (the engine's update_consequences):
  * sigma rescale and de-weighting per chain; when the ladder ended in ResetProposal (TSimpleMCMC.H:1389) the
  * chains are reset with it, the shared centre restarting from chain 0's current point. */
 static void ens_after_update(oracle_ensemble* e) {

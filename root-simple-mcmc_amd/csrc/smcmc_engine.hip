@@ -191,16 +191,10 @@ __global__ void reset_lanes_kernel(double* lane_f64, int32_t* lane_i32, int npad
     if (*sg < sigma_floor) *sg = sigma_reset;
 }
 
-size_t npacked(const smcmc_engine* h) { return (size_t)(h->dim + 1) * (h->dim + 2) / 2; }
-
 // doubles of the moment accumulators: per 64-chain group for the register kernels, per
 // (slice, 16x16 tile) for the large-dimension fold kernel
 size_t gacc_doubles(const smcmc_engine* h) {
-    if (h->panel_w) {
-        const size_t T = (size_t)(h->dim + 1 + 15) / 16;
-        return (size_t)fold_slices(h->dim) * (T * (T + 1) / 2) * 4 * kWave;
-    }
-    return (size_t)h->ngroups * h->nt * 4 * kWave;
+    return h->panel_w ? fold_gacc_doubles(h->dim) : (size_t)h->ngroups * h->nt * 4 * kWave;
 }
 
 // decomposition (and, for QUADFORM, the Error matrix) zero-padded to [dp][dp]
@@ -384,15 +378,10 @@ int upload_like(smcmc_engine* h) {
 
 // sigma rescale + acceptance de-weighting of every chain after an UpdateProposal on the shared proposal
 int adjust_lanes(smcmc_engine* h, double sigma_scale) {
-    const SharedProposal& P = *h->prop;
-    double acc_w = -1.0, acc_wW = 0.0;
-    if (P.acceptanceDeweight > 0.0) {
-        acc_w = 1.0 - std::min(P.acceptanceDeweight, 1.0);
-        acc_wW = acc_w * P.acceptanceWindow;
-    }
+    const SharedProposal::Deweight acc = h->prop->acceptanceDeweights();
     const int threads = 256;
     hipLaunchKernelGGL(adjust_lanes_kernel, dim3((h->nchains + threads - 1) / threads), dim3(threads), 0, h->stream,
-                       h->d_lane_f64, h->npad, h->nchains, sigma_scale, acc_w, acc_wW);
+                       h->d_lane_f64, h->npad, h->nchains, sigma_scale, acc.w, acc.wW);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("adjust_lanes launch: ") + hipGetErrorString(e));
     return SMCMC_OK;
@@ -419,28 +408,29 @@ int reset_lanes(smcmc_engine* h) {
     return SMCMC_OK;
 }
 
-
-// UpdateProposal() on the shared proposal and its consequences for the chains: every chain's sigma is
-// rescaled by the factor the shared template was, sqrt(old trace / new trace) (TSimpleMCMC.H:1042), and its
-// acceptance trials are de-weighted (:1081-1086); when the decomposition ladder ended in ResetProposal (:1389)
-// the chains are reset with it, about chain 0's current point.
-int update_shared(smcmc_engine* h) {
+// What an update of the shared proposal means for the chains: every chain's sigma is rescaled by the factor the shared
+// template was, sqrt(old trace / new trace) (TSimpleMCMC.H:1042), and its acceptance trials are de-weighted
+// (:1081-1086); when the decomposition ladder ended in ResetProposal (:1389) the chains are reset with it, about
+// chain 0's current point, and the moments gathered so far are dropped.
+int update_consequences(smcmc_engine* h) {
     SharedProposal& P = *h->prop;
-    int st = status_of(h, P.update(false));
+    int st = adjust_lanes(h, P.lastSigmaScale);
+    if (st || P.lastPath != 4) return st;
+    std::vector<double> x0;
+    st = read_chain0(h, x0);
     if (st) return st;
-    st = adjust_lanes(h, P.lastSigmaScale);
+    P.lastPoint = x0;
+    P.centre = x0;
+    st = reset_lanes(h);
     if (st) return st;
-    if (P.lastPath == 4) {
-        std::vector<double> x0;
-        st = read_chain0(h, x0);
-        if (st) return st;
-        P.lastPoint = x0;
-        P.centre = x0;
-        st = reset_lanes(h);
-        if (st) return st;
-        HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * gacc_doubles(h), h->stream));
-    }
+    HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * gacc_doubles(h), h->stream));
     return SMCMC_OK;
+}
+
+// UpdateProposal() on the shared proposal and its consequences for the chains
+int update_shared(smcmc_engine* h) {
+    const int st = status_of(h, h->prop->update(false));
+    return st ? st : update_consequences(h);
 }
 
 // ---- the pooled update on the device (smcmc_pooled_update.hip.h) ---------------------------------
@@ -488,11 +478,6 @@ int pull_raw(smcmc_engine* h) {
     return SMCMC_OK;
 }
 
-int upload_shared(smcmc_engine* h);
-int adjust_lanes(smcmc_engine* h, double sigma_scale);
-int read_chain0(smcmc_engine* h, std::vector<double>& x0);
-int reset_lanes(smcmc_engine* h);
-
 // Looks at the status word of the latest device update.  A decomposition that failed there continues on the host
 // exactly where SharedProposal::update would have: the fallback ladder, then the per-chain consequences.
 int check_pending(smcmc_engine* h) {
@@ -511,33 +496,11 @@ int check_pending(smcmc_engine* h) {
     if (st) return st;
     h->device_stale = true;
     // what SharedProposal::update does around the decomposition (the device did the numbers)
-    ++P.updateCount;
-    if (status == kPooledInvalidTrace) return status_of(h, UpdateStatus::InvalidTrace);
-    {
-        const double maxUp = (double)h->dim * (double)h->dim;
-        P.nextUpdate = (int)(P.acceptanceWindow + maxUp - maxUp / (0.5 * P.successes + 1.0));
-        if (P.acceptanceDeweight > 0.0) {
-            if (P.acceptanceDeweight > 1.0) P.acceptanceDeweight = 1.0;
-            const double w = 1.0 - P.acceptanceDeweight;
-            P.acceptanceTrials = std::max(1.0, w * P.acceptanceTrials);
-            P.acceptanceTrials = std::min(P.acceptanceTrials, w * P.acceptanceWindow);
-        }
-        if (P.covDeweight > 1.0) P.covDeweight = 1.0;
-    }
+    if (!P.bookkeepUpdate(status != kPooledInvalidTrace)) return status_of(h, UpdateStatus::InvalidTrace);
     st = status_of(h, P.finishUpdateOnHost(h->h_scal[kPsLastScale]));
     if (st) return st;
-    st = adjust_lanes(h, P.lastSigmaScale);
+    st = update_consequences(h);
     if (st) return st;
-    if (P.lastPath == 4) {
-        std::vector<double> x0;
-        st = read_chain0(h, x0);
-        if (st) return st;
-        P.lastPoint = x0;
-        P.centre = x0;
-        st = reset_lanes(h);
-        if (st) return st;
-        HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * gacc_doubles(h), h->stream));
-    }
     return upload_shared(h);
 }
 
@@ -587,23 +550,12 @@ int device_apply(smcmc_engine* h) {
     if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("pooled update launch: ") + hipGetErrorString(e));
     // the host-only half of SharedProposal::update, optimistically (check_pending takes it back if the device says no)
     h->before_update = {P.updateCount, P.nextUpdate, P.lastPath, P.acceptanceTrials, P.decompFull};
-    ++P.updateCount;
-    const double maxUp = (double)h->dim * (double)h->dim;
-    P.nextUpdate = (int)(P.acceptanceWindow + maxUp - maxUp / (0.5 * P.successes + 1.0));
-    if (P.covDeweight > 1.0) P.covDeweight = 1.0;
-    double acc_w = -1.0, acc_wW = 0.0;
-    if (P.acceptanceDeweight > 0.0) {
-        if (P.acceptanceDeweight > 1.0) P.acceptanceDeweight = 1.0;
-        const double w = 1.0 - P.acceptanceDeweight;
-        P.acceptanceTrials = std::max(1.0, w * P.acceptanceTrials);
-        P.acceptanceTrials = std::min(P.acceptanceTrials, w * P.acceptanceWindow);
-        acc_w = 1.0 - std::min(P.acceptanceDeweight, 1.0);
-        acc_wW = acc_w * P.acceptanceWindow;
-    }
+    (void)P.bookkeepUpdate(true);
     P.lastPath = 0;
     P.decompFull = false;
+    const SharedProposal::Deweight acc = P.acceptanceDeweights();
     // (the kernel also writes the update's scalars into h_scal, pinned and device-visible: no copy command behind it)
-    e = launch_pooled_adjust_lanes(h->d_lane_f64, h->npad, h->nchains, h->d_scal, acc_w, acc_wW, SMCMC_LANE_SIGMA,
+    e = launch_pooled_adjust_lanes(h->d_lane_f64, h->npad, h->nchains, h->d_scal, acc.w, acc.wW, SMCMC_LANE_SIGMA,
                                    SMCMC_LANE_ACCEPTANCE_TRIALS, h->h_scal_dev, h->stream);
     if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("adjust_lanes launch: ") + hipGetErrorString(e));
     if (!h->h_scal_dev)
@@ -614,8 +566,8 @@ int device_apply(smcmc_engine* h) {
     return SMCMC_OK;
 }
 
-// The ring of per-step states behind multi-step launches of the pooled large-dimension path (at most 8 steps, at
-// most 2 GiB); 0 steps when even two states do not fit the budget.
+// The ring of per-step states behind multi-step launches of the pooled large-dimension path (at most kFoldMaxSrc = 16
+// steps, at most 4 GiB); 0 steps when even two states do not fit the budget.
 int ensure_ring(smcmc_engine* h) {
     if (h->ring_steps >= 0) return SMCMC_OK;
     const size_t state = sizeof(double) * (size_t)h->npad * h->dim;
@@ -636,17 +588,11 @@ int ensure_ring(smcmc_engine* h) {
     return SMCMC_OK;
 }
 
-// Folds `n` points ([dim][npad] each, in this order) into the moment groups: one launch, the accumulators in registers
-// from the first point to the last.
+// Folds `n` points ([dim][npad] each, in this order) into the moment groups, kFoldMaxSrc of them per launch
 int fold_points(smcmc_engine* h, const double* const* pts, int n) {
     for (int done = 0; done < n; done += smcmc::kFoldMaxSrc) {
-        smcmc::FoldRingParams fp;
-        std::memset(&fp, 0, sizeof(fp));
-        fp.nsrc = std::min(n - done, (int)smcmc::kFoldMaxSrc);
-        for (int k = 0; k < fp.nsrc; ++k) fp.src[k] = pts[done + k];
-        fp.c0 = h->d_c0; fp.nchains = h->nchains; fp.npad = h->npad; fp.D = h->dim; fp.slice_chains = h->slice_chains;
-        fp.gacc = h->d_gacc; fp.mask = nullptr;
-        const hipError_t e = smcmc::launch_fold_ring(h->fold, fp, h->stream);
+        const hipError_t e = smcmc::fold_points(h->fold, pts + done, std::min(n - done, (int)smcmc::kFoldMaxSrc), h->d_c0,
+                                                nullptr, h->d_gacc, h->stream);
         if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("fold kernel launch: ") + hipGetErrorString(e));
     }
     return SMCMC_OK;
@@ -696,15 +642,8 @@ void pc_pack_decomp(const SharedProposal& P, std::vector<double>& ut) {
 }
 
 void pc_deweights(const SharedProposal& P, double& acc_w, double& acc_wW, double& cov_w, double& cov_wW) {
-    acc_w = -1.0; acc_wW = 0.0; cov_w = -1.0; cov_wW = 0.0;
-    if (P.acceptanceDeweight > 0.0) {
-        acc_w = 1.0 - std::min(P.acceptanceDeweight, 1.0);
-        acc_wW = acc_w * P.acceptanceWindow;
-    }
-    if (P.covDeweight > 0.0) {
-        cov_w = 1.0 - std::min(P.covDeweight, 1.0);
-        cov_wW = cov_w * P.covWindow;
-    }
+    const SharedProposal::Deweight acc = P.acceptanceDeweights(), cov = P.covDeweights();
+    acc_w = acc.w; acc_wW = acc.wW; cov_w = cov.w; cov_wW = cov.wW;
 }
 
 // Hands the template *h->prop (what InitializeState / RestoreState / ResetProposal computed once on the host) to every
@@ -938,14 +877,8 @@ StepParams make_params(smcmc_engine* h, int nsteps, int metropolis) {
     asig = std::sqrt(asig / P.acceptanceWindow);
     p.asig = asig;
     p.max_up = (double)h->dim * (double)h->dim;             // :1050
-    if (P.acceptanceDeweight > 0.0) {
-        const double w = 1.0 - std::min(P.acceptanceDeweight, 1.0);
-        p.acc_w = w;
-        p.acc_wW = w * P.acceptanceWindow;
-    } else {
-        p.acc_w = -1.0;
-        p.acc_wW = 0.0;
-    }
+    const SharedProposal::Deweight acc = P.acceptanceDeweights();
+    p.acc_w = acc.w; p.acc_wW = acc.wW;
     p.per_lane_update = (h->mode == SMCMC_MODE_FROZEN) ? 1 : 0;
     p.step_rms_window = h->step_rms_window;
     p.has_forced = h->has_forced ? 1 : 0;
@@ -983,6 +916,44 @@ hipError_t launch_panel_exact(smcmc_engine* h, const PanelParams& q) {
                              : launch_panel<8, kPanelCW>(q, h->likelihood, true, h->stream);
 }
 
+// The large-dimension kernels' view of a launch `p`: the fields the two parameter blocks share, the large-dimension
+// images, and whether a uniform dimension or a scan asks for the SPECIAL instantiation.  nsteps, step0 and Uperm are
+// set per segment (launch_panel_segment); nothing is saved unless the caller says so.
+PanelParams panel_params(smcmc_engine* h, const StepParams& p) {
+    PanelParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.nchains = p.nchains; q.npad = p.npad; q.dim = p.dim; q.metropolis = p.metropolis;
+    q.chain_offset = p.chain_offset; q.seed = p.seed;
+    q.Uperm = h->d_U; q.like = h->d_like;
+    q.like_csr = QuadCsr{h->d_like_rowptr, h->d_like_cols, h->d_like_vals, h->d_like_rows};
+    q.target = p.target; q.acc_window = p.acc_window; q.asig = p.asig; q.max_up = p.max_up;
+    q.acc_w = p.acc_w; q.acc_wW = p.acc_wW; q.per_lane_update = p.per_lane_update;
+    q.step_rms_window = p.step_rms_window; q.full_u = h->prop->decompFull ? 1 : 0;
+    q.x = p.x; q.lane_f64 = p.lane_f64; q.lane_i32 = p.lane_i32;
+    q.save_stride = 1;
+    q.has_forced = p.has_forced; q.forced = p.forced;
+    q.proposed = p.proposed;
+    q.scratch = h->d_scratch;
+    q.uniform = p.uniform; q.scan_dim = p.scan_dim; q.scan_uniform = p.scan_uniform;
+    q.scan_a = p.scan_a; q.scan_b = p.scan_b;
+    for (int d = 0; d < h->dim; ++d)
+        if (h->prop->ptype[d] == 1) q.special = 1;
+    if (p.scan_dim >= 0) q.special = 1;
+    return q;
+}
+
+// One launch of `seg` steps from h->total_steps, which it advances: the matrix-pipe kernel on its operand layout in the
+// fused order, the reference-order kernel otherwise.
+int launch_panel_segment(smcmc_engine* h, PanelParams& q, int seg, bool exact) {
+    q.nsteps = seg;
+    q.step0 = h->total_steps;
+    q.Uperm = exact ? h->d_U : h->d_Uop;   // fused order: the proposal on the matrix pipe
+    const hipError_t e = exact ? launch_panel_exact(h, q) : launch_panel_mfma(q, h->likelihood, h->stream);
+    if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("panel kernel launch: ") + hipGetErrorString(e));
+    h->total_steps += (uint32_t)seg;
+    return SMCMC_OK;
+}
+
 int launch(smcmc_engine* h, int nsteps, int metropolis, int stride, double* save_x, double* save_logl) {
     if (!h) return SMCMC_ERR_INVALID;
     ON_DEVICE(h);
@@ -1016,25 +987,7 @@ int launch(smcmc_engine* h, int nsteps, int metropolis, int stride, double* save
         return SMCMC_OK;
     }
     if (h->panel_w) {
-        PanelParams q;
-        std::memset(&q, 0, sizeof(q));
-        q.nchains = p.nchains; q.npad = p.npad; q.dim = p.dim; q.metropolis = p.metropolis;
-        q.chain_offset = p.chain_offset; q.seed = p.seed;
-        q.Uperm = h->d_U; q.like = h->d_like;
-        q.like_csr = QuadCsr{h->d_like_rowptr, h->d_like_cols, h->d_like_vals, h->d_like_rows};
-        q.target = p.target; q.acc_window = p.acc_window; q.asig = p.asig; q.max_up = p.max_up;
-        q.acc_w = p.acc_w; q.acc_wW = p.acc_wW; q.per_lane_update = p.per_lane_update;
-        q.step_rms_window = p.step_rms_window; q.full_u = h->prop->decompFull ? 1 : 0;
-        q.x = p.x; q.lane_f64 = p.lane_f64; q.lane_i32 = p.lane_i32;
-        q.save_stride = 1;
-        q.has_forced = p.has_forced; q.forced = p.forced;
-        q.proposed = p.proposed;
-        q.scratch = h->d_scratch;
-        q.uniform = p.uniform; q.scan_dim = p.scan_dim; q.scan_uniform = p.scan_uniform;
-        q.scan_a = p.scan_a; q.scan_b = p.scan_b;
-        for (int d = 0; d < h->dim; ++d)
-            if (h->prop->ptype[d] == 1) q.special = 1;
-        if (p.scan_dim >= 0) q.special = 1;
+        PanelParams q = panel_params(h, p);
         const bool exact = h->exact || h->prop->decompFull;
         const bool special_proposal = q.special != 0;
         if (exact && q.proposed != nullptr) q.special = 1;   // the SPECIAL instantiation also stores the proposal
@@ -1074,18 +1027,9 @@ int launch(smcmc_engine* h, int nsteps, int metropolis, int stride, double* save
                     const int fst = fold_points(h, &px, 1);
                     if (fst) return fst;
                 }
-                q.nsteps = seg;
-                q.step0 = h->total_steps;
                 q.save_x = h->d_ring; q.save_logl = h->d_ring_logl; q.save_stride = 1;
-                hipError_t e;
-                if (!exact) {
-                    q.Uperm = h->d_Uop;
-                    e = launch_panel_mfma(q, h->likelihood, h->stream);
-                } else {
-                    q.Uperm = h->d_U;
-                    e = launch_panel_exact(h, q);
-                }
-                if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("panel kernel launch: ") + hipGetErrorString(e));
+                const int lst = launch_panel_segment(h, q, seg, exact);
+                if (lst) return lst;
                 q.save_x = nullptr; q.save_logl = nullptr;
                 // The point after step s of the launch is the one UpdateState sees at the start of step s + 1.  The one
                 // after the LAST step (= d_x) goes in here too when this call steps on; otherwise the next call folds it.
@@ -1098,7 +1042,6 @@ int launch(smcmc_engine* h, int nsteps, int metropolis, int stride, double* save
                     if (fst) return fst;
                 }
                 x_folded = more;
-                h->total_steps += (uint32_t)seg;
                 done += seg;
                 continue;
             }
@@ -1114,18 +1057,8 @@ int launch(smcmc_engine* h, int nsteps, int metropolis, int stride, double* save
                 seg = std::min(seg, h->moment_stride - phase);
             }
             if (q.has_forced) seg = 1;   // the forced step is a launch of its own (FORCED instantiation of the fused kernel)
-            q.nsteps = seg;
-            q.step0 = h->total_steps;
-            hipError_t e;
-            if (!exact) {
-                q.Uperm = h->d_Uop;   // fused order: the proposal on the matrix pipe
-                e = launch_panel_mfma(q, h->likelihood, h->stream);
-            } else {
-                q.Uperm = h->d_U;
-                e = launch_panel_exact(h, q);
-            }
-            if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("panel kernel launch: ") + hipGetErrorString(e));
-            h->total_steps += (uint32_t)seg;
+            const int lst = launch_panel_segment(h, q, seg, exact);
+            if (lst) return lst;
             done += seg;
             q.has_forced = 0;
         }
@@ -1224,9 +1157,9 @@ int smcmc_create(int dim, int nchains, int likelihood, uint64_t seed, uint32_t c
     HIP_TRY(h, h->d_like.allocate(like_doubles));
     HIP_TRY(h, h->d_c0.allocate(dp));
     HIP_TRY(h, h->d_gacc.allocate(gacc_doubles(h)));
-    HIP_TRY(h, h->d_moments.allocate(npacked(h)));
-    HIP_TRY(h, h->h_moments.allocate(npacked(h)));
-    HIP_TRY(h, h->d_chunks.allocate(npacked(h) * ((h->ngroups + kReduceChunk - 1) / kReduceChunk)));
+    HIP_TRY(h, h->d_moments.allocate(moments_packed(h->dim)));
+    HIP_TRY(h, h->h_moments.allocate(moments_packed(h->dim)));
+    HIP_TRY(h, h->d_chunks.allocate(moments_packed(h->dim) * ((h->ngroups + kReduceChunk - 1) / kReduceChunk)));
     HIP_TRY(h, hipMemset(h->d_x, 0, sizeof(double) * np * dp));
     HIP_TRY(h, hipMemset(h->d_forced, 0, sizeof(double) * np * dp));
     HIP_TRY(h, h->d_uniform.allocate(2 * dp + 8));
@@ -1236,7 +1169,7 @@ int smcmc_create(int dim, int nchains, int likelihood, uint64_t seed, uint32_t c
     HIP_TRY(h, hipMemset(h->d_like, 0, sizeof(double) * like_doubles));
     HIP_TRY(h, hipMemset(h->d_c0, 0, sizeof(double) * dp));
     HIP_TRY(h, hipMemset(h->d_gacc, 0, sizeof(double) * gacc_doubles(h)));
-    HIP_TRY(h, hipMemset(h->d_moments, 0, sizeof(double) * npacked(h)));
+    HIP_TRY(h, hipMemset(h->d_moments, 0, sizeof(double) * moments_packed(h->dim)));
     HIP_TRY(h, h->d_centre.allocate(dim));
     HIP_TRY(h, h->d_cov.allocate((size_t)dim * dim));
     HIP_TRY(h, h->d_decomp.allocate((size_t)dim * dim));
@@ -1541,11 +1474,10 @@ static int place_chains(smcmc_engine* h, const double* x0, int broadcast, std::v
     HIP_TRY(h, hipMemsetAsync(h->d_lane_i32, 0, sizeof(int32_t) * NP * SMCMC_LANE_I32_COUNT_, h->stream));
     HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * gacc_doubles(h), h->stream));
     if (h->panel_w && h->likelihood == SMCMC_LIKE_QUADFORM && !h->exact) {
-        PanelParams q;
-        std::memset(&q, 0, sizeof(q));
-        q.nchains = N; q.npad = h->npad; q.dim = D; q.init_only = 1;
-        q.like = h->d_like; q.x = h->d_x; q.lane_f64 = h->d_lane_f64; q.lane_i32 = h->d_lane_i32;
-        q.save_stride = 1;
+        // (init_only: the kernel reads the ensemble's shape, the likelihood and the point, and returns before its step loop)
+        PanelParams q = panel_params(h, make_params(h, 0, 0));
+        q.init_only = 1;
+        q.has_forced = 0;
         hipError_t e = launch_panel_mfma(q, h->likelihood, h->stream);
         if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("start kernel launch: ") + hipGetErrorString(e));
     } else if (h->panel_w || h->mode == SMCMC_MODE_PER_CHAIN) {
@@ -1559,23 +1491,59 @@ static int place_chains(smcmc_engine* h, const double* x0, int broadcast, std::v
                                  h->likelihood, h->exact, h->stream);
         if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("start kernel launch: ") + hipGetErrorString(e));
     } else {
-        StepParams p;
-        std::memset(&p, 0, sizeof(p));
-        p.nchains = N; p.npad = h->npad; p.dim = D; p.nsteps = 1; p.metropolis = 2;
-        p.seed = h->seed; p.chain_offset = h->chain_offset;
-        p.U = h->d_U; p.like = h->d_like; p.c0 = h->d_c0;
-        p.target = 0.234; p.acc_window = 1.0; p.asig = 1.0; p.max_up = 1.0; p.acc_w = -1.0;
-        p.step_rms_window = 0;
-        p.has_forced = 1; p.forced = h->d_forced;
-        p.x = h->d_x; p.lane_f64 = h->d_lane_f64; p.lane_i32 = h->d_lane_i32; p.gacc = h->d_gacc;
-        p.save_stride = 1;
-        p.scan_dim = -1;
+        // The ensemble's shape, seed and images as every launch gets them.  The rest is literal: the proposal is not
+        // initialised yet (InitializeState follows Start's likelihood call), so its settings are placeholders; the
+        // step is number 1 and forced whatever the engine's counters say; and what would pick another instantiation or
+        // another sum (uniform dimensions, a scan, the kept proposal, the sparse Error matrix, the section profile)
+        // stays off, as it always has been for this call.
+        StepParams p = make_params(h, 1, 2);
+        p.step0 = 0;
+        p.like_rowptr = nullptr; p.like_cols = nullptr; p.like_vals = nullptr; p.like_rows = nullptr;
+        p.target = 0.234; p.acc_window = 1.0; p.asig = 1.0; p.max_up = 1.0; p.acc_w = -1.0; p.acc_wW = 0.0;
+        p.per_lane_update = 0; p.step_rms_window = 0;
+        p.has_forced = 1;
+        p.proposed = nullptr; p.prof = nullptr;
+        p.uniform_mask = 0; p.uniform = nullptr;
+        p.scan_dim = -1; p.scan_uniform = 0; p.scan_a = 0.0; p.scan_b = 0.0;
         hipError_t e = dispatch_step(h->dp, p, h->likelihood, h->exact, false, false, h->stream);
         if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("start kernel launch: ") + hipGetErrorString(e));
     }
     logl.assign(NP, 0.0);
     HIP_TRY(h, hipMemcpyAsync(logl.data(), h->d_lane_f64 + (size_t)SMCMC_LANE_LOGL * NP, NP * sizeof(double),
                               hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SMCMC_OK;
+}
+
+// Every chain's scalar columns as Start (TSimpleMCMC.H:258-272) and Restore (:282-352, 1501-1612) leave them: the
+// likelihood at its point, the shared proposal's template values, and for Restore the saved counters of the tree entry
+// `s` (null at Start); everything else zero.  The moments start empty.  Synchronises the stream.
+static int write_chain_columns(smcmc_engine* h, const std::vector<double>& x, const std::vector<double>& logl,
+                               const smcmc_saved_state* s) {
+    const SharedProposal& P = *h->prop;
+    const int N = h->nchains;
+    const size_t NP = (size_t)h->npad;
+    std::vector<double> lf(NP * SMCMC_LANE_F64_COUNT_, 0.0);
+    std::vector<int32_t> li(NP * SMCMC_LANE_I32_COUNT_, 0);
+    for (int c = 0; c < N; ++c) {
+        lf[(size_t)SMCMC_LANE_LOGL * NP + c] = logl[c];
+        lf[(size_t)SMCMC_LANE_SIGMA * NP + c] = P.sigma;
+        lf[(size_t)SMCMC_LANE_ACCEPTANCE * NP + c] = P.acceptance;
+        lf[(size_t)SMCMC_LANE_ACCEPTANCE_TRIALS * NP + c] = P.acceptanceTrials;
+        lf[(size_t)SMCMC_LANE_RIGIDITY * NP + c] = P.rigidity;
+        lf[(size_t)SMCMC_LANE_LAST_VALUE * NP + c] = logl[c];
+        lf[(size_t)SMCMC_LANE_LAST_X0 * NP + c] = x[c];
+        lf[(size_t)SMCMC_LANE_LOGL_PROPOSED * NP + c] = logl[c];
+        li[(size_t)SMCMC_LANE_NEXT_UPDATE * NP + c] = P.nextUpdate;
+        if (!s) continue;
+        lf[(size_t)SMCMC_LANE_STEP_RMS * NP + c] = s->step_rms;
+        li[(size_t)SMCMC_LANE_TRIALS * NP + c] = s->trials;
+        li[(size_t)SMCMC_LANE_SUCCESSES * NP + c] = s->successes;
+        li[(size_t)SMCMC_LANE_CHAIN_STEPS * NP + c] = s->total_steps;
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->d_lane_f64, lf.data(), lf.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_lane_i32, li.data(), li.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * gacc_doubles(h), h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SMCMC_OK;
 }
@@ -1608,23 +1576,8 @@ int smcmc_start(smcmc_engine* h, const double* x0, int broadcast) {
     st = status_of(h, P.initialize(p0.data()));
     if (st) return st;
 
-    std::vector<double> lf(NP * SMCMC_LANE_F64_COUNT_, 0.0);
-    std::vector<int32_t> li(NP * SMCMC_LANE_I32_COUNT_, 0);
-    for (int c = 0; c < N; ++c) {
-        lf[(size_t)SMCMC_LANE_LOGL * NP + c] = logl[c];
-        lf[(size_t)SMCMC_LANE_SIGMA * NP + c] = P.sigma;
-        lf[(size_t)SMCMC_LANE_ACCEPTANCE * NP + c] = P.acceptance;
-        lf[(size_t)SMCMC_LANE_ACCEPTANCE_TRIALS * NP + c] = P.acceptanceTrials;
-        lf[(size_t)SMCMC_LANE_RIGIDITY * NP + c] = P.rigidity;
-        lf[(size_t)SMCMC_LANE_LAST_VALUE * NP + c] = logl[c];
-        lf[(size_t)SMCMC_LANE_LAST_X0 * NP + c] = x[c];
-        lf[(size_t)SMCMC_LANE_LOGL_PROPOSED * NP + c] = logl[c];
-        li[(size_t)SMCMC_LANE_NEXT_UPDATE * NP + c] = P.nextUpdate;
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->d_lane_f64, lf.data(), lf.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_lane_i32, li.data(), li.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * gacc_doubles(h), h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    st = write_chain_columns(h, x, logl, nullptr);
+    if (st) return st;
     st = upload_shared(h);
     if (st) return st;
     if (per_chain(h)) {
@@ -1677,27 +1630,8 @@ int smcmc_restore(smcmc_engine* h, const double* accepted, int broadcast, const 
     st = status_of(h, P.update(false));                                              // :1612
     if (st) return st;
 
-    std::vector<double> lf(NP * SMCMC_LANE_F64_COUNT_, 0.0);
-    std::vector<int32_t> li(NP * SMCMC_LANE_I32_COUNT_, 0);
-    for (int c = 0; c < N; ++c) {
-        lf[(size_t)SMCMC_LANE_LOGL * NP + c] = logl[c];
-        lf[(size_t)SMCMC_LANE_SIGMA * NP + c] = P.sigma;
-        lf[(size_t)SMCMC_LANE_ACCEPTANCE * NP + c] = P.acceptance;
-        lf[(size_t)SMCMC_LANE_ACCEPTANCE_TRIALS * NP + c] = P.acceptanceTrials;
-        lf[(size_t)SMCMC_LANE_RIGIDITY * NP + c] = P.rigidity;
-        lf[(size_t)SMCMC_LANE_LAST_VALUE * NP + c] = logl[c];
-        lf[(size_t)SMCMC_LANE_LAST_X0 * NP + c] = x[c];
-        lf[(size_t)SMCMC_LANE_STEP_RMS * NP + c] = s->step_rms;
-        lf[(size_t)SMCMC_LANE_LOGL_PROPOSED * NP + c] = logl[c];
-        li[(size_t)SMCMC_LANE_TRIALS * NP + c] = s->trials;
-        li[(size_t)SMCMC_LANE_SUCCESSES * NP + c] = s->successes;
-        li[(size_t)SMCMC_LANE_NEXT_UPDATE * NP + c] = P.nextUpdate;
-        li[(size_t)SMCMC_LANE_CHAIN_STEPS * NP + c] = s->total_steps;
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->d_lane_f64, lf.data(), lf.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_lane_i32, li.data(), li.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * gacc_doubles(h), h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    st = write_chain_columns(h, x, logl, s);
+    if (st) return st;
     h->total_steps = (uint32_t)s->total_steps;
     h->has_forced = false;
     st = upload_shared(h);
@@ -1800,15 +1734,14 @@ int smcmc_force_step(smcmc_engine* h, const double* point, int broadcast) {
     return SMCMC_OK;
 }
 
-int smcmc_moments_size(const smcmc_engine* h) { return h ? (int)npacked(h) : 0; }
+int smcmc_moments_size(const smcmc_engine* h) { return h ? (int)moments_packed(h->dim) : 0; }
 
 int smcmc_reduce_moments(smcmc_engine* h) {
     if (!h || !h->started) return SMCMC_ERR_INVALID;
     ON_DEVICE(h);
     if (h->panel_w) {
-        hipError_t e = launch_fold_reduce(h->d_gacc, h->dim, h->fold_nslices, h->d_moments, h->stream);
+        const hipError_t e = smcmc::fold_reduce_clear(h->fold, h->d_gacc, h->d_moments, h->stream);
         if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("fold reduce launch: ") + hipGetErrorString(e));
-        HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * gacc_doubles(h), h->stream));
         return SMCMC_OK;
     }
     // (the first level leaves zero in the accumulators it read: no memset of the 21 MB per window)
@@ -1820,21 +1753,21 @@ int smcmc_reduce_moments(smcmc_engine* h) {
 int smcmc_export_moments(smcmc_engine* h, double* dst) {
     if (!h || !dst) return SMCMC_ERR_INVALID;
     ON_DEVICE(h);
-    HIP_TRY(h, hipMemcpyAsync(dst, h->d_moments, npacked(h) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(dst, h->d_moments, moments_packed(h->dim) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return SMCMC_OK;
 }
 
 int smcmc_import_moments(smcmc_engine* h, const double* src) {
     if (!h || !src) return SMCMC_ERR_INVALID;
     ON_DEVICE(h);
-    HIP_TRY(h, hipMemcpyAsync(h->d_moments, src, npacked(h) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_moments, src, moments_packed(h->dim) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return SMCMC_OK;
 }
 
 int smcmc_read_moments(smcmc_engine* h, double* out) {
     if (!h || !out) return SMCMC_ERR_INVALID;
     ON_DEVICE(h);
-    HIP_TRY(h, hipMemcpyAsync(out, h->d_moments, npacked(h) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_moments, moments_packed(h->dim) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SMCMC_OK;
 }
@@ -1846,10 +1779,10 @@ int smcmc_apply_moments(smcmc_engine* h) {
     int st = sync_shared_to_host(h, true);
     if (st) return st;
     const double* M = h->h_moments;
-    HIP_TRY(h, hipMemcpyAsync(h->h_moments, h->d_moments, npacked(h) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->h_moments, h->d_moments, moments_packed(h->dim) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     SharedProposal& P = *h->prop;
-    if (!(M[npacked(h) - 1] > 0.0)) return SMCMC_OK;
+    if (!(M[moments_packed(h->dim) - 1] > 0.0)) return SMCMC_OK;
     P.absorbMoments(M, h->mode == SMCMC_MODE_POOLED);
     st = update_shared(h);
     if (st) return st;
@@ -1956,7 +1889,7 @@ int smcmc_allreduce_moments(smcmc_engine* h) {
     if (!h->comm) return fail(h, SMCMC_ERR_LOGIC, "no communicator: smcmc_comm_init first");
     ON_DEVICE(h);
     RcclApi& api = rccl_api();
-    const ncclResult_t r = api.AllReduce(h->d_moments, h->d_moments, npacked(h), ncclDouble, ncclSum, h->comm, h->stream);
+    const ncclResult_t r = api.AllReduce(h->d_moments, h->d_moments, moments_packed(h->dim), ncclDouble, ncclSum, h->comm, h->stream);
     if (r != ncclSuccess) return fail(h, SMCMC_ERR_RUNTIME, std::string("ncclAllReduce: ") + api.GetErrorString(r));
     return SMCMC_OK;
 }

@@ -1,5 +1,6 @@
 // smcmc_fold_inst.hip -- the large-dimension moment fold: instantiations of fold_ring_kernel (one per class of staging
-// rounds, with and without a chain mask), the plan of an engine, the ordered reduction of the moment groups.
+// rounds, with and without a chain mask), the plan of an ensemble, the ordered reduction of the moment groups, and the
+// host helpers both engines fold and reduce through.
 #include "smcmc_fold_ring.hip.h"
 
 namespace smcmc {
@@ -47,6 +48,7 @@ hipError_t fold_ring_prepare(FoldRing& fr, int D, int nchains, int npad, int nsl
     if (e != hipSuccess) return e;
     f.nwg = (int)plan.wg.size();
     f.rounds = plan.rounds;
+    f.D = D; f.nchains = nchains; f.npad = npad; f.nslices = nslices; f.slice_chains = slice_chains;
     fr = std::move(f);
     return hipSuccess;
 }
@@ -62,6 +64,24 @@ hipError_t launch_fold_ring(const FoldRing& fr, FoldRingParams p, hipStream_t st
 #undef SMCMC_FR_GO
         default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t fold_points(const FoldRing& fr, const double* const* pts, int n, const double* c0, const int32_t* mask,
+                       double* gacc, hipStream_t stream) {
+    if (n < 1 || n > kFoldMaxSrc) return hipErrorInvalidValue;
+    FoldRingParams fp;
+    std::memset(&fp, 0, sizeof(fp));
+    fp.nsrc = n;
+    for (int k = 0; k < n; ++k) fp.src[k] = pts[k];
+    fp.c0 = c0; fp.nchains = fr.nchains; fp.npad = fr.npad; fp.D = fr.D; fp.slice_chains = fr.slice_chains;
+    fp.gacc = gacc; fp.mask = mask;
+    return launch_fold_ring(fr, fp, stream);
+}
+
+hipError_t fold_reduce_clear(const FoldRing& fr, double* gacc, double* moments, hipStream_t stream) {
+    const hipError_t e = launch_fold_reduce(gacc, fr.D, fr.nslices, moments, stream);
+    if (e != hipSuccess) return e;
+    return hipMemsetAsync(gacc, 0, sizeof(double) * fold_gacc_doubles(fr.D), stream);
 }
 
 hipError_t launch_fold_reduce(const double* gacc, int D, int nslices, double* moments, hipStream_t s) {

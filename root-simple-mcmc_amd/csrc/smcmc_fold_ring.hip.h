@@ -475,16 +475,31 @@ static __global__ void __launch_bounds__(kFrWaves* kWave, 1) __attribute__((amdg
     static_assert(kFrMaxT == 8, "one case per tile count");
 }
 
-// Host side (smcmc_fold_inst.hip): the plan of an engine on its device, and the launch.
+// Host side (smcmc_fold_inst.hip): the plan of an ensemble on its device, and what both engines do with its accumulators.
 struct FoldRing {
     DeviceBuffer<FoldPlanEntry> d_plan;
     DeviceBuffer<uint16_t> d_order;
     int nwg = 0;                      // workgroups of a launch = plan entries (a multiple of 8)
     int rounds = 0;                   // the staging-round class of the plan (the kernel instantiation)
+    int D = 0, nchains = 0, npad = 0, nslices = 0, slice_chains = 0;   // the ensemble the plan was made for
 };
+// the packed moments of D dimensions: the lower triangle of sum y y^T, y = (x - c0, 1)
+inline size_t moments_packed(int D) { return (size_t)(D + 1) * (D + 2) / 2; }
+// doubles of the accumulators `gacc`: one 16 x 16 tile per (slice, tile of the lower triangle)
+inline size_t fold_gacc_doubles(int D) {
+    const size_t T = (size_t)(D + 1 + 15) / 16;
+    return (size_t)fold_slices(D) * (T * (T + 1) / 2) * 4 * kWave;
+}
 // fr is replaced only when the whole plan is on the device
 hipError_t fold_ring_prepare(FoldRing& fr, int D, int nchains, int npad, int nslices, int slice_chains);
 // p.plan is taken from fr; p.nsrc points in p.src are folded in order (1 <= nsrc <= kFoldMaxSrc)
 hipError_t launch_fold_ring(const FoldRing& fr, FoldRingParams p, hipStream_t stream);
+// Folds `n` points ([D][npad] each, in this order, 1 <= n <= kFoldMaxSrc) about c0 into the moment groups of fr's
+// ensemble: one launch, the accumulators in registers from the first point to the last.  mask: optional [npad], a chain
+// with mask 0 folds nothing.
+hipError_t fold_points(const FoldRing& fr, const double* const* pts, int n, const double* c0, const int32_t* mask,
+                       double* gacc, hipStream_t stream);
+// The moment groups summed (in group order) into the packed vector `moments`, and cleared for the next window.
+hipError_t fold_reduce_clear(const FoldRing& fr, double* gacc, double* moments, hipStream_t stream);
 
 }  // namespace smcmc

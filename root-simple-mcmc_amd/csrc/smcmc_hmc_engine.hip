@@ -80,12 +80,6 @@ struct smcmc_hmc {
 
 namespace {
 
-size_t hmc_npacked(const smcmc_hmc* h) { return (size_t)(h->dim + 1) * (h->dim + 2) / 2; }
-size_t hmc_gacc_doubles(const smcmc_hmc* h) {
-    const size_t T = (size_t)(h->dim + 1 + 15) / 16;
-    return (size_t)fold_slices(h->dim) * (T * (T + 1) / 2) * 4 * kWave;
-}
-
 // the chains retune themselves (TSimpleHMC.H:302-345, 833-847) unless both the step length and the count are fixed
 bool hmc_adaptive(const smcmc_hmc* h) { return h->mean_epsilon > 0.0 || h->leapfrog > 0; }
 // likelihoods without a gradient of their own (the reference's functors throw / return false, TAsymLogLikelihood.H:34-36,
@@ -259,11 +253,11 @@ int hmc_tracking_buffers(smcmc_hmc* h) {
     smcmc::FoldRing fold;
     HIP_TRY(h, p0.allocate(vec));
     HIP_TRY(h, qprev.allocate(vec));
-    HIP_TRY(h, gacc.allocate(hmc_gacc_doubles(h)));
+    HIP_TRY(h, gacc.allocate(fold_gacc_doubles(h->dim)));
     HIP_TRY(h, smcmc::fold_ring_prepare(fold, h->dim, h->nchains, h->npad, h->fold_nslices, h->slice_chains));
-    HIP_TRY(h, moments.allocate(hmc_npacked(h)));
+    HIP_TRY(h, moments.allocate(moments_packed(h->dim)));
     HIP_TRY(h, zero.allocate(h->dim));
-    HIP_TRY(h, hmoments.allocate(hmc_npacked(h)));
+    HIP_TRY(h, hmoments.allocate(moments_packed(h->dim)));
     HIP_TRY(h, avg.allocate(h->dim));
     HIP_TRY(h, exxt.allocate((size_t)h->dim * h->dim));
     HIP_TRY(h, hcov.allocate((size_t)h->dim * h->dim));
@@ -271,8 +265,8 @@ int hmc_tracking_buffers(smcmc_hmc* h) {
     HIP_TRY(h, hhscal.allocate(8));
     HIP_TRY(h, hipMemsetAsync(p0, 0, sizeof(double) * vec, h->stream));
     HIP_TRY(h, hipMemsetAsync(qprev, 0, sizeof(double) * vec, h->stream));
-    HIP_TRY(h, hipMemsetAsync(gacc, 0, sizeof(double) * hmc_gacc_doubles(h), h->stream));
-    HIP_TRY(h, hipMemsetAsync(moments, 0, sizeof(double) * hmc_npacked(h), h->stream));
+    HIP_TRY(h, hipMemsetAsync(gacc, 0, sizeof(double) * fold_gacc_doubles(h->dim), h->stream));
+    HIP_TRY(h, hipMemsetAsync(moments, 0, sizeof(double) * moments_packed(h->dim), h->stream));
     HIP_TRY(h, hipMemsetAsync(zero, 0, sizeof(double) * h->dim, h->stream));
     h->d_p0 = std::move(p0); h->d_qprev = std::move(qprev); h->d_gacc = std::move(gacc);
     h->fold = std::move(fold);
@@ -372,9 +366,8 @@ int hmc_reduce(smcmc_hmc* h) {
         return fail(h, SMCMC_ERR_LOGIC, "moments of an earlier smcmc_hmc_reduce_moments are waiting for smcmc_hmc_apply_moments");
     h->steps_reduced += h->steps_in_window;
     h->steps_in_window = 0;
-    hipError_t e = launch_fold_reduce(h->d_gacc, h->dim, h->fold_nslices, h->d_moments, h->stream);
+    const hipError_t e = smcmc::fold_reduce_clear(h->fold, h->d_gacc, h->d_moments, h->stream);
     if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("fold reduce launch: ") + hipGetErrorString(e));
-    HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * hmc_gacc_doubles(h), h->stream));
     return SMCMC_OK;
 }
 
@@ -850,7 +843,7 @@ int smcmc_hmc_start(smcmc_hmc* h, const double* x0, int broadcast) {
     h->host_stale = false;
     h->cov_dirty = true;
     h->steps_in_window = 0;
-    if (h->d_gacc) HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * hmc_gacc_doubles(h), h->stream));
+    if (h->d_gacc) HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * fold_gacc_doubles(h->dim), h->stream));
     h->started = true;
     return SMCMC_OK;
 }
@@ -905,14 +898,9 @@ int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
         if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
         h->step_count += 1u;
         // UpdateCovariance (:338): the point each chain stood on, if its proposal's potential was finite (:336)
-        {
-            smcmc::FoldRingParams fp;
-            std::memset(&fp, 0, sizeof(fp));
-            fp.src[0] = h->d_qprev; fp.nsrc = 1; fp.c0 = h->d_zero;
-            fp.nchains = h->nchains; fp.npad = h->npad; fp.D = h->dim; fp.slice_chains = h->slice_chains;
-            fp.gacc = h->d_gacc; fp.mask = h->d_lane_i32 + (size_t)kHmcLaneContributes * h->npad;
-            e = smcmc::launch_fold_ring(h->fold, fp, h->stream);
-        }
+        const double* qprev = h->d_qprev;
+        e = smcmc::fold_points(h->fold, &qprev, 1, h->d_zero, h->d_lane_i32 + (size_t)kHmcLaneContributes * h->npad, h->d_gacc,
+                               h->stream);
         if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("fold launch: ") + hipGetErrorString(e));
         if (++h->steps_in_window >= h->sync_every) {
             st = hmc_sync(h);
@@ -933,7 +921,7 @@ int smcmc_hmc_sync(smcmc_hmc* h) {
 }
 
 // The same in pieces, for an ensemble sharded over engines / ranks: reduce, export, (sum over ranks), import, apply.
-int smcmc_hmc_moments_size(const smcmc_hmc* h) { return h ? (int)(((size_t)h->dim + 1) * ((size_t)h->dim + 2) / 2) : 0; }
+int smcmc_hmc_moments_size(const smcmc_hmc* h) { return h ? (int)moments_packed(h->dim) : 0; }
 
 int smcmc_hmc_reduce_moments(smcmc_hmc* h) {
     if (!h) return SMCMC_ERR_INVALID;

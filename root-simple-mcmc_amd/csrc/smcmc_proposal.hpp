@@ -104,31 +104,50 @@ public:
         return update(true);
     }
 
-    // UpdateProposal :1009-1390.  `sigma`, `acceptanceTrials` here are the shared
-    // template values; the engine applies the same rescale / de-weighting per chain.
-    UpdateStatus update(bool fromReset) {
+    // The de-weighting UpdateProposal applies to a trial count, as the device reads it: w = 1 - min(deweight, 1) and
+    // w * window (:1056-1066, 1081-1086); w = -1 (and 0) when the de-weighting is off.
+    struct Deweight { double w, wW; };
+    static Deweight deweightOf(double deweight, double window) {
+        if (!(deweight > 0.0)) return {-1.0, 0.0};
+        const double w = 1.0 - std::min(deweight, 1.0);
+        return {w, w * window};
+    }
+    Deweight acceptanceDeweights() const { return deweightOf(acceptanceDeweight, acceptanceWindow); }
+    Deweight covDeweights() const { return deweightOf(covDeweight, covWindow); }
+
+    // The part of UpdateProposal that looks at no sample: the update is counted, the next one scheduled (:1050-1052),
+    // both de-weights clamped to 1 (:1057, 1082) and the acceptance trials de-weighted (:1081-1086).  With a trace that
+    // is not positive (:1025-1028) the update is counted and nothing else happens: false.
+    bool bookkeepUpdate(bool validTrace) {
         ++updateCount;
-        const double currentTrace = trace();
-        if (currentTrace <= 0) return UpdateStatus::InvalidTrace;
-        const double sigmaScale = std::sqrt(sigmaTrace / currentTrace);
-        sigma = sigma * sigmaScale;
-        sigmaTrace = currentTrace;
+        if (!validTrace) return false;
         const double maxUp = (double)D * (double)D;
         const double up = 0.5 * successes;
         nextUpdate = (int)(acceptanceWindow + maxUp - maxUp / (up + 1.0));
-        if (covDeweight > 0.0) {
-            if (covDeweight > 1.0) covDeweight = 1.0;
-            const double w = 1.0 - covDeweight;
-            covTrials = std::max(1.0, w * covTrials);
-            covTrials = std::min(covTrials, w * covWindow);
-            centreTrials = std::max(1.0, w * centreTrials);
-            centreTrials = std::min(centreTrials, w * covWindow);
-        }
+        if (covDeweight > 1.0) covDeweight = 1.0;
         if (acceptanceDeweight > 0.0) {
             if (acceptanceDeweight > 1.0) acceptanceDeweight = 1.0;
             const double w = 1.0 - acceptanceDeweight;
             acceptanceTrials = std::max(1.0, w * acceptanceTrials);
             acceptanceTrials = std::min(acceptanceTrials, w * acceptanceWindow);
+        }
+        return true;
+    }
+
+    // UpdateProposal :1009-1390.  `sigma`, `acceptanceTrials` here are the shared
+    // template values; the engine applies the same rescale / de-weighting per chain.
+    UpdateStatus update(bool fromReset) {
+        const double currentTrace = trace();
+        if (!bookkeepUpdate(!(currentTrace <= 0))) return UpdateStatus::InvalidTrace;
+        const double sigmaScale = std::sqrt(sigmaTrace / currentTrace);
+        sigma = sigma * sigmaScale;
+        sigmaTrace = currentTrace;
+        if (covDeweight > 0.0) {   // (the device does this part itself on the device path)
+            const double w = 1.0 - covDeweight;
+            covTrials = std::max(1.0, w * covTrials);
+            covTrials = std::min(covTrials, w * covWindow);
+            centreTrials = std::max(1.0, w * centreTrials);
+            centreTrials = std::min(centreTrials, w * covWindow);
         }
         const UpdateStatus st = decompose(fromReset);
         lastSigmaScale = sigmaScale;   // after the ladder: a reset on its last rung runs update() again

@@ -427,9 +427,9 @@ def test_overlapped_update_changes_nothing_without_a_fallback(gpu):
 @pytest.mark.parametrize("exact", [True, False])
 @pytest.mark.parametrize("dim,n,kind", [(100, 192, 0), (200, 128, 2), (500, 64, 1)])
 def test_pooled_every_step_through_the_ring(gpu, oracle, dim, n, kind, exact):
-    """Covariance fed every step at D > 63: launches of up to eight steps leave each step's point in a ring and the
+    """Covariance fed every step at D > 63: launches of up to sixteen steps leave each step's point in a ring and the
     folds follow in step order -- the same moments, bit for bit, as a fold between one-step launches (windows of 19 and
-    3 steps cut the launches at 8 + 8 + 3 and 3; a window of 1 takes the one-step path)."""
+    3 steps cut the launches at 16 + 3 and 3; a window of 1 takes the one-step path)."""
     if kind == 1 and exact:
         pytest.skip("the serial quadratic form at D = 500 is covered by test_gpu_parity (slow on the oracle)")
     e, o = _pair(gpu, oracle, dim, n, kind, gpu.MODE_POOLED, exact, rowwise=(kind == 1 and not exact), stride=1)

@@ -193,6 +193,21 @@ def test_hmc_quadratic_form_adaptive(gpu, oracle, dim, nchains, sync, exact):
     assert e.lane("naccept").sum() > 0
 
 
+def test_hmc_window_that_ends_between_two_syncs(gpu, oracle):
+    """D > 63, a sync every 3 steps, 4 steps and then sync(): the fourth step's fold is reduced on its own after the
+    accumulators were cleared behind the third (the explicit pooled update of a partial window at the end of a run)."""
+    dim, nchains = 64, 32
+    e, o = _adaptive_pair(gpu, oracle, dim, nchains, 0, None, True, 3)
+    x0 = np.ones(dim)
+    e.Start(x0); o.start(x0)
+    e.Step(4); o.step(4)
+    _same_hmc(e, o, "after 4 steps")
+    e.sync(); o.sync()
+    _same_hmc(e, o, "after the sync of the partial window")
+    e.Step(1); o.step(1)
+    _same_hmc(e, o, "the step after it")
+
+
 def test_hmc_fixed_step_can_track_the_covariance(gpu, oracle):
     dim, n = 8, 64
     e, o = _adaptive_pair(gpu, oracle, dim, n, 0, None, True, 1)

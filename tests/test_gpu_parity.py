@@ -627,6 +627,38 @@ def test_restore_round_trip_of_the_pooled_engine(gpu):
     assert np.isfinite(b.GetAcceptedLogLikelihood()).all()
 
 
+def test_restore_of_the_pooled_engine_above_63_dimensions(gpu):
+    """Restore at D > 63 (the large-dimension kernels), in the manner of the round trip above: three steps, the entry
+    of chain 5 saved, and a fresh engine restored from it with every chain's point stands where the engine that was
+    not interrupted stands; three more steps and a pooled update go through.  (The steps after a Restore are not those
+    of the uninterrupted engine: RestoreState starts every chain from the saved chain's scalars and from
+    fLastValue = the restored point, TSimpleMCMC.H:1501-1612.)"""
+    dim, n, ch = 64, 64, 5
+    a = gpu.Engine(dim, n)
+    a.Start(np.zeros(dim))
+    a.Step(3)
+    st = a.saved_state(chain=ch)
+    b = gpu.Engine(dim, n)
+    b.Start(np.zeros(dim))
+    b.Restore(st, accepted=a.GetAccepted())
+    assert np.array_equal(b.GetAccepted(), a.GetAccepted())
+    # the saved likelihood stands for every chain whose own is within 1E-4 of it (:336-345)
+    logl = a.GetAcceptedLogLikelihood()
+    logl = np.where(np.abs(logl - st["log_likelihood"]) > 1E-4, logl, st["log_likelihood"])
+    assert np.array_equal(b.GetAcceptedLogLikelihood(), logl)
+    assert np.array_equal(b.covariance, a.covariance) and np.array_equal(b.GetEstimatedCenter(), a.GetEstimatedCenter())
+    assert np.array_equal(b.decomposition, a.decomposition)
+    assert b.get_param("TOTAL_STEPS") == 3 and np.all(b.lane("chain_steps") == 3)
+    assert np.all(b.lane("trials") == st["trials"]) and np.all(b.lane("successes") == st["successes"])
+    assert np.all(b.lane("step_rms") == st["step_rms"]) and np.all(b.lane("acceptance") == st["acceptance"])
+    # the covariance has not changed since Start: the update Restore ends in rescales sigma by exactly 1
+    assert np.all(b.lane("sigma") == st["sigma"]) and b.get_param("SIGMA_TRACE") == a.get_param("SIGMA_TRACE")
+    assert np.array_equal(b.lane("last_value"), b.GetAcceptedLogLikelihood())
+    b.Step(3); b.sync()
+    assert b.get_param("TOTAL_STEPS") == 6 and np.all(b.lane("trials") == st["trials"] + 3)
+    assert np.isfinite(b.GetAcceptedLogLikelihood()).all() and np.isfinite(b.covariance).all()
+
+
 def test_restore_needs_start(gpu):
     e = gpu.Engine(4, 8)
     st = dict(accepted=np.zeros(4), log_likelihood=0.0, total_steps=10, step_rms=0.1, trials=10, successes=3,
