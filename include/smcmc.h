@@ -570,6 +570,37 @@ int smcmc_marginal_histograms(const double* trace_device, int nslots, int dim, i
 int smcmc_trace_moments(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
                         int nchains_padded, const double* centre, double* sum, double* sumsq, void* stream);
 
+/* ---- posterior reducer: split R-hat and multi-chain ESS of a saved trace --------
+ * The reducers above pool slots and chains into one sum, which is the reference's single chain.  An ensemble can also be
+ * asked whether its chains agree: the split potential scale reduction (Gelman-Rubin in the split form) and the
+ * effective sample size built on it (Geyer's truncation; BDA3 section 11.5, Vehtari et al. 2021).  The reference has
+ * no counterpart, so this definition IS the engine's.  Over trace_device[slot][dim_stride][nchains_padded] (as
+ * smcmc_step_save, smcmc_vaat_step_save or smcmc_hmc_copy_positions wrote it; padding lanes and rows >= dim are never
+ * read into a result) and about the reference point `centre` ([dim] host; NULL = the origin):
+ *   segments     every live chain c < nchains is cut into S = nsegments >= 1 segments of L = nslots / S slots (integer
+ *                division); segment s covers the slots [r + s L, r + (s + 1) L), r = nslots - S L; the r earliest slots
+ *                are not read.  S = 2 is split R-hat, S = 1 the plain form.  M = S * nchains segment-chains m = (s, c).
+ *   per m        y_t = x[t][d][c] - centre[d];  s1_m[d] = sum_t y_t, slots ascending;  mean_m = s1_m / L (one
+ *                division);  z_t = y_t - mean_m (the two subtractions in this order)
+ *   sum[d]           = sum_m s1_m[d]
+ *   sumsq_of_sums[d] = sum_m s1_m[d]^2
+ *   within[k][d]     = sum_m sum_{t = k}^{L - 1} z_t z_(t-k)        k = 0 .. SMCMC_AUTOCORR_LAGS - 1
+ *                lags never reach across a segment's first slot; rows k >= L are 0; within[0] is the within-chain sum
+ *                of squares.
+ * Host outputs and raw sums so that ranks can add theirs (the same L and centre are required).  From them, on the host:
+ * W = within[0] / (M (L - 1)), the variance of the segment means (sumsq_of_sums / L^2 - (sum / L)^2 / M) / (M - 1),
+ * var+ = (L - 1) / L W + that, R-hat = sqrt(var+ / W), rho_k = 1 - (W - within[k] / (M L)) / var+.
+ * chain_sums_device: optional device output [S][dim][nchains_padded] that receives s1 (lanes >= nchains get 0); it is
+ * the intermediate of the second pass, so the caller gets per-chain means without another reducer.  NULL: a scratch
+ * buffer of the call's own.
+ * Fixed summation order (smcmc_convergence.hip states it): the same bits on every run.
+ * SMCMC_ERR_INVALID, with nothing launched and nothing written: nsegments < 1, L < 2, dim < 1 or dim > smcmc_max_dim(),
+ * dim_stride < dim, nchains < 1, nchains_padded < nchains or not a multiple of 64, trace_device, sum, sumsq_of_sums or
+ * within NULL.  SMCMC_ERR_UNSUPPORTED, likewise: nsegments > 65535.  `stream` is a hipStream_t or NULL. */
+int smcmc_trace_convergence(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
+                            int nchains_padded, int nsegments, const double* centre, double* chain_sums_device,
+                            double* sum, double* sumsq_of_sums, double* within, void* stream);
+
 /* ---- the Gaussian stand-in chain of a mean and a covariance ---------------------
  * CholeskyChain.C:18-66: covariance = U^T U with U upper triangular (:39-46; here the row-ordered routine the adaptive
  * proposal uses, a pivot that is not positive and finite is SMCMC_ERR_RUNTIME and nothing is launched or written, where

@@ -58,6 +58,7 @@ def _units(user_flag=None, name="user"):
           else ("smcmc_perchain_wg_inst.hip", [], "perchain_wg"))
     units = [engine, ("smcmc_selftest.hip", [], "selftest"), ("smcmc_autocorr.hip", [], "autocorr"),
              ("smcmc_marginals.hip", [], "marginals"), ("smcmc_trace_moments.hip", [], "trace_moments"),
+             ("smcmc_convergence.hip", [], "convergence"),
              hmc, ("smcmc_hmc_mfma_inst.hip", [], "hmc_mfma"),
              vaat, ("smcmc_vaat_large.hip", [], "vaat_large"),
              ("smcmc_pooled_update.hip", [], "pooled_update"), ("smcmc_perchain_inst.hip", [], "perchain"),
@@ -159,7 +160,8 @@ def _compile(unit):
 # Translation units whose kernels hold a chain's state in registers for a whole launch: every kernel in them must use
 # no scratch (private segment), which the compiler's resource report (-Rpass-analysis=kernel-resource-usage) states
 # per kernel.  A unit that spills is refused, not built.
-NO_SCRATCH_SOURCES = ("smcmc_perchain_wg_inst.hip", "smcmc_marginals.hip", "smcmc_trace_moments.hip")
+NO_SCRATCH_SOURCES = ("smcmc_perchain_wg_inst.hip", "smcmc_marginals.hip", "smcmc_trace_moments.hip",
+                      "smcmc_convergence.hip")
 
 
 def _check_no_scratch(name, obj, remarks):

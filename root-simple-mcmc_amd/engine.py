@@ -285,6 +285,14 @@ class Engine:
         return _trace_moments(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim_padded, self.nchains,
                               self.nchains_padded, centre, stream)
 
+    def Convergence(self, trace_ptr, nslots, nsegments=2, centre=None, stream=0):
+        """The sums behind split R-hat and the multi-chain effective sample size of a trace StepSave wrote
+        (smcmc_trace_convergence), taken on the device: every chain cut into `nsegments` segments (2: split R-hat, 1: the
+        plain form), each about its own mean.  Pass a `centre` near the mean, e.g. TraceMoments(...).mean from one
+        earlier pass: the variance of the segment means cancels like any E[yy] - E[y]^2.  Returns a Convergence."""
+        return _convergence(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim_padded, self.nchains,
+                            self.nchains_padded, nsegments, centre, stream)
+
     def GetAccepted(self):
         x = np.zeros((self.dim, self.nchains))
         self._check(self._lib.smcmc_read_state(self._h, _ptr(x), None))
@@ -638,6 +646,112 @@ def _trace_moments(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, ncha
     return TraceMoments(total, sumsq, nslots, nchains, c)
 
 
+class Convergence:
+    """Split R-hat and the multi-chain effective sample size of a saved trace, from the raw sums of
+    smcmc_trace_convergence (include/smcmc.h has the definition): every chain is cut into segments of L slots, M
+    segment-chains in all, y = x - centre, s1_m the sum of segment-chain m and z = y - s1_m / L:
+      sum[d] = sum_m s1_m,  sumsq_of_sums[d] = sum_m s1_m^2,  within[k][d] = sum_m sum_{t >= k} z_t z_(t-k)
+      W             within[0] / (M (L - 1)): the mean within-chain variance
+      var_of_means  (sumsq_of_sums / L^2 - (sum / L)^2 / M) / (M - 1): the variance of the segment means (B / L)
+      var_plus      (L - 1) / L W + var_of_means
+      rhat()        sqrt(var_plus / W) (Gelman-Rubin; the split form when the segments are halves); NaN where W is 0 or
+                    M < 2
+      rho()         [lag][dim], 1 - (W - within[k] / (M L)) / var_plus for the lags below min(64, L)
+      tau()         Geyer's initial monotone sequence (BDA3 section 11.5, Vehtari et al. 2021): the pairs
+                    P_j = rho[2j] + rho[2j + 1] up to the first negative one, P_j = min(P_j, P_(j-1)), -1 + 2 sum P_j
+      ess()         M L / tau()
+      truncated()   per dimension: the pairs ran out at the last available lag before one turned negative (the
+                    autocorrelation outlives the 64 lags, or L): ess() is then an upper bound
+      mean()        centre + sum / (M L)
+    sumsq_of_sums / L^2 - (sum / L)^2 / M cancels like any E[yy] - E[y]^2: take the sums about a centre near the mean,
+    e.g. TraceMoments(...).mean from one earlier pass.  Sums of several ranks add (`+`) when L and the centre agree."""
+
+    def __init__(self, total, sumsq_of_sums, within, L, M, centre=None):
+        self.sum, self.sumsq_of_sums, self.within = _f64(total).copy(), _f64(sumsq_of_sums).copy(), _f64(within).copy()
+        self.L, self.M = int(L), int(M)
+        self.centre = np.zeros(self.sum.size) if centre is None else _f64(centre).copy()
+        if (self.sum.ndim != 1 or self.sumsq_of_sums.shape != self.sum.shape or self.centre.shape != self.sum.shape
+                or self.within.ndim != 2 or self.within.shape[1] != self.sum.size):
+            raise ValueError("sum[dim], sumsq_of_sums[dim], within[lag][dim] and centre[dim] do not fit together")
+
+    def __add__(self, other):
+        if self.L != other.L:
+            raise ValueError("segments of different lengths do not pool")
+        if not np.array_equal(self.centre, other.centre):
+            raise ValueError("sums about different centres do not add")
+        return Convergence(self.sum + other.sum, self.sumsq_of_sums + other.sumsq_of_sums, self.within + other.within,
+                           self.L, self.M + other.M, self.centre)
+
+    @property
+    def W(self):
+        return self.within[0] / (float(self.M) * (self.L - 1))
+
+    @property
+    def var_of_means(self):
+        if self.M < 2:
+            return np.full(self.sum.size, np.nan)
+        L, M = float(self.L), float(self.M)
+        return (self.sumsq_of_sums / (L * L) - (self.sum / L) ** 2 / M) / (M - 1.0)
+
+    @property
+    def var_plus(self):
+        return (self.L - 1.0) / self.L * self.W + self.var_of_means
+
+    def rhat(self):
+        W = self.W
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(W == 0.0, np.nan, np.sqrt(self.var_plus / W))
+
+    def rho(self):
+        """[lag][dim]"""
+        nlag = min(self.within.shape[0], self.L)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return 1.0 - (self.W[None, :] - self.within[:nlag] / (float(self.M) * self.L)) / self.var_plus[None, :]
+
+    def _geyer(self):
+        """(tau[dim], truncated[dim])"""
+        rho = self.rho()
+        npairs, dim = rho.shape[0] // 2, rho.shape[1]
+        tau, truncated = np.empty(dim), np.zeros(dim, dtype=bool)
+        for d in range(dim):
+            total, last, j = 0.0, np.inf, 0
+            while j < npairs:
+                pair = rho[2 * j, d] + rho[2 * j + 1, d]
+                if pair < 0.0:
+                    break
+                last = min(pair, last) if pair == pair else pair           # a NaN pair makes tau NaN
+                total += last
+                j += 1
+            tau[d], truncated[d] = -1.0 + 2.0 * total, j == npairs
+        return tau, truncated
+
+    def tau(self):
+        return self._geyer()[0]
+
+    def truncated(self):
+        return self._geyer()[1]
+
+    def ess(self):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return float(self.M) * self.L / self.tau()
+
+    def mean(self):
+        return self.centre + self.sum / (float(self.M) * self.L)
+
+
+def _convergence(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchains_padded, nsegments, centre, stream):
+    """The body of the engines' Convergence methods."""
+    c = None if centre is None else _f64(centre)
+    if c is not None and c.shape != (dim,):
+        raise ValueError("centre must be [dim]")
+    nslots, nsegments = int(nslots), int(nsegments)
+    total, sumsq, within = np.zeros(dim), np.zeros(dim), np.zeros((_capi.AUTOCORR_LAGS, dim))
+    check(lib.smcmc_trace_convergence(C.c_void_p(int(trace_ptr)), nslots, dim, dim_stride, nchains, nchains_padded,
+                                      nsegments, None if c is None else _ptr(c), None, _ptr(total), _ptr(sumsq),
+                                      _ptr(within), C.c_void_p(int(stream))))
+    return Convergence(total, sumsq, within, nslots // nsegments, nsegments * nchains, c)
+
+
 def cholesky_chain(mean, covariance, nslots, nchains, seed=20240607, chain_offset=0, dim_stride=None, stream=0):
     """The Gaussian stand-in chain of CholeskyChain.C:18-66, filled on the device: covariance = U^T U, every
     (slot, chain) one draw mean + sum_i r_i U(i, :) on the random stream (seed, chain_offset + chain, slot).  Returns
@@ -929,6 +1043,11 @@ class HmcEngine:
         return _trace_moments(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains,
                               self.nchains_padded, centre, stream)
 
+    def Convergence(self, trace_ptr, nslots, nsegments=2, centre=None, stream=0):
+        """As Engine.Convergence, over a trace of copy_positions slots ([slot][dim][nchains_padded])."""
+        return _convergence(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains,
+                            self.nchains_padded, nsegments, centre, stream)
+
     def lane(self, name):
         if name in _capi.HMC_LANE_F64:
             out = np.zeros(self.nchains)
@@ -1040,6 +1159,11 @@ class VaatEngine:
         """As Engine.TraceMoments, over a trace step_save wrote ([slot][dim][nchains_padded])."""
         return _trace_moments(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains,
                               self.nchains_padded, centre, stream)
+
+    def Convergence(self, trace_ptr, nslots, nsegments=2, centre=None, stream=0):
+        """As Engine.Convergence, over a trace step_save wrote ([slot][dim][nchains_padded])."""
+        return _convergence(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains,
+                            self.nchains_padded, nsegments, centre, stream)
 
     @property
     def total_steps(self): return self._lib.smcmc_vaat_total_steps(self._h)
