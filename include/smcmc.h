@@ -517,6 +517,37 @@ int smcmc_selftest_hmc_error_matrix(int device, int dim, double est_trace, const
 int smcmc_autocorrelation_sums(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
                                int nchains_padded, const double* centre, double* sum, double* lagged, void* stream);
 
+/* ---- posterior reducer: autocorrelation of a saved trace on a lag grid ---------
+ * MakeAutocorrelation.C looks far back along the chain: it evaluates the lags 1, 1 + lagStep, 1 + 2 lagStep, ... < maxLag
+ * with maxLag = min(entries - sqrt(entries), 30000) and lagStep = max(1, int(0.5 maxLag / bins)) (:70-73, 98-99, 117),
+ * over the last `trials` entries (:105-108), fills them into `bins` bins (:121-122) and turns every bin into
+ * a = (v/e - mean^2) / err^2 (:127-147).  This takes the sums of such a grid on the device; trace layout, `centre`,
+ * padding rules and `stream` exactly as smcmc_autocorrelation_sums.  With y = x[t][d][c] - centre[d] and
+ * k_i = lag_first + i lag_step:
+ *   sum[d]       = sum_{t, c} y_t
+ *   sumsq[d]     = sum_{t, c} y_t^2                       (lag 0: the variance's sum, whatever the grid)
+ *   lagged[i][d] = sum_{t >= k_i, c} y_t y_(t - k_i)      i = 0 .. nlags - 1
+ * Host outputs and raw sums so that ranks can add theirs.  Row i has max(nslots - k_i, 0) * nchains terms; a row with
+ * k_i >= nslots is exactly +0.0.  Fixed summation order (smcmc_autocorr_grid.hip states it): the same bits on every
+ * run; on a finite trace the bits of a row depend on (k_i, lag_step, trace, centre) only, not on lag_first or nlags
+ * (a pass skips the leading products with 0 that another computes, which differ for an Inf or a NaN), so a grid split over
+ * several calls gives the same rows; with lag_step = 1 every row with k < SMCMC_AUTOCORR_LAGS and `sum` have the bits
+ * smcmc_autocorrelation_sums returns on the same finite trace and centre.
+ * The bin of a lag is the fixed-width axis rule stated below for the marginals, 0-based and without the under- and
+ * overflow counters: bin = (int)(bins * (lag + 0.5) / maxLag).  A bin no lag falls into is 0/0 = NaN, as in the macro.
+ * Deviations from the macro, on purpose:
+ *   - its ring buffer holds floats (:63): every value is rounded to single precision before it is multiplied; the
+ *     trace here holds doubles and the products are taken in double;
+ *   - its TH1F sums are floats (:88-93) and stop counting at 2^24; the sums and counts here are doubles;
+ *   - it reads one chain; here the chains of an ensemble are pooled into one sum, so one chain is the macro.
+ * SMCMC_ERR_INVALID, with nothing launched and nothing written: the argument errors of smcmc_autocorrelation_sums,
+ * lag_first < 0, lag_step < 1, nlags < 1, nlags > SMCMC_AUTOCORR_GRID_MAX_LAGS, lag_first + (nlags - 1) lag_step
+ * beyond int, sum, sumsq or lagged NULL.  SMCMC_ERR_NO_DEVICE without a GPU. */
+#define SMCMC_AUTOCORR_GRID_MAX_LAGS 512   /* the macro never asks for more than 398 (entries = 420: maxLag = 399, lagStep = 1) */
+int smcmc_autocorrelation_grid_sums(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
+                                    int nchains_padded, const double* centre, int lag_first, int lag_step, int nlags,
+                                    double* sum, double* sumsq, double* lagged, void* stream);
+
 /* ---- posterior reducer: marginal and pair histograms of a saved trace ----------
  * TestMarginalization.C says WHAT is histogrammed, in three passes over the entries (here: every slot of every live
  * chain of trace_device[slot][dim_stride][nchains_padded], as smcmc_step_save, smcmc_vaat_step_save or

@@ -184,6 +184,8 @@ SIGNATURES = {
     "smcmc_selftest_hmc_error_matrix": (C.c_int, [C.c_int, C.c_int, C.c_double, _dp, _dp]),
     "smcmc_autocorrelation_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
                                              C.c_void_p]),
+    "smcmc_autocorrelation_grid_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int,
+                                                  C.c_int, C.c_int, _dp, _dp, _dp, C.c_void_p]),
     "smcmc_trace_ranges": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_void_p]),
     "smcmc_marginal_histograms": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_int, _dp, _dp, _up, C.c_int, _ip, C.c_int, _dp, _dp, _up, C.c_void_p]),
@@ -194,6 +196,7 @@ SIGNATURES = {
                                        C.c_void_p, _dp, C.c_void_p]),
 }
 AUTOCORR_LAGS = 64
+AUTOCORR_GRID_MAX_LAGS = 512   # SMCMC_AUTOCORR_GRID_MAX_LAGS of include/smcmc.h
 MARGINAL_MAX_BINS1, MARGINAL_MAX_BINS2, MARGINAL_MAX_PAIR_DIMS = 1000, 126, 32   # SMCMC_MARGINAL_MAX_* of include/smcmc.h
 COMM_ID_BYTES = 128
 

@@ -57,6 +57,7 @@ def _units(user_flag=None, name="user"):
     wg = (("smcmc_perchain_wg_inst.hip", [user_flag], "perchain_wg" + tag) if user_flag
           else ("smcmc_perchain_wg_inst.hip", [], "perchain_wg"))
     units = [engine, ("smcmc_selftest.hip", [], "selftest"), ("smcmc_autocorr.hip", [], "autocorr"),
+             ("smcmc_autocorr_grid.hip", [], "autocorr_grid"),
              ("smcmc_marginals.hip", [], "marginals"), ("smcmc_trace_moments.hip", [], "trace_moments"),
              ("smcmc_convergence.hip", [], "convergence"),
              hmc, ("smcmc_hmc_mfma_inst.hip", [], "hmc_mfma"),
@@ -161,7 +162,7 @@ def _compile(unit):
 # no scratch (private segment), which the compiler's resource report (-Rpass-analysis=kernel-resource-usage) states
 # per kernel.  A unit that spills is refused, not built.
 NO_SCRATCH_SOURCES = ("smcmc_perchain_wg_inst.hip", "smcmc_marginals.hip", "smcmc_trace_moments.hip",
-                      "smcmc_convergence.hip")
+                      "smcmc_convergence.hip", "smcmc_autocorr_grid.hip")
 
 
 def _check_no_scratch(name, obj, remarks):

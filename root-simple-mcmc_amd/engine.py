@@ -269,6 +269,22 @@ class Engine:
                                                          _ptr(s), _ptr(lagged), C.c_void_p(int(stream))))
         return Autocorrelation(s, lagged, int(nslots), self.nchains)
 
+    def AutocorrelationGrid(self, trace_ptr, nslots, lag_first=1, lag_step=1, nlags=64, centre=None, stream=0):
+        """The pooled sums of a trace StepSave wrote on the lags lag_first + i lag_step, i < nlags, taken on the device
+        (smcmc_autocorrelation_grid_sums): as far back along the chain as the caller asks, where AutocorrelationSums
+        stops at lag 63.  More than 512 lags are taken in several calls.  Returns an AutocorrelationGrid."""
+        return _autocorrelation_grid(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim_padded, self.nchains,
+                                     self.nchains_padded, lag_first, lag_step, nlags, centre, stream)
+
+    def MakeAutocorrelation(self, trace_ptr, nslots, stream=0, centre=None, plan=None):
+        """MakeAutocorrelation.C over a trace StepSave wrote: the macro's plan for entries = nslots
+        (autocorrelation_plan), the device sums over the last `trials` slots on its lag grid, its bins.  centre: the
+        reference point of the sums (default: the origin, as the macro has it).  plan: another AutocorrelationPlan for
+        entries = nslots, e.g. autocorrelation_plan(nslots, depth, bins, precision) with constants of the caller's own.
+        Returns a MacroAutocorrelation."""
+        return _make_autocorrelation(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim_padded, self.nchains,
+                                     self.nchains_padded, centre, stream, plan)
+
     def Marginals(self, trace_ptr, nslots, n1=100, n2=50, pair_dims=None, sample_stride=None, ranges=None, stream=0):
         """The histograms of TestMarginalization.C over a trace StepSave wrote, counted on the device: the ranges of the
         dimensions over every sample_stride-th slot (default: the macro's stride; skipped when `ranges` = (lo, hi) is
@@ -433,6 +449,190 @@ class Autocorrelation:
                     break
                 out[d] += 2.0 * pair
         return out
+
+
+class AutocorrelationGrid:
+    """The pooled sums of smcmc_autocorrelation_grid_sums (include/smcmc.h) on the lags `lags` = lag_first + i lag_step:
+    sum[dim], sumsq[dim] (lag 0) and lagged[lag][dim] about one reference point.
+      counts   terms per lag, max(nslots - lag, 0) * nchains
+      rho()    [lag][dim], (lagged / counts - mean^2) / (sumsq / n - mean^2); NaN for a lag beyond the trace
+    Sums of several ranks add (`+`) when the grid and nslots agree."""
+
+    def __init__(self, lags, total, sumsq, lagged, nslots, nchains):
+        self.lags = np.array(lags, dtype=np.int64)
+        self.sum, self.sumsq, self.lagged = _f64(total).copy(), _f64(sumsq).copy(), _f64(lagged).copy()
+        self.nslots, self.nchains = int(nslots), int(nchains)
+        if (self.lags.ndim != 1 or self.sum.ndim != 1 or self.sumsq.shape != self.sum.shape
+                or self.lagged.shape != (self.lags.size, self.sum.size)):
+            raise ValueError("lags[lag], sum[dim], sumsq[dim] and lagged[lag][dim] do not fit together")
+
+    @property
+    def counts(self):
+        return np.maximum(self.nslots - self.lags, 0) * float(self.nchains)
+
+    def __add__(self, other):
+        if self.nslots != other.nslots:
+            raise ValueError("traces of different lengths do not pool")
+        if not np.array_equal(self.lags, other.lags):
+            raise ValueError("sums on different lag grids do not add")
+        return AutocorrelationGrid(self.lags, self.sum + other.sum, self.sumsq + other.sumsq, self.lagged + other.lagged,
+                                   self.nslots, self.nchains + other.nchains)
+
+    def rho(self):
+        """[lag][dim]"""
+        n = float(self.nslots) * self.nchains
+        mean = self.sum / n
+        var = self.sumsq / n - mean * mean
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (self.lagged / self.counts[:, None] - mean * mean) / var
+
+
+def _autocorrelation_grid(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchains_padded, lag_first, lag_step,
+                          nlags, centre, stream):
+    """The body of the engines' AutocorrelationGrid methods: calls of at most AUTOCORR_GRID_MAX_LAGS lags each, the rows
+    concatenated (a row's bits do not depend on the call it is taken in)."""
+    c = None if centre is None else _f64(centre)
+    if c is not None and c.shape != (dim,):
+        raise ValueError("centre must be [dim]")
+    nslots, lag_first, lag_step, nlags = int(nslots), int(lag_first), int(lag_step), int(nlags)
+    if nlags < 1:
+        raise ValueError("nlags must be at least 1")
+    total, sumsq, lagged = np.zeros(dim), np.zeros(dim), np.zeros((nlags, dim))
+    for i0 in range(0, nlags, _capi.AUTOCORR_GRID_MAX_LAGS):
+        n = min(_capi.AUTOCORR_GRID_MAX_LAGS, nlags - i0)
+        rows = np.zeros((n, dim))
+        check(lib.smcmc_autocorrelation_grid_sums(C.c_void_p(int(trace_ptr)), nslots, dim, dim_stride, nchains,
+                                                  nchains_padded, None if c is None else _ptr(c),
+                                                  lag_first + i0 * lag_step, lag_step, n, _ptr(total), _ptr(sumsq),
+                                                  _ptr(rows), C.c_void_p(int(stream))))
+        lagged[i0:i0 + n] = rows
+    return AutocorrelationGrid(lag_first + lag_step * np.arange(nlags), total, sumsq, lagged, nslots, nchains)
+
+
+class AutocorrelationPlan:
+    """The constants MakeAutocorrelation.C derives from the number of entries (autocorrelation_plan): entries, depth,
+    max_lag, bins, lag_step, trials, lags[lag], lag_bins[lag] (0-based bin of each lag) and bin_centres[bin]."""
+
+    def __init__(self, entries, depth, max_lag, bins, lag_step, trials):
+        self.entries, self.depth, self.max_lag, self.bins = entries, depth, max_lag, bins
+        self.lag_step, self.trials = lag_step, trials
+        self.lags = np.arange(1, max_lag, lag_step, dtype=np.int64)
+        # the fixed-width axis of include/smcmc.h over [0, max_lag), filled at lag + 0.5 (:121)
+        self.lag_bins = np.array([int(bins * (lag + 0.5) / max_lag) for lag in self.lags], dtype=np.int64)
+        self.bin_centres = (np.arange(bins) + 0.5) * (float(max_lag) / bins)
+
+    def __eq__(self, other):
+        return (isinstance(other, AutocorrelationPlan)
+                and (self.entries, self.depth, self.max_lag, self.bins, self.lag_step, self.trials)
+                == (other.entries, other.depth, other.max_lag, other.bins, other.lag_step, other.trials))
+
+
+def autocorrelation_plan(entries, depth=30000, bins=100, precision=0.01):
+    """MakeAutocorrelation.C's constants for a tree of `entries` entries (:62, 70-73, 98-99, 104-106):
+      maxLag  = min(int(entries - sqrt(entries)), depth)        bins    = min(bins, maxLag)
+      lagStep = max(1, int(0.5 maxLag / bins))                  trials  = min(int(maxLag + 1 / precision^3), entries)
+      lags 1, 1 + lagStep, ... < maxLag, each in bin int(bins (lag + 0.5) / maxLag).
+    A pure function; returns an AutocorrelationPlan."""
+    entries = int(entries)
+    max_lag = min(int(entries - np.sqrt(float(entries))), int(depth)) if entries > 0 else 0
+    if max_lag < 2:
+        raise ValueError("the macro evaluates no lag below 4 entries")
+    bins = min(int(bins), max_lag)
+    lag_step = max(1, int(0.5 * max_lag / bins))
+    trials = min(int(max_lag + 1.0 / (precision * precision * precision)), entries)
+    return AutocorrelationPlan(entries, int(depth), max_lag, bins, lag_step, trials)
+
+
+class MacroAutocorrelation:
+    """What MakeAutocorrelation.C writes, from pooled device sums over the last plan.trials slots on the macro's lag
+    grid (the engines' MakeAutocorrelation; from_sums is pure).  With n = trials * nchains and y = x - centre:
+      bin_centres      [bin], the centres of the bins over [0, maxLag)
+      mean[d]          centre + sum / n                                          (meanValues, :132)
+      err2[d]          sumsq / n - (sum / n)^2: the "s" error of meanValues, squared (:133)
+      autocorr[d][bin] (v / e - (sum / n)^2) / err2, v and e the sums of `lagged` and of `counts` over the lags that
+                       fall into the bin (:135-139); a bin no lag falls into is 0/0 = NaN, as in the macro
+      average[bin], spread[bin]   mean and population r.m.s. of autocorr over the dimensions (avgCorr, option "S", :146)
+    Sums of several ranks add (`+`) when the plan and the centre agree.
+    Deviations from the macro, on purpose (include/smcmc.h states them): its ring buffer holds floats, so every value is
+    rounded to single precision before it is multiplied, and the values here are doubles; its TH1F sums are floats, and
+    these are doubles; it reads one chain, and here the chains are pooled into one sum, so one chain is the macro.  The
+    macro's reference point is the origin (centre = None); another centre changes autocorr only through the edges of
+    the lagged sums, O(lag / trials)."""
+
+    def __init__(self, plan, total, sumsq, lagged, nchains, centre=None):
+        self.plan, self.nchains = plan, int(nchains)
+        self.sum, self.sumsq, self.lagged = _f64(total).copy(), _f64(sumsq).copy(), _f64(lagged).copy()
+        self.centre = np.zeros(self.sum.size) if centre is None else _f64(centre).copy()
+        if (self.sum.ndim != 1 or self.sumsq.shape != self.sum.shape or self.centre.shape != self.sum.shape
+                or self.lagged.shape != (plan.lags.size, self.sum.size)):
+            raise ValueError("sum[dim], sumsq[dim], centre[dim] and lagged[lag][dim] do not fit the plan")
+
+    @classmethod
+    def from_sums(cls, plan, total, sumsq, lagged, nchains, centre=None):
+        return cls(plan, total, sumsq, lagged, nchains, centre)
+
+    def __add__(self, other):
+        if self.plan != other.plan:
+            raise ValueError("sums of different plans do not add")
+        if not np.array_equal(self.centre, other.centre):
+            raise ValueError("sums about different centres do not add")
+        return MacroAutocorrelation(self.plan, self.sum + other.sum, self.sumsq + other.sumsq, self.lagged + other.lagged,
+                                    self.nchains + other.nchains, self.centre)
+
+    @property
+    def counts(self):
+        """[lag]: the macro's fills per lag (`fills <= lag` breaks, :118), times the chains"""
+        return (self.plan.trials - self.plan.lags) * float(self.nchains)
+
+    @property
+    def bin_centres(self):
+        return self.plan.bin_centres
+
+    @property
+    def _ymean(self):
+        return self.sum / (float(self.plan.trials) * self.nchains)
+
+    @property
+    def mean(self):
+        return self.centre + self._ymean
+
+    @property
+    def err2(self):
+        m = self._ymean
+        return self.sumsq / (float(self.plan.trials) * self.nchains) - m * m
+
+    @property
+    def autocorr(self):
+        """[dim][bin]"""
+        dim, bins = self.sum.size, self.plan.bins
+        v, e = np.zeros((dim, bins)), np.zeros(bins)
+        counts = self.counts
+        for i, b in enumerate(self.plan.lag_bins):      # lags ascending, as the macro fills them
+            v[:, b] += self.lagged[i]
+            e[b] += counts[i]
+        m = self._ymean
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (v / e[None, :] - (m * m)[:, None]) / self.err2[:, None]
+
+    @property
+    def average(self):
+        return self.autocorr.mean(axis=0)
+
+    @property
+    def spread(self):
+        return self.autocorr.std(axis=0)
+
+
+def _make_autocorrelation(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchains_padded, centre, stream, plan):
+    """The body of the engines' MakeAutocorrelation methods."""
+    if plan is None:
+        plan = autocorrelation_plan(int(nslots))
+    elif plan.entries != int(nslots):
+        raise ValueError("the plan is for %d entries, the trace has %d slots" % (plan.entries, int(nslots)))
+    first = int(trace_ptr) + 8 * (plan.entries - plan.trials) * dim_stride * nchains_padded   # the last `trials` slots
+    g = _autocorrelation_grid(lib, check, first, plan.trials, dim, dim_stride, nchains, nchains_padded, 1, plan.lag_step,
+                              plan.lags.size, centre, stream)
+    return MacroAutocorrelation.from_sums(plan, g.sum, g.sumsq, g.lagged, nchains, centre)
 
 
 class Marginals:
@@ -1033,6 +1233,16 @@ class HmcEngine:
                                                          C.c_void_p(int(stream))))
         return Autocorrelation(s, lagged, int(nslots), self.nchains)
 
+    def AutocorrelationGrid(self, trace_ptr, nslots, lag_first=1, lag_step=1, nlags=64, centre=None, stream=0):
+        """As Engine.AutocorrelationGrid, over a trace of copy_positions slots ([slot][dim][nchains_padded])."""
+        return _autocorrelation_grid(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains,
+                                     self.nchains_padded, lag_first, lag_step, nlags, centre, stream)
+
+    def MakeAutocorrelation(self, trace_ptr, nslots, stream=0, centre=None, plan=None):
+        """As Engine.MakeAutocorrelation, over a trace of copy_positions slots ([slot][dim][nchains_padded])."""
+        return _make_autocorrelation(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains,
+                                     self.nchains_padded, centre, stream, plan)
+
     def Marginals(self, trace_ptr, nslots, n1=100, n2=50, pair_dims=None, sample_stride=None, ranges=None, stream=0):
         """As Engine.Marginals, over a trace of copy_positions slots ([slot][dim][nchains_padded])."""
         return _marginals(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains, self.nchains_padded,
@@ -1149,6 +1359,16 @@ class VaatEngine:
     def step_save(self, nsteps, stride, save_x_ptr, save_logl_ptr=None):
         self._check(self._lib.smcmc_vaat_step_save(self._h, int(nsteps), int(stride), C.c_void_p(int(save_x_ptr)),
                                                    C.c_void_p(int(save_logl_ptr)) if save_logl_ptr else None))
+
+    def AutocorrelationGrid(self, trace_ptr, nslots, lag_first=1, lag_step=1, nlags=64, centre=None, stream=0):
+        """As Engine.AutocorrelationGrid, over a trace step_save wrote ([slot][dim][nchains_padded])."""
+        return _autocorrelation_grid(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains,
+                                     self.nchains_padded, lag_first, lag_step, nlags, centre, stream)
+
+    def MakeAutocorrelation(self, trace_ptr, nslots, stream=0, centre=None, plan=None):
+        """As Engine.MakeAutocorrelation, over a trace step_save wrote ([slot][dim][nchains_padded])."""
+        return _make_autocorrelation(self._lib, self._check, trace_ptr, nslots, self.dim, self.dim, self.nchains,
+                                     self.nchains_padded, centre, stream, plan)
 
     def Marginals(self, trace_ptr, nslots, n1=100, n2=50, pair_dims=None, sample_stride=None, ranges=None, stream=0):
         """As Engine.Marginals, over a trace step_save wrote ([slot][dim][nchains_padded])."""
