@@ -418,6 +418,21 @@ int smcmc_hmc_read_state(smcmc_hmc* h, double* q, double* momentum, double* logl
 /* fAccepted of every chain into a DEVICE buffer [dim][smcmc_hmc_nchains_padded] (one slot of a trace for
  * smcmc_autocorrelation_sums), on the engine's stream: what SimpleHMC.C:51-66 fills its tree with, without the trip to the host. */
 int smcmc_hmc_copy_positions(smcmc_hmc* h, double* dst_device);
+/* smcmc_hmc_step(h, nsteps) that leaves its trace on the device: the same chain bit for bit (state, lanes, tuning and
+ * draws, in every mode and gradient type), and after every `stride`-th step of the call fAccepted of every live chain
+ * goes into save_x[slot][dim][smcmc_hmc_nchains_padded] (the layout smcmc_hmc_copy_positions fills and the posterior
+ * reducers read) and SMCMC_LANE_LOGL into save_logl[slot][smcmc_hmc_nchains_padded] (may be NULL), both caller-owned
+ * DEVICE buffers.  SMCMC_LANE_LOGL is -fAcceptedPotential, the log-likelihood for the likelihoods here; the reference's
+ * `LogLikelihood` branch of the HMC tree (TSimpleHMC.H:140) holds the potential itself, the other sign.
+ * slots = nsteps / stride, counted from the start of each call; steps past the last slot still run.  Lanes >= nchains
+ * and anything beyond slot slots - 1 are never written.  The stores sit in the step kernels beside the commit of
+ * fAccepted, in instantiations of their own (smcmc_hmc_step runs the code it ran before): with a fixed step length and
+ * leapfrog count (nothing tracked) the call is still one launch; the tuned modes keep their one step per launch.
+ * (Gradient types 2 / 3 / 5 and the two- and four-tile matrix kernels of the quadratic form, 128 < dim <= 512, are
+ * served by cutting the launch at the save steps and copying the slot on the device: the same bits.)  Work goes on the
+ * engine's stream; nothing waits on the host where smcmc_hmc_step does not.  SMCMC_ERR_INVALID, with nothing launched
+ * and nothing written: NULL handle, not started, save_x_device NULL, stride < 1, nsteps < 0. */
+int smcmc_hmc_step_save(smcmc_hmc* h, int nsteps, int stride, double* save_x_device, double* save_logl_device);
 int smcmc_hmc_nchains_padded(const smcmc_hmc* h);
 int smcmc_hmc_read_lane_f64(smcmc_hmc* h, int field, double* out);
 int smcmc_hmc_read_lane_i32(smcmc_hmc* h, int field, int32_t* out);
@@ -437,6 +452,39 @@ int smcmc_hmc_get_mode(const smcmc_hmc* h);
 /* chain `chain`'s fAveragePoint [dim], fEstimatedCovariance [dim*dim] and tuning[10] in the layout of
  * smcmc_hmc_get_tuning; any pointer may be NULL.  In SMCMC_MODE_POOLED the shared values. */
 int smcmc_hmc_read_chain_tuning(smcmc_hmc* h, int chain, double* average, double* covariance, double* tuning);
+/* nsteps x Step(false) of the whole ensemble in SMCMC_MODE_PER_CHAIN (any tuning, any gradient type the mode serves)
+ * with a per-step record of one chain in the HOST array records[step * smcmc_hmc_record_stride()]: [0, dim) fAccepted,
+ * [dim, 2 dim) fAveragePoint, then the scalars of smcmc_hmc_record_field.  A row is the chain after that step and after
+ * the UpdateCovariance / UpdateErrorMatrix that follows it: what smcmc_hmc_read_state, the lanes and
+ * smcmc_hmc_read_chain_tuning(h, chain, ...) would return at that moment, i.e. what the branches of TSimpleHMC.H:139-147
+ * hold.  POTENTIAL / PROPOSED_POTENTIAL are fAcceptedPotential / fProposedPotential (minus SMCMC_LANE_LOGL /
+ * SMCMC_LANE_LOGL_PROPOSED), LEAPFROG is signed as fLeapFrogSteps is, TUNING0 + k is field k of smcmc_hmc_get_tuning.
+ * Nothing waits on the host between the steps: a gather kernel after each step's update fills a device row, one copy to
+ * the host ends the call.  SMCMC_ERR_UNSUPPORTED outside SMCMC_MODE_PER_CHAIN (the pooled update decides on the host);
+ * SMCMC_ERR_INVALID: chain out of range, records NULL, not started. */
+typedef enum {
+    SMCMC_HMC_REC_POTENTIAL = 0, SMCMC_HMC_REC_PROPOSED_POTENTIAL, SMCMC_HMC_REC_ACCEPTANCE, SMCMC_HMC_REC_LAST_ACCEPT,
+    SMCMC_HMC_REC_MEAN_EPSILON, SMCMC_HMC_REC_LEAPFROG, SMCMC_HMC_REC_REVERSAL_LEN, SMCMC_HMC_REC_STEP_COUNT,
+    SMCMC_HMC_REC_TUNING0,   /* ... ten fields, the layout of smcmc_hmc_get_tuning */
+    SMCMC_HMC_REC_COUNT_ = SMCMC_HMC_REC_TUNING0 + 10
+} smcmc_hmc_record_field;
+int smcmc_hmc_record_stride(const smcmc_hmc* h);    /* 2 dim + SMCMC_HMC_REC_COUNT_; 0 for NULL */
+int smcmc_hmc_step_recorded(smcmc_hmc* h, int nsteps, int chain, double* records);
+/* The contract of smcmc_snapshot / smcmc_rollback for a started SMCMC_MODE_PER_CHAIN HMC ensemble: the snapshot holds
+ * positions, momenta, both lane tables, the points UpdateCovariance folds, every chain's fAveragePoint, fEXXT, repaired
+ * diagonal and tuning scalars, and the step count; rollback returns to it any number of times.  Draws are keyed on
+ * (chain, step), so stepping again repeats the same steps.  Settings the engine keeps on the host -- alpha, the
+ * gradient type, the gradient matrix -- are not part of the snapshot and stay as they are at a rollback.
+ * smcmc_hmc_set_mean_epsilon and smcmc_hmc_set_leapfrog of a started engine are different: they write every chain's
+ * fMeanEpsilon / fLeapFrogSteps lanes, and the lanes ARE in the snapshot, so a rollback puts the lanes back to what they
+ * were when the snapshot was taken (the engine's host copy, which only the next Start reads, keeps the new value): set
+ * them again after the rollback, or, as TSimpleHMC_amd.H does, roll back first and set them afterwards.
+ * The snapshot is a second copy of the per-chain state, fEXXT included (dim (dim + 1) / 2 doubles per padded chain):
+ * when it does not fit, smcmc_hmc_snapshot is SMCMC_ERR_HIP, keeps nothing and leaves the engine as it was.
+ * smcmc_hmc_start discards the snapshot.  Outside the mode SMCMC_ERR_UNSUPPORTED; not started SMCMC_ERR_INVALID; a
+ * rollback without a snapshot SMCMC_ERR_LOGIC. */
+int smcmc_hmc_snapshot(smcmc_hmc* h);
+int smcmc_hmc_rollback(smcmc_hmc* h);
 
 /* ---- variable-at-a-time chains: TSimpleMCMC<L, TProposeVAATStep> ---------
  * N independent chains of sMCMC::TSimpleMCMC<L, sMCMC::TProposeVAATStep> (TProposeVAATStep.H:22-307, the proposal

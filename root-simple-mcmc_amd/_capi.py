@@ -42,6 +42,10 @@ VAAT_DIM_F64 = {"sigma": 0, "acceptance": 1}
 VAAT_DIM_I32 = {"acceptance_trials": 2, "queue": 3}
 HMC_TUNING = ["trace", "orbit", "updates", "cov_trials", "average_trials", "steps_remaining", "steps_since_update",
               "max_scale", "min_scale", "est_trace"]
+# smcmc_hmc_record_field: the scalars of a row of smcmc_hmc_step_recorded, after [0, dim) fAccepted and [dim, 2 dim)
+# fAveragePoint; SMCMC_HMC_REC_TUNING0 + k is field k of smcmc_hmc_get_tuning
+HMC_RECORD_FIELDS = ["potential", "proposed_potential", "acceptance", "last_accept", "mean_epsilon", "leapfrog",
+                     "reversal_len", "step_count"] + HMC_TUNING
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -146,6 +150,11 @@ SIGNATURES = {
     "smcmc_hmc_step": (C.c_int, [_H, C.c_int]),
     "smcmc_hmc_read_state": (C.c_int, [_H, _dp, _dp, _dp]),
     "smcmc_hmc_copy_positions": (C.c_int, [_H, C.c_void_p]),
+    "smcmc_hmc_step_save": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "smcmc_hmc_record_stride": (C.c_int, [_H]),
+    "smcmc_hmc_step_recorded": (C.c_int, [_H, C.c_int, C.c_int, _dp]),
+    "smcmc_hmc_snapshot": (C.c_int, [_H]),
+    "smcmc_hmc_rollback": (C.c_int, [_H]),
     "smcmc_hmc_nchains_padded": (C.c_int, [_H]),
     "smcmc_hmc_read_lane_f64": (C.c_int, [_H, C.c_int, _dp]),
     "smcmc_hmc_read_lane_i32": (C.c_int, [_H, C.c_int, _ip]),

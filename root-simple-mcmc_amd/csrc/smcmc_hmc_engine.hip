@@ -28,6 +28,8 @@
 
 using namespace smcmc;
 
+constexpr int kHmcSnapArrays = 9;
+
 struct smcmc_hmc {
     int dim = 0, nchains = 0, npad = 0, likelihood = 0, device = 0, W = 4;
     uint64_t seed = 0;
@@ -74,6 +76,12 @@ struct smcmc_hmc {
     DeviceBuffer<double> d_pc_avg, d_pc_exxt, d_pc_covdiag, d_pc_scal, d_pc_scratch;
     DeviceBuffer<int32_t> d_pc_work;
     int pc_grid = 0;               // workgroups of hmc_pc_error_kernel
+    // smcmc_hmc_step_recorded: one row per step of the call, gathered on the device
+    DeviceBuffer<double> d_rec;
+    // smcmc_hmc_snapshot / smcmc_hmc_rollback: a copy of the ensemble's state on the device (SMCMC_MODE_PER_CHAIN)
+    DeviceBuffer<unsigned char> snap[kHmcSnapArrays];
+    uint32_t snap_step_count = 0;
+    bool snap_valid = false;
     std::string error;
     ~smcmc_hmc() { delete shared; }
 };
@@ -430,12 +438,67 @@ int hmc_apply(smcmc_hmc* h) {
     return SMCMC_OK;
 }
 
-hipError_t hmc_dispatch(smcmc_hmc* h, const HmcParams& p) {
+hipError_t hmc_dispatch(smcmc_hmc* h, const HmcParams& p, const HmcSaveArgs* sv = nullptr);
+
+// ---- smcmc_hmc_step_save ----
+// the trace of one call: every `stride`-th of its steps has a slot; `done` counts the steps of the call that have run
+struct HmcSave {
+    double* x = nullptr;       // [slot][dim][npad]; nullptr: a plain smcmc_hmc_step
+    double* logl = nullptr;    // [slot][npad], or nullptr
+    int stride = 1;
+    int done = 0;
+};
+
+// does the step kernel of this engine have a SAVE instantiation that writes the slots itself?  (otherwise the launch
+// is cut at the save steps: the GENERIC gradient types, and the matrix kernels above 128 dimensions)
+bool hmc_saves_in_kernel(const smcmc_hmc* h) {
+    if (hmc_generic_gradient(h) || hmc_no_own_gradient(h->likelihood)) return false;
+    if (h->use_mfma || h->use_matrix_exact) return hmc_mfma_saves_in_kernel(h->dim);
+    return true;
+}
+
+HmcSaveArgs hmc_save_args(const HmcSave& sv) { return HmcSaveArgs{sv.x, sv.logl, sv.stride, sv.done}; }
+
+// fAccepted and SMCMC_LANE_LOGL of every live chain as they stand -> slot `slot` of the trace (the cut launch)
+__global__ void __launch_bounds__(256) hmc_save_slot_kernel(const double* q, const double* logl, int nchains, int npad, int dim,
+                                                            double* save_x, double* save_logl) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nchains) return;
+    const int i = blockIdx.y;
+    if (i < dim) save_x[(size_t)i * npad + c] = q[(size_t)i * npad + c];
+    else if (save_logl != nullptr) save_logl[c] = logl[c];
+}
+
+int hmc_save_slot(smcmc_hmc* h, const HmcSave& sv, int slot) {
+    const size_t NP = (size_t)h->npad;
+    hipLaunchKernelGGL(hmc_save_slot_kernel, dim3((h->nchains + 255) / 256, h->dim + 1), dim3(256), 0, h->stream,
+                       (const double*)h->d_q, (const double*)(h->d_lane_f64 + (size_t)SMCMC_LANE_LOGL * NP), h->nchains, h->npad,
+                       h->dim, sv.x + (size_t)slot * h->dim * NP, sv.logl ? sv.logl + (size_t)slot * NP : nullptr);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("trace slot launch: ") + hipGetErrorString(e));
+    return SMCMC_OK;
+}
+
+// one step of a tuned mode (one step per launch) and, when it has one, its slot
+int hmc_one_step(smcmc_hmc* h, HmcSave& sv) {
+    HmcParams p = hmc_params(h, 1, 0);
+    p.adaptive = 1;
+    const bool in_kernel = sv.x != nullptr && hmc_saves_in_kernel(h);
+    const HmcSaveArgs args = hmc_save_args(sv);
+    hipError_t e = hmc_dispatch(h, p, in_kernel ? &args : nullptr);
+    if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
+    h->step_count += 1u;
+    sv.done += 1;
+    if (sv.x != nullptr && !in_kernel && sv.done % sv.stride == 0) return hmc_save_slot(h, sv, sv.done / sv.stride - 1);
+    return SMCMC_OK;
+}
+
+hipError_t hmc_dispatch(smcmc_hmc* h, const HmcParams& p, const HmcSaveArgs* sv) {
     const bool generic = hmc_generic_gradient(h) && !p.init_only;
-    if (h->use_mfma && !generic) return launch_hmc_mfma(p, h->stream);
-    if (h->use_matrix_exact && !generic) return launch_hmc_matrix_exact(p, h->stream);
-    return (h->W == 4) ? launch_hmc<4, kPanelCW>(p, h->likelihood, h->stream)
-                       : launch_hmc<8, kPanelCW>(p, h->likelihood, h->stream);
+    if (h->use_mfma && !generic) return launch_hmc_mfma(p, h->stream, sv);
+    if (h->use_matrix_exact && !generic) return launch_hmc_matrix_exact(p, h->stream, sv);
+    return (h->W == 4) ? launch_hmc<4, kPanelCW>(p, h->likelihood, h->stream, sv)
+                       : launch_hmc<8, kPanelCW>(p, h->likelihood, h->stream, sv);
 }
 
 // ---- SMCMC_MODE_PER_CHAIN ----
@@ -843,16 +906,21 @@ int smcmc_hmc_start(smcmc_hmc* h, const double* x0, int broadcast) {
     h->host_stale = false;
     h->cov_dirty = true;
     h->steps_in_window = 0;
+    h->snap_valid = false;         // a snapshot belongs to the run it was taken in
     if (h->d_gacc) HIP_TRY(h, hipMemsetAsync(h->d_gacc, 0, sizeof(double) * fold_gacc_doubles(h->dim), h->stream));
     h->started = true;
     return SMCMC_OK;
 }
 
-int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
-    if (!h) return SMCMC_ERR_INVALID;
-    if (!h->started) return fail(h, SMCMC_ERR_INVALID, "Must initialize starting point");   // :280-284
+}  // extern "C"
+
+namespace {
+
+// nsteps x Step(false) for every chain; sv.x != nullptr: with the trace of smcmc_hmc_step_save.  after_step (per-chain
+// mode only): called on the stream's order after each step's update, with the index of the step in the call
+template <typename AfterStep>
+int hmc_run(smcmc_hmc* h, int nsteps, HmcSave sv, AfterStep&& after_step) {
     if (nsteps <= 0) return SMCMC_OK;
-    ON_DEVICE(h);
     if (hmc_no_own_gradient(h->likelihood) && !hmc_generic_gradient(h))
         return fail(h, SMCMC_ERR_RUNTIME, "the likelihood has no gradient (TSimpleHMC.H:85-89: its functor returns false): "
                                            "choose gradient type 2 (covariant), 3 (finite differences) or 5 (none)");
@@ -867,22 +935,34 @@ int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
     if (hmc_per_chain(h)) {
         // every chain tunes itself after every step (:337-341), whatever is fixed; nothing waits on the device
         for (int s = 0; s < nsteps; ++s) {
-            HmcParams p = hmc_params(h, 1, 0);
-            p.adaptive = 1;
-            hipError_t e = hmc_dispatch(h, p);
-            if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
-            h->step_count += 1u;
-            int st = hmc_pc_update(h);
+            int st = hmc_one_step(h, sv);
+            if (st) return st;
+            st = hmc_pc_update(h);
+            if (st) return st;
+            st = after_step(s);
             if (st) return st;
         }
         return SMCMC_OK;
     }
     if (!hmc_tracking(h)) {
-        // fixed step length and leapfrog count: the chains share nothing, one launch runs all the steps
-        HmcParams p = hmc_params(h, nsteps, 0);
-        hipError_t e = hmc_dispatch(h, p);
-        if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
-        h->step_count += (uint32_t)nsteps;
+        // fixed step length and leapfrog count: the chains share nothing, one launch runs all the steps -- or, with a
+        // trace and a kernel that does not write it, one launch up to each save step
+        const bool cut = sv.x != nullptr && !hmc_saves_in_kernel(h);
+        while (sv.done < nsteps) {
+            int n = nsteps - sv.done;
+            const bool to_slot = cut && sv.done + sv.stride <= (nsteps / sv.stride) * sv.stride;
+            if (to_slot) n = sv.stride;
+            HmcParams p = hmc_params(h, n, 0);
+            const HmcSaveArgs args = hmc_save_args(sv);
+            hipError_t e = hmc_dispatch(h, p, (sv.x != nullptr && !cut) ? &args : nullptr);
+            if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
+            h->step_count += (uint32_t)n;
+            sv.done += n;
+            if (to_slot) {
+                int st = hmc_save_slot(h, sv, sv.done / sv.stride - 1);
+                if (st) return st;
+            }
+        }
         return SMCMC_OK;
     }
     int st = hmc_tracking_buffers(h);
@@ -892,21 +972,152 @@ int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
             st = hmc_generic_buffers(h);
             if (st) return st;
         }
-        HmcParams p = hmc_params(h, 1, 0);
-        p.adaptive = 1;
-        hipError_t e = hmc_dispatch(h, p);
-        if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("hmc step launch: ") + hipGetErrorString(e));
-        h->step_count += 1u;
+        st = hmc_one_step(h, sv);
+        if (st) return st;
         // UpdateCovariance (:338): the point each chain stood on, if its proposal's potential was finite (:336)
         const double* qprev = h->d_qprev;
-        e = smcmc::fold_points(h->fold, &qprev, 1, h->d_zero, h->d_lane_i32 + (size_t)kHmcLaneContributes * h->npad, h->d_gacc,
-                               h->stream);
+        hipError_t e = smcmc::fold_points(h->fold, &qprev, 1, h->d_zero, h->d_lane_i32 + (size_t)kHmcLaneContributes * h->npad,
+                                          h->d_gacc, h->stream);
         if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("fold launch: ") + hipGetErrorString(e));
         if (++h->steps_in_window >= h->sync_every) {
             st = hmc_sync(h);
             if (st) return st;
         }
     }
+    return SMCMC_OK;
+}
+
+// ---- smcmc_hmc_step_recorded ----
+// the row of one chain after a step and its update: what smcmc_hmc_read_state, the lanes and smcmc_hmc_read_chain_tuning
+// would return at that moment
+__global__ void __launch_bounds__(kWave) hmc_record_kernel(const double* q, const double* avg, const double* lane_f64,
+                                                           const int32_t* lane_i32, const double* scal, int npad, int dim,
+                                                           int chain, uint32_t step_count, double* row) {
+    const size_t NP = (size_t)npad;
+    for (int i = threadIdx.x; i < dim; i += kWave) {
+        row[i] = q[(size_t)i * NP + chain];
+        row[dim + i] = avg[(size_t)i * NP + chain];
+    }
+    double* sc = row + 2 * dim;
+    if (threadIdx.x == 0) {
+        sc[SMCMC_HMC_REC_POTENTIAL] = -lane_f64[(size_t)SMCMC_LANE_LOGL * NP + chain];
+        sc[SMCMC_HMC_REC_PROPOSED_POTENTIAL] = -lane_f64[(size_t)SMCMC_LANE_LOGL_PROPOSED * NP + chain];
+        sc[SMCMC_HMC_REC_ACCEPTANCE] = lane_f64[(size_t)SMCMC_LANE_ACCEPTANCE * NP + chain];
+        sc[SMCMC_HMC_REC_LAST_ACCEPT] = (double)lane_i32[(size_t)SMCMC_LANE_LAST_ACCEPT * NP + chain];
+        sc[SMCMC_HMC_REC_MEAN_EPSILON] = lane_f64[(size_t)kHmcLaneMeanEpsilon * NP + chain];
+        sc[SMCMC_HMC_REC_LEAPFROG] = (double)lane_i32[(size_t)kHmcLaneLeapfrog * NP + chain];
+        sc[SMCMC_HMC_REC_REVERSAL_LEN] = lane_f64[(size_t)kHmcLaneReversalLen * NP + chain];
+        sc[SMCMC_HMC_REC_STEP_COUNT] = (double)step_count;
+    }
+    if (threadIdx.x < kPcTuningFields) sc[SMCMC_HMC_REC_TUNING0 + threadIdx.x] = scal[(size_t)threadIdx.x * NP + chain];
+}
+
+// the arrays of a snapshot (SMCMC_MODE_PER_CHAIN, started)
+int hmc_snap_arrays(smcmc_hmc* h, void** arr, size_t* bytes) {
+    const size_t D = (size_t)h->dim, NP = (size_t)h->npad;
+    arr[0] = h->d_q; bytes[0] = sizeof(double) * D * NP;
+    arr[1] = h->d_pm; bytes[1] = sizeof(double) * D * NP;
+    arr[2] = h->d_lane_f64; bytes[2] = sizeof(double) * NP * SMCMC_LANE_F64_COUNT_;
+    arr[3] = h->d_lane_i32; bytes[3] = sizeof(int32_t) * NP * SMCMC_LANE_I32_COUNT_;
+    arr[4] = h->d_qprev; bytes[4] = sizeof(double) * D * NP;
+    arr[5] = h->d_pc_avg; bytes[5] = sizeof(double) * D * NP;
+    arr[6] = h->d_pc_exxt; bytes[6] = sizeof(double) * pc_npacked(h->dim) * NP;
+    arr[7] = h->d_pc_covdiag; bytes[7] = sizeof(double) * D * NP;
+    arr[8] = h->d_pc_scal; bytes[8] = sizeof(double) * kPcCount * NP;
+    for (int k = 0; k < kHmcSnapArrays; ++k)
+        if (!arr[k]) return fail(h, SMCMC_ERR_LOGIC, "the ensemble has not been started in SMCMC_MODE_PER_CHAIN");
+    return SMCMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smcmc_hmc_step(smcmc_hmc* h, int nsteps) {
+    if (!h) return SMCMC_ERR_INVALID;
+    if (!h->started) return fail(h, SMCMC_ERR_INVALID, "Must initialize starting point");   // :280-284
+    if (nsteps <= 0) return SMCMC_OK;
+    ON_DEVICE(h);
+    return hmc_run(h, nsteps, HmcSave{}, [](int) { return (int)SMCMC_OK; });
+}
+
+int smcmc_hmc_step_save(smcmc_hmc* h, int nsteps, int stride, double* save_x_device, double* save_logl_device) {
+    if (!h) return SMCMC_ERR_INVALID;
+    if (!h->started) return fail(h, SMCMC_ERR_INVALID, "Must initialize starting point");
+    if (!save_x_device || stride < 1 || nsteps < 0)
+        return fail(h, SMCMC_ERR_INVALID, "smcmc_hmc_step_save: a trace buffer, stride >= 1, nsteps >= 0");
+    ON_DEVICE(h);
+    HmcSave sv;
+    sv.x = save_x_device; sv.logl = save_logl_device; sv.stride = stride;
+    return hmc_run(h, nsteps, sv, [](int) { return (int)SMCMC_OK; });
+}
+
+int smcmc_hmc_record_stride(const smcmc_hmc* h) { return h ? 2 * h->dim + SMCMC_HMC_REC_COUNT_ : 0; }
+
+int smcmc_hmc_step_recorded(smcmc_hmc* h, int nsteps, int chain, double* records) {
+    if (!h) return SMCMC_ERR_INVALID;
+    if (!h->started) return fail(h, SMCMC_ERR_INVALID, "Must initialize starting point");
+    if (!records) return fail(h, SMCMC_ERR_INVALID, "smcmc_hmc_step_recorded: no record array");
+    if (!hmc_per_chain(h))
+        return fail(h, SMCMC_ERR_UNSUPPORTED, "smcmc_hmc_step_recorded serves SMCMC_MODE_PER_CHAIN (the pooled update decides on the host)");
+    if (chain < 0 || chain >= h->nchains) return fail(h, SMCMC_ERR_INVALID, "no such chain");
+    if (nsteps <= 0) return SMCMC_OK;
+    ON_DEVICE(h);
+    const int stride = smcmc_hmc_record_stride(h);
+    const size_t need = (size_t)nsteps * stride;
+    if (need > h->d_rec.size()) HIP_TRY(h, h->d_rec.allocate(need));
+    const int st = hmc_run(h, nsteps, HmcSave{}, [&](int s) {
+        hipLaunchKernelGGL(hmc_record_kernel, dim3(1), dim3(kWave), 0, h->stream, (const double*)h->d_q, (const double*)h->d_pc_avg,
+                           (const double*)h->d_lane_f64, (const int32_t*)h->d_lane_i32, (const double*)h->d_pc_scal, h->npad,
+                           h->dim, chain, h->step_count, h->d_rec + (size_t)s * stride);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("record launch: ") + hipGetErrorString(e));
+        return (int)SMCMC_OK;
+    });
+    if (st) return st;
+    HIP_TRY(h, hipMemcpyAsync(records, h->d_rec, need * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SMCMC_OK;
+}
+
+int smcmc_hmc_snapshot(smcmc_hmc* h) {
+    if (!h) return SMCMC_ERR_INVALID;
+    ON_DEVICE(h);
+    if (!hmc_per_chain(h)) return fail(h, SMCMC_ERR_UNSUPPORTED, "smcmc_hmc_snapshot serves SMCMC_MODE_PER_CHAIN");
+    if (!h->started) return fail(h, SMCMC_ERR_INVALID, "Must initialize starting point");
+    void* arr[kHmcSnapArrays]; size_t bytes[kHmcSnapArrays];
+    int st = hmc_snap_arrays(h, arr, bytes);
+    if (st) return st;
+    h->snap_valid = false;
+    for (int k = 0; k < kHmcSnapArrays; ++k) {
+        if (h->snap[k].size() == bytes[k]) continue;
+        const hipError_t e = h->snap[k].allocate(bytes[k]);
+        if (e != hipSuccess) {
+            // a second copy of the per-chain state does not fit: nothing is kept, and the engine steps on as it was
+            for (int j = 0; j < kHmcSnapArrays; ++j) h->snap[j] = DeviceBuffer<unsigned char>();
+            (void)hipGetLastError();
+            return fail(h, SMCMC_ERR_HIP, std::string("the snapshot does not fit in device memory: ") + hipGetErrorString(e));
+        }
+    }
+    for (int k = 0; k < kHmcSnapArrays; ++k)
+        HIP_TRY(h, hipMemcpyAsync(h->snap[k], arr[k], bytes[k], hipMemcpyDeviceToDevice, h->stream));
+    h->snap_step_count = h->step_count;
+    h->snap_valid = true;
+    return SMCMC_OK;
+}
+
+int smcmc_hmc_rollback(smcmc_hmc* h) {
+    if (!h) return SMCMC_ERR_INVALID;
+    ON_DEVICE(h);
+    if (!hmc_per_chain(h)) return fail(h, SMCMC_ERR_UNSUPPORTED, "smcmc_hmc_rollback serves SMCMC_MODE_PER_CHAIN");
+    if (!h->started) return fail(h, SMCMC_ERR_INVALID, "Must initialize starting point");
+    if (!h->snap_valid) return fail(h, SMCMC_ERR_LOGIC, "no snapshot to return to");
+    void* arr[kHmcSnapArrays]; size_t bytes[kHmcSnapArrays];
+    int st = hmc_snap_arrays(h, arr, bytes);
+    if (st) return st;
+    for (int k = 0; k < kHmcSnapArrays; ++k)
+        HIP_TRY(h, hipMemcpyAsync(arr[k], h->snap[k], bytes[k], hipMemcpyDeviceToDevice, h->stream));
+    h->step_count = h->snap_step_count;
     return SMCMC_OK;
 }
 

@@ -95,8 +95,27 @@ struct HmcParams {
                            // no longer Error q, and the potential contracts with Eperm once more
 };
 
-template <int W, int CW, int LIKE, bool GENERIC = false>
-__global__ void __launch_bounds__(W * kWave) hmc_step_kernel(const HmcParams p) {
+// smcmc_hmc_step_save: after every stride-th step of the call, fAccepted of every live chain and its SMCMC_LANE_LOGL go
+// into the slot that step has.  A second kernel argument, read by the SAVE instantiations only: the instantiations that
+// serve smcmc_hmc_step are compiled without a trace of it (HmcParams and their code are what they were before it).
+struct HmcSaveArgs {
+    double* x;             // the call's trace [slot][dim][npad]
+    double* logl;          // the call's [slot][npad], or nullptr
+    int stride;
+    int first;             // steps of the call that ran before this launch
+};
+
+// the steps of this launch until its first slot, and that slot
+__device__ __forceinline__ void hmc_save_phase(const HmcSaveArgs& sv, int& wait, size_t& slot) {
+    wait = sv.stride - sv.first % sv.stride;
+    slot = (size_t)(sv.first / sv.stride);
+}
+
+// SAVE: the instantiation smcmc_hmc_step_save launches (the likelihood's own gradient only: the GENERIC instantiations
+// spill most of their state already and are served by cutting the launch at the save steps instead)
+template <int W, int CW, int LIKE, bool GENERIC = false, bool SAVE = false>
+__global__ void __launch_bounds__(W * kWave) hmc_step_kernel(const HmcParams p, const HmcSaveArgs sv) {
+    static_assert(!(GENERIC && SAVE), "the GENERIC instantiations do not write a trace");
     __shared__ double rbuf[kPanelRows * kWave];                                   // q rows of the current panel
     __shared__ __attribute__((aligned(16))) double ulds[W * kPanelRows * CW];     // Error^T panels / gather panels
     __shared__ double verdict_f[kWave];
@@ -399,6 +418,9 @@ __global__ void __launch_bounds__(W * kWave) hmc_step_kernel(const HmcParams p) 
     int lfrog = p.adaptive ? li[kHmcLaneLeapfrog * NP] : -p.leapfrog;
     double reversal = p.adaptive ? lf[kHmcLaneReversalLen * NP] : 0.0;
     int contributes = 1;
+    int save_wait = 0;
+    size_t save_slot = 0;
+    if constexpr (SAVE) hmc_save_phase(sv, save_wait, save_slot);
 
     for (int s = 0; s < p.nsteps; ++s) {
         const uint64_t step = (uint64_t)(p.step0 + (uint32_t)s + 1u);   // ++fStepCount, :286
@@ -542,18 +564,31 @@ __global__ void __launch_bounds__(W * kWave) hmc_step_kernel(const HmcParams p) 
             acceptance = (acceptance * 4999.0) / 5000.0;                        // :367
         }
         last_accept = take ? 1 : 0;
+        // the slot of this step, if it has one: the accepted point whether the step was taken or not, then -pot_acc
+        double* save_q = nullptr;
+        if constexpr (SAVE) {
+            if (--save_wait == 0) save_q = sv.x + save_slot * (size_t)D * NP;
+        }
 #pragma unroll
         for (int il = 0; il < CW; ++il) {
             const int i = il * W + w;
             if (i < D && active) {
                 if (p.adaptive) p.qprev[(size_t)i * NP + chain] = p.q[(size_t)i * NP + chain];   // what :338 folds
                 if (take) {                                                     // :380-383
-                    p.q[(size_t)i * NP + chain] = p.qn[(size_t)i * NP + chain];
+                    const double v = p.qn[(size_t)i * NP + chain];
+                    p.q[(size_t)i * NP + chain] = v;
                     p.pm[(size_t)i * NP + chain] = p.pn[(size_t)i * NP + chain];
+                    if (SAVE && save_q != nullptr) save_q[(size_t)i * NP + chain] = v;
                 } else {                                                        // :364-366
                     p.pm[(size_t)i * NP + chain] = -p.pm[(size_t)i * NP + chain];
+                    if (SAVE && save_q != nullptr) save_q[(size_t)i * NP + chain] = p.q[(size_t)i * NP + chain];
                 }
             }
+        }
+        if (SAVE && save_q != nullptr) {
+            if (w == 0 && active && sv.logl != nullptr) sv.logl[save_slot * NP + chain] = -pot_acc;
+            save_wait = sv.stride;
+            ++save_slot;
         }
         __syncthreads();
     }
@@ -574,7 +609,8 @@ __global__ void __launch_bounds__(W * kWave) hmc_step_kernel(const HmcParams p) 
     }
 }
 
+// sv != nullptr: the SAVE instantiation (hipErrorInvalidValue where there is none: hmc_saves_in_kernel)
 template <int W, int CW>
-hipError_t launch_hmc(const HmcParams& p, int like, hipStream_t stream);
+hipError_t launch_hmc(const HmcParams& p, int like, hipStream_t stream, const HmcSaveArgs* sv = nullptr);
 
 }  // namespace smcmc

@@ -37,6 +37,10 @@ constexpr int kMfCT = 32;                            // chains per workgroup
 constexpr int kMfW = 8;                              // wavefronts per workgroup
 constexpr int kMfTIMax = 4;                          // 16-component tiles per wavefront: dim <= 512
 constexpr int kMfDimMax = 16 * kMfW * kMfTIMax;
+// smcmc_hmc_step_save: the SAVE instantiations hmc_mfma_kernel<1, *, true> (dim <= 128) write the slots themselves.  The
+// instantiations with two and four tiles are at the register limit of their one workgroup per CU (their private segment
+// grows with the stores): for them the engine cuts the launch at the save steps and copies the slot.
+inline bool hmc_mfma_saves_in_kernel(int dim) { return dim <= 16 * kMfW; }
 
 // Eop[(tile * nkqp + kq) * 64 + lane] = Error(16 tile + (lane & 15), 4 kq + (lane >> 4)), zero padded
 // (k-quads per tile rounded up to the prefetch depth of pm_contract, zero padded)
@@ -51,8 +55,10 @@ inline size_t hmc_exact_ex_doubles(int dim) { return (size_t)((dim + 15) / 16) *
 // ascending (TDummyLogLikelihood.H:34-42), on the vector pipe in the same layout (p.Eperm = Ex).  With the caller's
 // gradient matrix (p.Gperm, in the layout of Ex) the leapfrog contracts with it instead, and the potential of the
 // proposal with Error once more: L + 2 passes of the same loop per step instead of L + 1.
-template <int kMfTI, bool FUSED = true>
-__global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParams p) {
+// SAVE: the instantiation smcmc_hmc_step_save launches (sv: see HmcSaveArgs; the others never read it).
+template <int kMfTI, bool FUSED = true, bool SAVE = false>
+__global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParams p, const HmcSaveArgs sv) {
+    static_assert(!SAVE || kMfTI == 1, "only the one-tile instantiations write a trace");
     __shared__ double qs[16 * kMfW * kMfTI * kMfCT];   // [component][chain]: the published vector
     // one 16-component tile per wavefront x 32 chains: ordered sums that must leave qs (the positions) alone; its
     // first bytes double as the verdict of the Hamiltonian test (with kMfTI = 4 the two arrays fill the 160 KB)
@@ -261,6 +267,10 @@ __global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParam
 
     // what the leapfrog contracts with: Error, or the caller's gradient matrix (smcmc_hmc_set_gradient_matrix)
     const double* const grad_matrix = (!FUSED && p.Gperm != nullptr) ? p.Gperm : p.Eperm;
+    constexpr bool kSaves = SAVE;
+    int save_wait = 0;
+    size_t save_slot = 0;
+    if constexpr (kSaves) hmc_save_phase(sv, save_wait, save_slot);
 
     for (int s = 0; s < p.nsteps; ++s) {
         const uint64_t step = (uint64_t)(p.step0 + (uint32_t)s + 1u);   // ++fStepCount, :286
@@ -419,6 +429,11 @@ __global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParam
             last_accept = reject ? 0 : 1;
         }
         __syncthreads();
+        // the slot of this step, if it has one: the accepted point whether the step was taken or not, then -pot_acc
+        double* save_q = nullptr;
+        if constexpr (kSaves) {
+            if (--save_wait == 0) save_q = sv.x + save_slot * (size_t)D * NP;
+        }
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
             const bool take = verdict[16 * ct + c] != 0;
@@ -431,13 +446,21 @@ __global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParam
                     if (owns(t) && i < D && chain < p.nchains) {
                         if (p.adaptive) p.qprev[(size_t)i * NP + chain] = p.q[(size_t)i * NP + chain];   // what :338 folds
                         if (take) {                                     // :380-383
-                            p.q[(size_t)i * NP + chain] = p.qn[(size_t)i * NP + chain];
+                            const double v = p.qn[(size_t)i * NP + chain];
+                            p.q[(size_t)i * NP + chain] = v;
                             p.pm[(size_t)i * NP + chain] = pn[t][ct][r];
+                            if (kSaves && save_q != nullptr) save_q[(size_t)i * NP + chain] = v;
                         } else {                                        // :364-366
                             p.pm[(size_t)i * NP + chain] = -p.pm[(size_t)i * NP + chain];
+                            if (kSaves && save_q != nullptr) save_q[(size_t)i * NP + chain] = p.q[(size_t)i * NP + chain];
                         }
                     }
                 }
+        }
+        if (kSaves && save_q != nullptr) {
+            if (summer && mychain < p.nchains && sv.logl != nullptr) sv.logl[save_slot * NP + mychain] = -pot_acc;
+            save_wait = sv.stride;
+            ++save_slot;
         }
         __syncthreads();
     }
@@ -458,7 +481,8 @@ __global__ void __launch_bounds__(kMfW* kWave, 1) hmc_mfma_kernel(const HmcParam
     }
 }
 
-hipError_t launch_hmc_mfma(const HmcParams& p, hipStream_t stream);
-hipError_t launch_hmc_matrix_exact(const HmcParams& p, hipStream_t stream);
+// sv != nullptr: the SAVE instantiation (dim <= 128: hmc_mfma_saves_in_kernel; hipErrorInvalidValue above)
+hipError_t launch_hmc_mfma(const HmcParams& p, hipStream_t stream, const HmcSaveArgs* sv = nullptr);
+hipError_t launch_hmc_matrix_exact(const HmcParams& p, hipStream_t stream, const HmcSaveArgs* sv = nullptr);
 
 }  // namespace smcmc

@@ -1209,6 +1209,27 @@ class HmcEngine:
             self.SetGradientType(gradient_type)
         self._check(self._lib.smcmc_hmc_step(self._h, int(nsteps)))
 
+    def StepSave(self, nsteps, save_x_ptr, save_logl_ptr=None, stride=1):
+        """As Step, and after every `stride`-th step of the call the accepted points go into the device buffer
+        save_x[slot][dim][nchains_padded] and lane "logl" into save_logl[slot][nchains_padded] (raw pointers; save_logl_ptr
+        may be None), from the launches that make the steps (smcmc_hmc_step_save)."""
+        self._check(self._lib.smcmc_hmc_step_save(self._h, int(nsteps), int(stride), C.c_void_p(int(save_x_ptr)),
+                                                  C.c_void_p(int(save_logl_ptr)) if save_logl_ptr else None))
+
+    def snapshot(self): self._check(self._lib.smcmc_hmc_snapshot(self._h))
+    def rollback(self): self._check(self._lib.smcmc_hmc_rollback(self._h))
+
+    @property
+    def record_stride(self): return self._lib.smcmc_hmc_record_stride(self._h)
+
+    def StepRecorded(self, nsteps, chain=0):
+        """nsteps x Step(false) of the ensemble (MODE_PER_CHAIN) with the per-step record of one chain
+        (smcmc_hmc_step_recorded): an [nsteps, record_stride] array, a row = [0, dim) fAccepted, [dim, 2 dim) fAveragePoint,
+        then the scalars HMC_RECORD_FIELDS, all after the step and the update that follows it."""
+        rec = np.zeros((int(nsteps), self.record_stride))
+        self._check(self._lib.smcmc_hmc_step_recorded(self._h, int(nsteps), int(chain), _ptr(rec)))
+        return rec
+
     def state(self):
         q = np.zeros((self.dim, self.nchains))
         m = np.zeros((self.dim, self.nchains))
