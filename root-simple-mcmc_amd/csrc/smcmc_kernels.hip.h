@@ -30,6 +30,7 @@
 
 #include "smcmc.h"
 #include "smcmc_detmath.h"
+#include "smcmc_step_deal.h"
 
 namespace smcmc {
 
@@ -117,70 +118,6 @@ __device__ __forceinline__ void static_for_impl(F& f) {
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) { static_for_impl<0, N>(f); }
 
-constexpr int kPiece = 16;   // columns of U consumed per scheduling region (8 x ds_read_b128)
-
-template <int DP>
-struct Geo {
-    static constexpr int T = (DP + 1 + 15) / 16;   // 16-row tiles covering dims 0..DP-1 plus the ones row DP
-    static constexpr int NT = T * (T + 1) / 2;     // lower-triangular tiles
-    static constexpr int NB = (DP + 3) / 4;        // Philox blocks of 4 normals
-    static constexpr int ROWS_MOMENTS = DP + 1;    // LDS rows of x: the dims and the ones row (zero rows are synthesized)
-    // When at most 4 rows spill into the last 16-row tile (D = 50: rows 48, 49 and the ones row), that tile
-    // row is folded with v_mfma_f64_4x4x4_4b_f64 instead (a quarter of the matrix-pipe time): its four
-    // 4x4 blocks are (strip rows) x (columns 16 t + 4 blk ..), which lands exactly where register 0 of
-    // tile (T-1, t) of the 16x16 scheme would, so the stored layout does not change.
-    static constexpr bool STRIP = ((DP + 1) % 16 != 0) && ((DP + 1) % 16 <= 4);
-    static constexpr int T16 = STRIP ? T - 1 : T;  // tile rows folded with 16x16x4
-    static constexpr int NT16 = T16 * (T16 + 1) / 2;
-};
-
-// LDS image of the decomposition: row i keeps columns j0(i)..DP-1 (j0 = i rounded
-// down to even for the triangular factor, 0 for a full matrix), padded to an even
-// length so that every row starts 16-byte aligned (ds_read_b128 = two columns).
-template <int DP, bool FULLU>
-struct ULayout {
-    static constexpr int DPE = DP + (DP & 1);       // DP rounded up to even
-    static constexpr int j0(int i) { return FULLU ? 0 : (i & ~1); }
-    static constexpr int len(int i) { return DPE - j0(i); }
-    // closed form of sum_{r<i} len(r) (no loop: must fold once the caller's loops unroll)
-    static constexpr int off(int i) {
-        return FULLU ? i * DPE
-                     : i * DPE - ((i & 1) ? 2 * (i / 2) * (i / 2) : 2 * (i / 2) * (i / 2 - 1));
-    }
-    static constexpr int SIZE = off(DP);
-};
-
-// The pieces (row, first column) that the rows of Philox block B contribute, in
-// the order they are consumed.
-template <int DP, bool FULLU, int B>
-struct UPieces {
-    typedef ULayout<DP, FULLU> UL;
-    static constexpr int rows() { return (4 * B + 4 <= DP) ? 4 : (DP - 4 * B); }
-    static constexpr int per_row(int i) { return (UL::len(i) + kPiece - 1) / kPiece; }
-    static constexpr int count() {
-        int n = 0;
-        for (int q = 0; q < rows(); ++q) n += per_row(4 * B + q);
-        return n;
-    }
-    static constexpr int COUNT = count();
-    // pieces of the blocks before B (all rows < 4B)
-    static constexpr int first_global() {
-        int n = 0;
-        for (int i = 0; i < 4 * B; ++i) n += per_row(i);
-        return n;
-    }
-    static constexpr int row(int r) {
-        int i = 4 * B;
-        while (r >= per_row(i)) { r -= per_row(i); ++i; }
-        return i;
-    }
-    static constexpr int col(int r) {
-        int i = 4 * B;
-        while (r >= per_row(i)) { r -= per_row(i); ++i; }
-        return UL::j0(i) + r * kPiece;
-    }
-};
-
 // kPiece columns of row i starting at column c (c - j0(i) is even: 16-byte aligned reads).
 //
 // The reads are inline assembly and so is the wait for them.  A lone wavefront pays an issue slot (four cycles) for
@@ -200,13 +137,6 @@ __device__ __forceinline__ void load_piece(uint32_t ubase, f64x2 (&dst)[kPiece /
         }
         load_piece<DP, FULLU, i, c, k + 1>(ubase, dst);
     }
-}
-// LDS reads load_piece issues for the piece at column c
-template <int DP, bool FULLU, int c>
-constexpr int piece_reads() {
-    int n = 0;
-    for (int k = 0; k < kPiece / 2; ++k) n += (c + 2 * k < ULayout<DP, FULLU>::DPE) ? 1 : 0;
-    return n;
 }
 // every LDS read older than the N youngest has returned; `piece` is the piece those older reads filled (its first M pairs)
 template <int N, int M, bool ASM>
@@ -246,13 +176,6 @@ __device__ __forceinline__ void operands_ready(double (&raw)[T], double& raws) {
     } else {
         asm volatile("" : "+v"(raws));
     }
-}
-
-// row ti of lower-triangular tile number `tile` (tile = ti (ti + 1) / 2 + tj, tj <= ti)
-constexpr int tile_row(int tile) {
-    int ti = 0;
-    while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-    return ti;
 }
 
 struct StepParams {
@@ -678,6 +601,9 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     // the families below 47 share a SIMD between two wavefronts, and the other likelihoods and the 47-dimension family
     // have no timing yet.  Every other instantiation keeps the step boundary it had, instruction for instruction.
     constexpr bool BOUNDARY = EXACT && !SWAP && !FULLU && !SPECIAL && DP == 50 && LIKE == SMCMC_LIKE_ISO_GAUSS;
+    // ... and, with the moment fold, its matrix instructions dealt over the pieces by plan (smcmc_step_deal.h;
+    // profiles/step_shadow_notes.md) instead of evenly by piece number
+    constexpr bool DEAL = BOUNDARY && MOMENTS && OPF && Geo<DP>::STRIP;
 
     // Coordinate 0 of the accepted point, which UpdateState compares with the step before.  BOUNDARY: carried in a register
     // from commit to commit (read back from LDS at the top of a step it was a read and a full wait behind the commit's
@@ -928,6 +854,9 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
                 load_piece<DP, FULLU, i0, c0p>(up, cur);
                 if constexpr (4 * b + 2 < DP) normal_tables_ready<piece_reads<DP, FULLU, c0p>(), kAsmReads<DP>>(t0, t1);
                 else normal_tables_ready<piece_reads<DP, FULLU, c0p>(), kAsmReads<DP>>(t0);
+                // the reads stay right behind the matrix instruction that closed the block before: the vector
+                // instructions of the normals that need no table would otherwise go first, and wait for it
+                if constexpr (DEAL) __builtin_amdgcn_sched_barrier(0);
             }
             double n[4];
             normal_pair_lds(blk.v[0], blk.v[1], t0, &n[0], &n[1]);
@@ -978,46 +907,89 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
                     // operands of the next k-quad, then the next piece's eight reads and its wait -- and runs in
                     // its shadow.  (Left to the scheduler it goes to the top of the piece, in front of 32 vector
                     // instructions that then wait for it.)  Chains fold in ascending order.
-                    constexpr int G = UPieces<DP, FULLU, NB - 1>::first_global() + UPieces<DP, FULLU, NB - 1>::COUNT;
-                    constexpr int NM = 16 * NT;
-                    constexpr int m_lo = (int)(((long)g * NM) / G), m_hi = (int)(((long)(g + 1) * NM) / G);
-                    if constexpr (m_hi > m_lo) __builtin_amdgcn_sched_barrier(0);
-                    static_for<m_hi - m_lo>([&](auto mc) {
-                        constexpr int m = m_lo + decltype(mc)::value;
-                        constexpr int kk = m / NT, tile = m % NT;
-                        if constexpr (tile == 0) {
-                            if constexpr (OPF) operands_ready<T>(raw, raws);   // fetched a k-quad ago, a piece_ready since
+                    if constexpr (DEAL) {
+                        // The headline kernels deal by the plan of smcmc_step_deal.h instead of by piece number: one
+                        // 16x16 per slot, last in its slot (what follows the slot issues in ITS shadow), the strip
+                        // instructions in front of it or alone behind the pieces whose successor has few reads, the
+                        // operand prefetch at the end of the slot that opens a k-quad.  The order inside a slot is pinned
+                        // (left alone the scheduler puts a strip instruction behind the 16x16), and so is the operand
+                        // preparation in front of the k-quad's first instruction (left alone, all but the first operand's
+                        // sink behind it and wait out its 64 cycles).
+                        static_assert(StepDeal<DP>::valid(kStepDealPlan<DP>) && StepDeal<DP>::G == UPieces<DP, FULLU, NB - 1>::first_global() + UPieces<DP, FULLU, NB - 1>::COUNT,
+                                      "the plan keeps the operands' order: see smcmc_step_deal.h");
+                        constexpr int m_lo = kStepDealPlan<DP>.first[g], m_hi = kStepDealPlan<DP>.first[g + 1];
+                        if constexpr (m_hi > m_lo) __builtin_amdgcn_sched_barrier(0);
+                        static_for<m_hi - m_lo>([&](auto mc) {
+                            constexpr int m = m_lo + decltype(mc)::value;
+                            constexpr int kk = kStepDealPlan<DP>.kk[m], tile = kStepDealPlan<DP>.tile[m];
+                            if constexpr (m % NT == 0) {
+                                operands_ready<T>(raw, raws);   // fetched a k-quad ago, a piece_ready since
 #pragma unroll
-                            for (int t = 0; t < T; ++t) {
-                                if constexpr (OPF) ma[t] = raw[t] - c0r[t];
-                                else ma[t] = xs[xrow[t] + 4 * kk] - c0r[t];
-                                if (16 * t + 15 > DP) ma[t] = (16 * t + (lane & 15) <= DP) ? ma[t] : 0.0;   // rows past the ones row
-                            }
-                            if constexpr (STRIP) {
-                                if constexpr (OPF) ms = raws - c0s;
-                                else ms = xs[xsrow + 4 * kk] - c0s;
+                                for (int t = 0; t < T; ++t) {
+                                    ma[t] = raw[t] - c0r[t];
+                                    if (16 * t + 15 > DP) ma[t] = (16 * t + (lane & 15) <= DP) ? ma[t] : 0.0;   // rows past the ones row
+                                }
+                                ms = raws - c0s;
                                 ms = (16 * Geo<DP>::T16 + (lane & 3) <= DP) ? ms : 0.0;
+                                __builtin_amdgcn_sched_barrier(0);
                             }
-                        }
-                        if constexpr (!STRIP || tile < NT16) {
-                            constexpr int ti = tile_row(tile), tj = tile - ti * (ti + 1) / 2;
-                            acc[tile] = __builtin_amdgcn_mfma_f64_16x16x4f64(ma[ti], ma[tj], acc[tile], 0, 0, 0);
-                            asm volatile("" : "+a"(acc[tile]));   // keeps the instruction in this piece
-                        } else {
-                            // A: strip rows (lane & 3) x chains (lane >> 4), the same for the four blocks;
-                            // B: the column operand of tile column t, block (lane >> 2) & 3
-                            constexpr int t = tile - NT16;
-                            accs[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(ms, ma[t], accs[t], 0, 0, 0);
-                            asm volatile("" : "+a"(accs[t]));
-                        }
-                        if constexpr (tile == 0 && OPF && kk + 1 < 16) {
-                            // (behind the k-quad's first matrix instruction: in its shadow) the next k-quad's first
-                            // matrix instruction sits in a later piece
-                            static_assert(((long)(kk + 1) * NT * G) / NM > g, "operand prefetch needs a piece boundary");
-                            fetch_operands<T, kk + 1>(xaddr, raw);
-                            if constexpr (STRIP) fetch_operand<kk + 1>(xsaddr, raws);
-                        }
-                    });
+                            if constexpr (tile < NT16) {
+                                constexpr int ti = tile_row(tile), tj = tile - ti * (ti + 1) / 2;
+                                acc[tile] = __builtin_amdgcn_mfma_f64_16x16x4f64(ma[ti], ma[tj], acc[tile], 0, 0, 0);
+                                asm volatile("" : "+a"(acc[tile]));   // keeps the instruction in this piece
+                            } else {
+                                constexpr int t = tile - NT16;
+                                accs[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(ms, ma[t], accs[t], 0, 0, 0);
+                                asm volatile("" : "+a"(accs[t]));
+                            }
+                            if constexpr (m + 1 < m_hi) __builtin_amdgcn_sched_barrier(0);
+                            if constexpr (kStepDealPlan<DP>.pf_after[m]) {
+                                fetch_operands<T, kk + 1>(xaddr, raw);
+                                fetch_operand<kk + 1>(xsaddr, raws);
+                            }
+                        });
+                    } else {
+                        constexpr int G = UPieces<DP, FULLU, NB - 1>::first_global() + UPieces<DP, FULLU, NB - 1>::COUNT;
+                        constexpr int NM = 16 * NT;
+                        constexpr int m_lo = (int)(((long)g * NM) / G), m_hi = (int)(((long)(g + 1) * NM) / G);
+                        if constexpr (m_hi > m_lo) __builtin_amdgcn_sched_barrier(0);
+                        static_for<m_hi - m_lo>([&](auto mc) {
+                            constexpr int m = m_lo + decltype(mc)::value;
+                            constexpr int kk = m / NT, tile = m % NT;
+                            if constexpr (tile == 0) {
+                                if constexpr (OPF) operands_ready<T>(raw, raws);   // fetched a k-quad ago, a piece_ready since
+#pragma unroll
+                                for (int t = 0; t < T; ++t) {
+                                    if constexpr (OPF) ma[t] = raw[t] - c0r[t];
+                                    else ma[t] = xs[xrow[t] + 4 * kk] - c0r[t];
+                                    if (16 * t + 15 > DP) ma[t] = (16 * t + (lane & 15) <= DP) ? ma[t] : 0.0;   // rows past the ones row
+                                }
+                                if constexpr (STRIP) {
+                                    if constexpr (OPF) ms = raws - c0s;
+                                    else ms = xs[xsrow + 4 * kk] - c0s;
+                                    ms = (16 * Geo<DP>::T16 + (lane & 3) <= DP) ? ms : 0.0;
+                                }
+                            }
+                            if constexpr (!STRIP || tile < NT16) {
+                                constexpr int ti = tile_row(tile), tj = tile - ti * (ti + 1) / 2;
+                                acc[tile] = __builtin_amdgcn_mfma_f64_16x16x4f64(ma[ti], ma[tj], acc[tile], 0, 0, 0);
+                                asm volatile("" : "+a"(acc[tile]));   // keeps the instruction in this piece
+                            } else {
+                                // A: strip rows (lane & 3) x chains (lane >> 4), the same for the four blocks;
+                                // B: the column operand of tile column t, block (lane >> 2) & 3
+                                constexpr int t = tile - NT16;
+                                accs[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(ms, ma[t], accs[t], 0, 0, 0);
+                                asm volatile("" : "+a"(accs[t]));
+                            }
+                            if constexpr (tile == 0 && OPF && kk + 1 < 16) {
+                                // (behind the k-quad's first matrix instruction: in its shadow) the next k-quad's first
+                                // matrix instruction sits in a later piece
+                                static_assert(((long)(kk + 1) * NT * G) / NM > g, "operand prefetch needs a piece boundary");
+                                fetch_operands<T, kk + 1>(xaddr, raw);
+                                if constexpr (STRIP) fetch_operand<kk + 1>(xsaddr, raws);
+                            }
+                        });
+                    }
                 }
                 SMCMC_PROF_PIECE(PROF_PIECE_MATRIX, g);
                 __builtin_amdgcn_sched_barrier(0);

@@ -1,0 +1,299 @@
+// smcmc_step_deal.h -- the compile-time geometry of the step kernel (tiles of the moment fold, LDS layout of the
+// decomposition, the pieces of a step) and the plan that deals the fold's matrix instructions over the pieces.
+//
+// Plain C++17, no HIP: smcmc_kernels.hip.h includes it, and so does a host program (tests/cpp/step_deal_plan.C) that
+// prints the plan and lets a test check its invariants.
+#pragma once
+
+namespace smcmc {
+
+constexpr int kPiece = 16;   // columns of U consumed per scheduling region (8 x ds_read_b128)
+
+template <int DP>
+struct Geo {
+    static constexpr int T = (DP + 1 + 15) / 16;   // 16-row tiles covering dims 0..DP-1 plus the ones row DP
+    static constexpr int NT = T * (T + 1) / 2;     // lower-triangular tiles
+    static constexpr int NB = (DP + 3) / 4;        // Philox blocks of 4 normals
+    static constexpr int ROWS_MOMENTS = DP + 1;    // LDS rows of x: the dims and the ones row (zero rows are synthesized)
+    // When at most 4 rows spill into the last 16-row tile (D = 50: rows 48, 49 and the ones row), that tile
+    // row is folded with v_mfma_f64_4x4x4_4b_f64 instead (a quarter of the matrix-pipe time): its four
+    // 4x4 blocks are (strip rows) x (columns 16 t + 4 blk ..), which lands exactly where register 0 of
+    // tile (T-1, t) of the 16x16 scheme would, so the stored layout does not change.
+    static constexpr bool STRIP = ((DP + 1) % 16 != 0) && ((DP + 1) % 16 <= 4);
+    static constexpr int T16 = STRIP ? T - 1 : T;  // tile rows folded with 16x16x4
+    static constexpr int NT16 = T16 * (T16 + 1) / 2;
+};
+
+// LDS image of the decomposition: row i keeps columns j0(i)..DP-1 (j0 = i rounded
+// down to even for the triangular factor, 0 for a full matrix), padded to an even
+// length so that every row starts 16-byte aligned (ds_read_b128 = two columns).
+template <int DP, bool FULLU>
+struct ULayout {
+    static constexpr int DPE = DP + (DP & 1);       // DP rounded up to even
+    static constexpr int j0(int i) { return FULLU ? 0 : (i & ~1); }
+    static constexpr int len(int i) { return DPE - j0(i); }
+    // closed form of sum_{r<i} len(r) (no loop: must fold once the caller's loops unroll)
+    static constexpr int off(int i) {
+        return FULLU ? i * DPE
+                     : i * DPE - ((i & 1) ? 2 * (i / 2) * (i / 2) : 2 * (i / 2) * (i / 2 - 1));
+    }
+    static constexpr int SIZE = off(DP);
+};
+
+// The pieces (row, first column) that the rows of Philox block B contribute, in
+// the order they are consumed.
+template <int DP, bool FULLU, int B>
+struct UPieces {
+    typedef ULayout<DP, FULLU> UL;
+    static constexpr int rows() { return (4 * B + 4 <= DP) ? 4 : (DP - 4 * B); }
+    static constexpr int per_row(int i) { return (UL::len(i) + kPiece - 1) / kPiece; }
+    static constexpr int count() {
+        int n = 0;
+        for (int q = 0; q < rows(); ++q) n += per_row(4 * B + q);
+        return n;
+    }
+    static constexpr int COUNT = count();
+    // pieces of the blocks before B (all rows < 4B)
+    static constexpr int first_global() {
+        int n = 0;
+        for (int i = 0; i < 4 * B; ++i) n += per_row(i);
+        return n;
+    }
+    static constexpr int row(int r) {
+        int i = 4 * B;
+        while (r >= per_row(i)) { r -= per_row(i); ++i; }
+        return i;
+    }
+    static constexpr int col(int r) {
+        int i = 4 * B;
+        while (r >= per_row(i)) { r -= per_row(i); ++i; }
+        return UL::j0(i) + r * kPiece;
+    }
+};
+
+// LDS reads load_piece issues for the piece at column c
+template <int DP, bool FULLU, int c>
+constexpr int piece_reads() {
+    int n = 0;
+    for (int k = 0; k < kPiece / 2; ++k) n += (c + 2 * k < ULayout<DP, FULLU>::DPE) ? 1 : 0;
+    return n;
+}
+
+// row ti of lower-triangular tile number `tile` (tile = ti (ti + 1) / 2 + tj, tj <= ti)
+constexpr int tile_row(int tile) {
+    int ti = 0;
+    while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
+    return ti;
+}
+
+// ---- The deal of the fold's matrix instructions over the pieces of a step (triangular decomposition) ----
+//
+// A step has G pieces; behind the vector work of piece g is slot g, where matrix instructions of the moment fold issue.
+// An FP64 matrix instruction holds the vector pipe (64 cycles for 16x16x4, 16 for the strip's 4x4x4) but not the issue of
+// LDS reads, waits and scalar instructions: the non-vector instructions that follow a slot -- the operand prefetch of the
+// next k-quad where the slot carries it, the next piece's reads and their wait -- issue in the shadow of the slot's
+// LAST matrix instruction, four cycles each.  The model's score of a deal is
+//     sum over instructions of min(4 x (non-vector instructions right behind it), duration - 4),
+// and the plan maximises it under what the single-buffered operands (ma[], ms, raw[]) demand:
+//   * k-quads in ascending order, all instructions of one before the operand preparation of the next (so every
+//     accumulator tile sees ascending k: the sums keep their order and their bits);
+//   * the first instruction of a k-quad is a 16x16, the prefetch of the next k-quad's operands goes to the end of that
+//     slot, and the next k-quad starts in a later slot (a piece_ready lies between the prefetch and its use);
+//   * at most one 16x16 per slot; strip instructions stand in front of it, or alone in a slot that gets no 16x16.
+// Which slots get no 16x16 (there are G - 16 NT16 of them) is chosen by dynamic programming over the slots; the score of
+// a 16x16 there is what the following piece's reads are worth, so the short pieces' boundaries go to the strip.
+template <int DP>
+struct StepDeal {
+    typedef ULayout<DP, false> UL;
+    static constexpr int NQ = 16;                          // k-quads: 64 chains, four per matrix instruction
+    static constexpr int T = Geo<DP>::T;
+    static constexpr int NT = Geo<DP>::NT;
+    static constexpr int NT16 = Geo<DP>::STRIP ? Geo<DP>::NT16 : NT;
+    static constexpr int NS = NT - NT16;                   // strip instructions per k-quad
+    static constexpr int NM = NQ * NT;
+    static constexpr int PREFETCH = T + (NS > 0 ? 1 : 0);  // LDS reads of one operand prefetch
+    static constexpr int CYC16 = 64, CYCS = 16, ISSUE = 4; // cycles: 16x16x4, 4x4x4 4-block, one issue slot
+    static constexpr int pieces() {
+        int n = 0;
+        for (int i = 0; i < DP; ++i) n += (UL::len(i) + kPiece - 1) / kPiece;
+        return n;
+    }
+    static constexpr int G = pieces();
+    static constexpr int SPARE = G - NQ * NT16;            // slots without a 16x16
+
+    struct Plan {
+        int first[G + 1];      // slot g issues instructions first[g] .. first[g + 1] - 1 of the sequence, in this order
+        int kk[NM], tile[NM];  // the sequence: k-quad and accumulator tile (tile >= NT16: strip instruction tile - NT16)
+        bool pf_after[NM];     // the operand prefetch of k-quad kk + 1 is issued right behind this instruction
+        int fill[G];           // non-vector instructions behind slot g without a prefetch: LDS reads and one wait
+        int score;
+    };
+
+    // Piece g + 1 opens with the reads of piece g + 2 and the wait for its own (the step loop of smcmc_kernels.hip.h); the
+    // last piece of a Philox block opens with its wait alone, and behind it the next block starts with the reads of its
+    // first piece and the wait for the normals' tables.
+    static constexpr void fills(Plan& p) {
+        int reads[G] = {};
+        bool closes[G] = {};   // the last piece of its block
+        int g = 0;
+        for (int i = 0; i < DP; ++i) {
+            for (int c = UL::j0(i); c < UL::DPE; c += kPiece, ++g) {
+                for (int k = 0; k < kPiece / 2; ++k) reads[g] += (c + 2 * k < UL::DPE) ? 1 : 0;   // piece_reads<DP, false, c>()
+                closes[g] = (c + kPiece >= UL::DPE) && (i % 4 == 3 || i + 1 == DP);
+            }
+        }
+        for (g = 0; g < G; ++g) {
+            if (g + 1 == G) p.fill[g] = 0;   // behind the last piece the step goes on with vector work
+            else if (closes[g]) p.fill[g] = reads[g + 1] + 1;
+            else if (closes[g + 1]) p.fill[g] = 1;
+            else p.fill[g] = reads[g + 2] + 1;
+        }
+    }
+    static constexpr int duration(int tile) { return tile < NT16 ? CYC16 : CYCS; }
+    static constexpr int shadow(int nonvector, int tile) {
+        const int a = ISSUE * nonvector, b = duration(tile) - ISSUE;
+        return a < b ? a : b;
+    }
+    static constexpr void score(Plan& p) {
+        p.score = 0;
+        for (int g = 0; g < G; ++g) {
+            for (int m = p.first[g]; m < p.first[g + 1]; ++m) {
+                const int behind = (p.pf_after[m] ? PREFETCH : 0) + (m + 1 == p.first[g + 1] ? p.fill[g] : 0);
+                p.score += shadow(behind, p.tile[m]);
+            }
+        }
+    }
+
+    // the deal the kernels without a plan keep: instruction m = kk NT + tile goes to piece m G / NM, prefetch behind tile 0
+    static constexpr Plan make_uniform() {
+        Plan p = {};
+        fills(p);
+        for (int g = 0; g <= G; ++g) p.first[g] = (int)(((long)g * NM) / G);
+        for (int m = 0; m < NM; ++m) {
+            p.kk[m] = m / NT;
+            p.tile[m] = m % NT;
+            p.pf_after[m] = (m % NT == 0) && (m / NT + 1 < NQ);
+        }
+        score(p);
+        return p;
+    }
+
+    static constexpr Plan make() {
+        static_assert(SPARE >= 0, "a 16x16 instruction per slot needs as many slots");
+        static_assert(NS == 0 || NT16 >= 2, "strip instructions stand in front of a k-quad's later 16x16");
+        Plan p = {};
+        fills(p);
+        // best[k][u]: the best score of the slots so far with k of them left without a 16x16 and u strip instructions of
+        // the current k-quad standing alone in such slots.  what[g][k][u]: 0 = slot g gets a 16x16, 1 = a strip
+        // instruction alone, 2 = nothing, as the step INTO that state.
+        constexpr int K = SPARE + 1, U = NS + 1;
+        int best[K][U] = {}, next[K][U] = {};
+        signed char what[G][K][U] = {};
+        for (int k = 0; k < K; ++k) for (int u = 0; u < U; ++u) best[k][u] = -1;
+        best[0][0] = 0;
+        for (int g = 0; g < G; ++g) {
+            for (int k = 0; k < K; ++k) for (int u = 0; u < U; ++u) next[k][u] = -1;
+            for (int k = 0; k < K; ++k) {
+                for (int u = 0; u < U; ++u) {
+                    if (best[k][u] < 0 || k > g) continue;
+                    const int n16 = g - k;   // 16x16 instructions issued in the slots before g
+                    if (n16 < NQ * NT16) {
+                        const bool opens = n16 % NT16 == 0;
+                        const bool carries = opens && n16 / NT16 + 1 < NQ;
+                        const int v = best[k][u] + shadow(p.fill[g] + (carries ? PREFETCH : 0), 0);
+                        const int u1 = opens ? 0 : u;
+                        if (v > next[k][u1]) { next[k][u1] = v; what[g][k][u1] = (signed char)(0 + 4 * u); }
+                    }
+                    if (k + 1 < K) {
+                        if (n16 > 0 && u < NS) {
+                            const int v = best[k][u] + shadow(p.fill[g], NT16);
+                            if (v > next[k + 1][u + 1]) { next[k + 1][u + 1] = v; what[g][k + 1][u + 1] = (signed char)(1 + 4 * u); }
+                        }
+                        if (best[k][u] > next[k + 1][u]) { next[k + 1][u] = best[k][u]; what[g][k + 1][u] = (signed char)(2 + 4 * u); }
+                    }
+                }
+            }
+            for (int k = 0; k < K; ++k) for (int u = 0; u < U; ++u) best[k][u] = next[k][u];
+        }
+        // walk back from the best end state (all 16x16 issued: k = SPARE)
+        int choice[G] = {};
+        {
+            int k = SPARE, u = 0;
+            for (int v = 0; v < U; ++v) if (best[k][v] > best[k][u]) u = v;
+            for (int g = G - 1; g >= 0; --g) {
+                const int w = what[g][k][u];
+                choice[g] = w % 4;
+                const int u0 = w / 4;
+                if (choice[g] != 0) --k;
+                u = u0;
+            }
+        }
+        // the sequence: per k-quad its 16x16 in tile order, one per chosen slot; its strip instructions in order: those
+        // that stand alone where the walk put them, the rest one each in front of the k-quad's second, third, ... 16x16
+        // (the last 16x16 takes what remains)
+        int alone[NQ] = {};
+        for (int g = 0, n = 0; g < G; ++g) {
+            if (choice[g] == 0) ++n;
+            else if (choice[g] == 1) ++alone[(n - 1) / NT16];
+        }
+        int m = 0, n16 = 0, strips = 0, front = 0;   // strips, front: strip instructions of the current k-quad so far
+        for (int g = 0; g < G; ++g) {
+            p.first[g] = m;
+            if (choice[g] == 2) continue;
+            if (choice[g] == 1) {
+                p.kk[m] = (n16 - 1) / NT16; p.tile[m] = NT16 + strips; ++m; ++strips;
+                continue;
+            }
+            const int kq = n16 / NT16, t16 = n16 % NT16;
+            if (t16 == 0) { strips = 0; front = 0; }
+            else {
+                int give = NS - alone[kq] - front;
+                if (t16 + 1 < NT16 && give > 1) give = 1;
+                for (int q = 0; q < give; ++q) { p.kk[m] = kq; p.tile[m] = NT16 + strips; ++m; ++strips; ++front; }
+            }
+            p.kk[m] = kq; p.tile[m] = t16; ++m;
+            ++n16;
+        }
+        p.first[G] = m;
+        // the prefetch of k-quad kk + 1: behind the last instruction of the slot that opens k-quad kk
+        for (int g = 0; g < G; ++g) {
+            for (int q = p.first[g]; q < p.first[g + 1]; ++q) {
+                if (q % NT == 0 && p.kk[q] + 1 < NQ) p.pf_after[p.first[g + 1] - 1] = true;
+            }
+        }
+        score(p);
+        return p;
+    }
+
+    // what the kernel relies on (the host test checks the same on the printed plan)
+    static constexpr bool valid(const Plan& p) {
+        if (p.first[0] != 0 || p.first[G] != NM) return false;
+        int pf_slot[NQ] = {};                    // slot of the prefetch of k-quad kk's operands (kk >= 1)
+        for (int kk = 0; kk < NQ; ++kk) pf_slot[kk] = -1;
+        for (int g = 0; g < G; ++g) {
+            if (p.first[g + 1] < p.first[g]) return false;
+            for (int m = p.first[g]; m < p.first[g + 1]; ++m) {
+                // k-quads ascending, each complete before the next opens; every tile once per k-quad
+                if (p.kk[m] != m / NT || p.tile[m] < 0 || p.tile[m] >= NT) return false;
+                for (int q = (m / NT) * NT; q < m; ++q) if (p.tile[q] == p.tile[m]) return false;
+                // the operands a k-quad opens with were fetched in an earlier slot: a piece_ready since
+                if (m % NT == 0 && m > 0 && !(pf_slot[m / NT] >= 0 && pf_slot[m / NT] < g)) return false;
+                if (p.pf_after[m]) {
+                    // once per k-quad, behind its first instruction and in that instruction's slot
+                    if (p.kk[m] + 1 >= NQ || pf_slot[p.kk[m] + 1] >= 0 || p.kk[m] * NT < p.first[g]) return false;
+                    pf_slot[p.kk[m] + 1] = g;
+                }
+            }
+        }
+        for (int kk = 1; kk < NQ; ++kk) if (pf_slot[kk] < 0) return false;
+        return true;
+    }
+};
+
+// the plan of the headline kernels and the deal every other kernel keeps, scored by the same model
+template <int DP>
+inline constexpr typename StepDeal<DP>::Plan kStepDealPlan = StepDeal<DP>::make();
+template <int DP>
+inline constexpr typename StepDeal<DP>::Plan kStepDealUniform = StepDeal<DP>::make_uniform();
+
+}  // namespace smcmc

@@ -6,7 +6,7 @@
 set -e
 R=$(cd "$(dirname "$0")/../.." && pwd); B=$R/root-simple-mcmc_amd/build; P=$B/prof
 mkdir -p $P
-OBJS=$(ls $B/*.o | grep -v -e '_frozen_definition\.o$' -e '_user\.o$' -e '/user_large' -e '/inst_dp50_l0\.o$' -e '/inst_dp[0-9]*_l3\.o$')
+OBJS=$(ls $B/*.o | grep -v -e '_frozen_definition\.o$' -e '_user\.o$' -e '_user_grad\.o$' -e '/user_large' -e '/inst_dp50_l0\.o$' -e '/inst_dp[0-9]*_l3\.o$')
 for L in ${1:-1 2}; do
     rm -rf $P/tmp$L; mkdir -p $P/tmp$L
     /opt/rocm/bin/hipcc -std=c++17 -O3 -fPIC -ffp-contract=off --offload-arch=gfx950 -fno-gpu-rdc -Wall -Wno-unused-function \
