@@ -532,6 +532,50 @@ int smcmc_vaat_read_lane_i32(smcmc_vaat* h, int field, int32_t* out);
 int smcmc_vaat_read_dim_f64(smcmc_vaat* h, int field, double* out);
 int smcmc_vaat_read_dim_i32(smcmc_vaat* h, int field, int32_t* out);
 int smcmc_vaat_state_device_ptr(smcmc_vaat* h, double** x, double** logl);
+/* smcmc_vaat_step(h, nsteps) for every chain, in one launch, with a per-step record of one chain in the HOST array
+ * records[step * smcmc_vaat_record_stride()]: the caller's loop around TSimpleMCMC::Step() (SimpleVAAT.C:47-61) without
+ * the host in every step.  A step changes ONE coordinate (TProposeVAATStep.H:58-78) and adapts ONE dimension's width
+ * (:237-254), so a row is SMCMC_VAAT_REC_COUNT_ scalars whatever the dimension is, and a reader rebuilds the chain from
+ * the state at the start of the call plus the rows: x[INDEX] = ACCEPTED_VALUE and nothing else moves; fSigma /
+ * fAcceptance / fAcceptanceTrials [ADAPT_INDEX] = ADAPT_* and no other entry changes.  The row after a step holds what
+ * the engine would read back after that step:
+ *   LOGL, LOGL_PROPOSED, STEP_RMS                  the lanes of the same names (TSimpleMCMC.H:568, 589, 580)
+ *   LAST_ACCEPT, TRIALS, SUCCESSES, NACCEPT, STEP_RMS_TRIALS   the integer lanes, as doubles
+ *   INDEX                                          fLastIndex, the coordinate this step proposed (:58)
+ *   PROPOSED_VALUE                                 fProposed[INDEX] (:62, 77)
+ *   ACCEPTED_VALUE                                 fAccepted[INDEX] after the Metropolis test (TSimpleMCMC.H:432-491): the
+ *                                                  old value on a rejection
+ *   ADAPT_INDEX                                    the dimension whose width UpdateState adapted at the top of this step
+ *                                                  (:237-254: the previous step's index), -1 when there was none
+ *                                                  (fLastIndex < 0 after Start or the explicit UpdateProposal, :183, 235)
+ *   ADAPT_SIGMA, ADAPT_ACCEPTANCE, ADAPT_TRIALS    that dimension's fSigma / fAcceptance / fAcceptanceTrials after the
+ *                                                  update, written whether or not the width moved; +0 when ADAPT_INDEX is -1
+ *   TOTAL_STEPS, QUEUE_LENGTH                      fTotalSteps (TSimpleMCMC.H:376) and the entries left in fNextIndex
+ * In both arithmetic orders, for every likelihood id the library serves and both kernels (dim <= smcmc_max_dim()), any
+ * number of chains.  The lane that owns the chain writes its row from inside the step kernel (instantiations of their
+ * own: smcmc_vaat_step runs the code it ran before); one copy to the host ends the call.  Calls may be cut anywhere:
+ * step_recorded(a) then step_recorded(b) gives the rows of step_recorded(a + b).  SMCMC_ERR_INVALID, with nothing
+ * launched and nothing written: NULL handle, not started, records NULL, nsteps < 1, chain outside [0, nchains). */
+typedef enum {
+    SMCMC_VAAT_REC_LOGL = 0, SMCMC_VAAT_REC_LOGL_PROPOSED, SMCMC_VAAT_REC_STEP_RMS, SMCMC_VAAT_REC_LAST_ACCEPT,
+    SMCMC_VAAT_REC_TRIALS, SMCMC_VAAT_REC_SUCCESSES, SMCMC_VAAT_REC_NACCEPT, SMCMC_VAAT_REC_STEP_RMS_TRIALS,
+    SMCMC_VAAT_REC_INDEX, SMCMC_VAAT_REC_PROPOSED_VALUE, SMCMC_VAAT_REC_ACCEPTED_VALUE, SMCMC_VAAT_REC_ADAPT_INDEX,
+    SMCMC_VAAT_REC_ADAPT_SIGMA, SMCMC_VAAT_REC_ADAPT_ACCEPTANCE, SMCMC_VAAT_REC_ADAPT_TRIALS, SMCMC_VAAT_REC_TOTAL_STEPS,
+    SMCMC_VAAT_REC_QUEUE_LENGTH,
+    SMCMC_VAAT_REC_COUNT_
+} smcmc_vaat_record_field;
+int smcmc_vaat_record_stride(const smcmc_vaat* h);    /* SMCMC_VAAT_REC_COUNT_, independent of dim; 0 for NULL */
+int smcmc_vaat_step_recorded(smcmc_vaat* h, int nsteps, int chain, double* records);
+/* The contract of smcmc_snapshot / smcmc_rollback for a started variable-at-a-time ensemble: the snapshot holds device
+ * copies of the whole state -- the points, both lane tables, every chain's fSigma / fAcceptance / fAcceptanceTrials and
+ * index queue -- plus the step count, the queue length and the started / initialised flags; rollback returns to it any
+ * number of times.  Draws are keyed on (chain, step), so stepping again repeats the same steps.  Settings -- proposal
+ * types, acceptance window and rigidity, StepRMS window, likelihood parameters -- are not part of the snapshot and stay
+ * as they are at a rollback.  The copies are a second ensemble on the device, freed by smcmc_vaat_destroy: when they do
+ * not fit, smcmc_vaat_snapshot is SMCMC_ERR_HIP, keeps nothing and leaves the engine as it was.  Not started
+ * SMCMC_ERR_INVALID; a rollback without a snapshot SMCMC_ERR_LOGIC. */
+int smcmc_vaat_snapshot(smcmc_vaat* h);
+int smcmc_vaat_rollback(smcmc_vaat* h);
 
 /* ---- self test (no engine needed) --------------------------------------- */
 /* Runs every function of include/smcmc_detmath.h on the device for n inputs so

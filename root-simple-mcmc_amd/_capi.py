@@ -40,6 +40,10 @@ VAAT_LANE_I32 = dict(LANE_I32, last_index=LANE_I32["next_update"])
 VAAT_LANE_F64 = dict(LANE_F64, proposed_value=LANE_F64["last_x0"])
 VAAT_DIM_F64 = {"sigma": 0, "acceptance": 1}
 VAAT_DIM_I32 = {"acceptance_trials": 2, "queue": 3}
+# smcmc_vaat_record_field: a row of smcmc_vaat_step_recorded, whatever the dimension
+VAAT_RECORD_FIELDS = ["logl", "logl_proposed", "step_rms", "last_accept", "trials", "successes", "naccept",
+                      "step_rms_trials", "index", "proposed_value", "accepted_value", "adapt_index", "adapt_sigma",
+                      "adapt_acceptance", "adapt_trials", "total_steps", "queue_length"]
 HMC_TUNING = ["trace", "orbit", "updates", "cov_trials", "average_trials", "steps_remaining", "steps_since_update",
               "max_scale", "min_scale", "est_trace"]
 # smcmc_hmc_record_field: the scalars of a row of smcmc_hmc_step_recorded, after [0, dim) fAccepted and [dim, 2 dim)
@@ -187,6 +191,10 @@ SIGNATURES = {
     "smcmc_vaat_read_dim_f64": (C.c_int, [_H, C.c_int, _dp]),
     "smcmc_vaat_read_dim_i32": (C.c_int, [_H, C.c_int, _ip]),
     "smcmc_vaat_state_device_ptr": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "smcmc_vaat_record_stride": (C.c_int, [_H]),
+    "smcmc_vaat_step_recorded": (C.c_int, [_H, C.c_int, C.c_int, _dp]),
+    "smcmc_vaat_snapshot": (C.c_int, [_H]),
+    "smcmc_vaat_rollback": (C.c_int, [_H]),
     "smcmc_selftest_detmath": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]),
     "smcmc_selftest_mfma": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp]),
     "smcmc_selftest_mfma_strip": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp]),

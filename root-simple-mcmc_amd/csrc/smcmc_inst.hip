@@ -37,6 +37,11 @@ hipError_t launch_step_like<SMCMC_DP, SMCMC_LIKE>(const StepParams& p, bool exac
 template <>
 hipError_t launch_vaat_like<SMCMC_DP, SMCMC_LIKE>(const VaatParams& p, bool exact, hipStream_t s) {
     constexpr int DP = SMCMC_DP, LIKE = SMCMC_LIKE;
+    if (p.record != nullptr) {   // smcmc_vaat_step_recorded: the instantiations that write a row per step
+        if (exact) hipLaunchKernelGGL(HIP_KERNEL_NAME(vaat_step_kernel<DP, LIKE, true, true>), dim3(p.npad / kWave), dim3(kWave), 0, s, p);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(vaat_step_kernel<DP, LIKE, false, true>), dim3(p.npad / kWave), dim3(kWave), 0, s, p);
+        return hipGetLastError();
+    }
     if (exact) hipLaunchKernelGGL(HIP_KERNEL_NAME(vaat_step_kernel<DP, LIKE, true>), dim3(p.npad / kWave), dim3(kWave), 0, s, p);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(vaat_step_kernel<DP, LIKE, false>), dim3(p.npad / kWave), dim3(kWave), 0, s, p);
     return hipGetLastError();

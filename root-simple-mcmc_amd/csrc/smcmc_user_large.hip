@@ -34,6 +34,11 @@ hipError_t launch_start_loglike_user(const double* x, int nchains, size_t npad, 
 }
 
 hipError_t launch_vaat_large_user(const VaatParams& p, bool exact, hipStream_t s) {
+    if (p.record != nullptr) {   // smcmc_vaat_step_recorded
+        if (exact) hipLaunchKernelGGL(HIP_KERNEL_NAME(vaat_large_kernel<SMCMC_LIKE_USER, true, true>), dim3(p.npad / kWave), dim3(kWave), 0, s, p);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(vaat_large_kernel<SMCMC_LIKE_USER, false, true>), dim3(p.npad / kWave), dim3(kWave), 0, s, p);
+        return hipGetLastError();
+    }
     if (exact) hipLaunchKernelGGL(HIP_KERNEL_NAME(vaat_large_kernel<SMCMC_LIKE_USER, true>), dim3(p.npad / kWave), dim3(kWave), 0, s, p);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(vaat_large_kernel<SMCMC_LIKE_USER, false>), dim3(p.npad / kWave), dim3(kWave), 0, s, p);
     return hipGetLastError();

@@ -37,6 +37,14 @@ struct smcmc_vaat {
     DeviceBuffer<double> d_x, d_like, d_lane_f64, d_sigma, d_acceptance, d_param1, d_param2;
     DeviceBuffer<int32_t> d_lane_i32, d_acc_trials, d_ptype;
     DeviceBuffer<uint16_t> d_queue;
+    DeviceBuffer<double> d_rec;    // smcmc_vaat_step_recorded: one row per step of the call, written by the step kernel
+    // smcmc_vaat_snapshot / smcmc_vaat_rollback: a copy of the ensemble's state on the device
+    DeviceBuffer<double> snap_x, snap_lane_f64, snap_sigma, snap_acceptance;
+    DeviceBuffer<int32_t> snap_lane_i32, snap_acc_trials;
+    DeviceBuffer<uint16_t> snap_queue;
+    uint32_t snap_total_steps = 0;
+    int snap_queue_len = 0;
+    bool snap_started = false, snap_initialized = false, snap_valid = false;
     std::string error;
 };
 
@@ -97,6 +105,30 @@ int vaat_upload_like(smcmc_vaat* h) {
     HIP_TRY(h, hipMemcpyAsync(h->d_like, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SMCMC_OK;
+}
+
+// the arrays of a snapshot: the engine's buffer, the copy, its size in bytes
+struct VaatSnapArray { void* live; void* copy; size_t bytes; };
+template <typename T>
+hipError_t vaat_snap_fit(DeviceBuffer<T>& copy, const DeviceBuffer<T>& live) {
+    return copy.size() == live.size() ? hipSuccess : copy.allocate(live.size());
+}
+void vaat_snap_drop(smcmc_vaat* h) {
+    h->snap_x = DeviceBuffer<double>(); h->snap_lane_f64 = DeviceBuffer<double>();
+    h->snap_sigma = DeviceBuffer<double>(); h->snap_acceptance = DeviceBuffer<double>();
+    h->snap_lane_i32 = DeviceBuffer<int32_t>(); h->snap_acc_trials = DeviceBuffer<int32_t>();
+    h->snap_queue = DeviceBuffer<uint16_t>();
+    h->snap_valid = false;
+}
+constexpr int kVaatSnapArrays = 7;
+void vaat_snap_arrays(smcmc_vaat* h, VaatSnapArray* a) {
+    a[0] = {h->d_x.get(), h->snap_x.get(), h->d_x.size() * sizeof(double)};
+    a[1] = {h->d_lane_f64.get(), h->snap_lane_f64.get(), h->d_lane_f64.size() * sizeof(double)};
+    a[2] = {h->d_lane_i32.get(), h->snap_lane_i32.get(), h->d_lane_i32.size() * sizeof(int32_t)};
+    a[3] = {h->d_sigma.get(), h->snap_sigma.get(), h->d_sigma.size() * sizeof(double)};
+    a[4] = {h->d_acceptance.get(), h->snap_acceptance.get(), h->d_acceptance.size() * sizeof(double)};
+    a[5] = {h->d_acc_trials.get(), h->snap_acc_trials.get(), h->d_acc_trials.size() * sizeof(int32_t)};
+    a[6] = {h->d_queue.get(), h->snap_queue.get(), h->d_queue.size() * sizeof(uint16_t)};
 }
 
 }  // namespace
@@ -302,6 +334,75 @@ int smcmc_vaat_step_save(smcmc_vaat* h, int nsteps, int stride, double* save_x_d
 }
 
 int smcmc_vaat_step(smcmc_vaat* h, int nsteps) { return smcmc_vaat_step_save(h, nsteps, 1, nullptr, nullptr); }
+
+int smcmc_vaat_record_stride(const smcmc_vaat* h) { return h ? (int)SMCMC_VAAT_REC_COUNT_ : 0; }
+
+int smcmc_vaat_step_recorded(smcmc_vaat* h, int nsteps, int chain, double* records) {
+    if (!h) return SMCMC_ERR_INVALID;
+    if (!h->started) return fail(h, SMCMC_ERR_INVALID, "Must initialize starting point");   // TSimpleMCMC.H:371-374
+    if (!records) return fail(h, SMCMC_ERR_INVALID, "smcmc_vaat_step_recorded: no record array");
+    if (nsteps < 1) return fail(h, SMCMC_ERR_INVALID, "smcmc_vaat_step_recorded: nsteps >= 1");
+    if (chain < 0 || chain >= h->nchains) return fail(h, SMCMC_ERR_INVALID, "no such chain");
+    ON_DEVICE(h);
+    const size_t need = (size_t)nsteps * SMCMC_VAAT_REC_COUNT_;
+    if (need > h->d_rec.size()) HIP_TRY(h, h->d_rec.allocate(need));
+    VaatParams p = vaat_params(h, nsteps);
+    p.record = h->d_rec; p.record_chain = chain;
+    hipError_t e = vaat_dispatch(h, p);
+    if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("recorded step launch: ") + hipGetErrorString(e));
+    h->total_steps += (uint32_t)nsteps;
+    const int D = h->dim;
+    h->queue_len = ((h->queue_len - nsteps) % D + D) % D;     // as smcmc_vaat_step_save
+    HIP_TRY(h, hipMemcpyAsync(records, h->d_rec, need * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SMCMC_OK;
+}
+
+int smcmc_vaat_snapshot(smcmc_vaat* h) {
+    if (!h) return SMCMC_ERR_INVALID;
+    if (!h->started) return fail(h, SMCMC_ERR_INVALID, "Must initialize starting point");
+    ON_DEVICE(h);
+    hipError_t e = vaat_snap_fit(h->snap_x, h->d_x);
+    if (e == hipSuccess) e = vaat_snap_fit(h->snap_lane_f64, h->d_lane_f64);
+    if (e == hipSuccess) e = vaat_snap_fit(h->snap_lane_i32, h->d_lane_i32);
+    if (e == hipSuccess) e = vaat_snap_fit(h->snap_sigma, h->d_sigma);
+    if (e == hipSuccess) e = vaat_snap_fit(h->snap_acceptance, h->d_acceptance);
+    if (e == hipSuccess) e = vaat_snap_fit(h->snap_acc_trials, h->d_acc_trials);
+    if (e == hipSuccess) e = vaat_snap_fit(h->snap_queue, h->d_queue);
+    if (e != hipSuccess) {
+        // a second copy of the ensemble does not fit: nothing is kept, and the engine steps on as it was
+        vaat_snap_drop(h);
+        (void)hipGetLastError();
+        return fail(h, SMCMC_ERR_HIP, std::string("the snapshot does not fit in device memory: ") + hipGetErrorString(e));
+    }
+    h->snap_valid = false;
+    VaatSnapArray a[kVaatSnapArrays];
+    vaat_snap_arrays(h, a);
+    for (int k = 0; k < kVaatSnapArrays; ++k)
+        HIP_TRY(h, hipMemcpyAsync(a[k].copy, a[k].live, a[k].bytes, hipMemcpyDeviceToDevice, h->stream));
+    h->snap_total_steps = h->total_steps;
+    h->snap_queue_len = h->queue_len;
+    h->snap_started = h->started;
+    h->snap_initialized = h->initialized;
+    h->snap_valid = true;
+    return SMCMC_OK;
+}
+
+int smcmc_vaat_rollback(smcmc_vaat* h) {
+    if (!h) return SMCMC_ERR_INVALID;
+    if (!h->started) return fail(h, SMCMC_ERR_INVALID, "Must initialize starting point");
+    if (!h->snap_valid) return fail(h, SMCMC_ERR_LOGIC, "no snapshot to return to");
+    ON_DEVICE(h);
+    VaatSnapArray a[kVaatSnapArrays];
+    vaat_snap_arrays(h, a);
+    for (int k = 0; k < kVaatSnapArrays; ++k)
+        HIP_TRY(h, hipMemcpyAsync(a[k].live, a[k].copy, a[k].bytes, hipMemcpyDeviceToDevice, h->stream));
+    h->total_steps = h->snap_total_steps;
+    h->queue_len = h->snap_queue_len;
+    h->started = h->snap_started;
+    h->initialized = h->snap_initialized;
+    return SMCMC_OK;
+}
 
 int smcmc_vaat_total_steps(const smcmc_vaat* h) { return h ? (int)h->total_steps : -1; }
 int smcmc_vaat_queue_length(const smcmc_vaat* h) { return h ? h->queue_len : -1; }

@@ -16,6 +16,9 @@
 //     the reference calls the whole likelihood too, TSimpleMCMC.H:410).
 // The queue length is the same for every chain (each step pops one index, all chains shuffle in the same steps), so
 // the host carries it and the shuffle is a uniform branch.
+// RECORD (smcmc_vaat_step_recorded): after every step the lane of chain `record_chain` writes one row of
+// SMCMC_VAAT_REC_COUNT_ doubles -- a step moves one coordinate and adapts one dimension's width, so that is the whole
+// step whatever the dimension.  An instantiation of its own: the plain launches run the code they ran before.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -54,6 +57,8 @@ struct VaatParams {
     double* save_x;            // optional [slot][dim][npad]: the accepted point after every save_stride-th step
     double* save_logl;         // optional [slot][npad]
     int save_stride;
+    double* record;            // RECORD kernels: [nsteps][SMCMC_VAAT_REC_COUNT_], the steps of chain record_chain
+    int record_chain;
 };
 
 constexpr int kVaatLaneLastIndex = SMCMC_LANE_NEXT_UPDATE;
@@ -74,6 +79,34 @@ __device__ __forceinline__ void vaat_adapt(int& at, double& acc, double& sg, boo
         v *= (ratio > 0.0) ? smcmc_pow_small(ratio, expo) : 0.0;        // pow(0, y > 0) = 0
         sg = dmax(v, 1.0E-4);                                           // :253
     }
+}
+
+// RECORD: the half of a row that UpdateState decides (the dimension it adapted, or none: fLastIndex < 0, :235)
+__device__ __forceinline__ void vaat_record_adapt(double* row, int index, double sg, double acc, int at) {
+    row[SMCMC_VAAT_REC_ADAPT_INDEX] = (double)index;
+    row[SMCMC_VAAT_REC_ADAPT_SIGMA] = sg;
+    row[SMCMC_VAAT_REC_ADAPT_ACCEPTANCE] = acc;
+    row[SMCMC_VAAT_REC_ADAPT_TRIALS] = (double)at;
+}
+
+// RECORD: the rest of the row, what the engine would read back after the step
+__device__ __forceinline__ void vaat_record_step(double* row, double logl, double logl_proposed, double step_rms,
+                                                 int last_accept, int trials, int successes, int naccept,
+                                                 int step_rms_trials, int index, double proposed_value,
+                                                 double accepted_value, uint64_t total_steps, int qlen) {
+    row[SMCMC_VAAT_REC_LOGL] = logl;
+    row[SMCMC_VAAT_REC_LOGL_PROPOSED] = logl_proposed;
+    row[SMCMC_VAAT_REC_STEP_RMS] = step_rms;
+    row[SMCMC_VAAT_REC_LAST_ACCEPT] = (double)last_accept;
+    row[SMCMC_VAAT_REC_TRIALS] = (double)trials;
+    row[SMCMC_VAAT_REC_SUCCESSES] = (double)successes;
+    row[SMCMC_VAAT_REC_NACCEPT] = (double)naccept;
+    row[SMCMC_VAAT_REC_STEP_RMS_TRIALS] = (double)step_rms_trials;
+    row[SMCMC_VAAT_REC_INDEX] = (double)index;
+    row[SMCMC_VAAT_REC_PROPOSED_VALUE] = proposed_value;
+    row[SMCMC_VAAT_REC_ACCEPTED_VALUE] = accepted_value;
+    row[SMCMC_VAAT_REC_TOTAL_STEPS] = (double)total_steps;
+    row[SMCMC_VAAT_REC_QUEUE_LENGTH] = (double)qlen;
 }
 
 // the proposed value of coordinate idx (TProposeVAATStep.H:60-78)
@@ -118,7 +151,7 @@ __device__ __forceinline__ bool vaat_accepts(double lp, double value, uint32_t a
     return true;
 }
 
-template <int DP, int LIKE, bool EXACT>
+template <int DP, int LIKE, bool EXACT, bool RECORD = false>
 __global__ void __launch_bounds__(kWave) vaat_step_kernel(const VaatParams p) {
     __shared__ double s_sigma[DP * kWave];
     __shared__ double s_acc[DP * kWave];
@@ -197,9 +230,11 @@ __global__ void __launch_bounds__(kWave) vaat_step_kernel(const VaatParams p) {
     int step_rms_trials = li[SMCMC_LANE_STEP_RMS_TRIALS * NP];
     int last_accept = li[SMCMC_LANE_LAST_ACCEPT * NP];
     int last_index = li[kVaatLaneLastIndex * NP];
+    const bool recorded = RECORD && active && chain == p.record_chain;   // one lane of one wavefront
 
     for (int s = 0; s < p.nsteps; ++s) {
         const uint64_t step = (uint64_t)(p.step0 + (uint32_t)s + 1u);   // ++fTotalSteps, TSimpleMCMC.H:376
+        double* row = RECORD ? p.record + (size_t)s * SMCMC_VAAT_REC_COUNT_ : nullptr;
         // ---- UpdateState (:219-255) ----
         ++trials;
         const bool accepted = (logl != last_value);                     // :225-226
@@ -211,6 +246,9 @@ __global__ void __launch_bounds__(kWave) vaat_step_kernel(const VaatParams p) {
             double acc = s_acc[k], sg = s_sigma[k];
             vaat_adapt(at, acc, sg, accepted, p.acc_window, p.rigidity, p.target);
             s_at[k] = at; s_acc[k] = acc; s_sigma[k] = sg;
+            if constexpr (RECORD) if (recorded) vaat_record_adapt(row, last_index, sg, acc, at);
+        } else {
+            if constexpr (RECORD) if (recorded) vaat_record_adapt(row, -1, 0.0, 0.0, 0);
         }
         // ---- operator() (:52-78) ----
         if (qlen == 0) shuffle(step);                                   // :55
@@ -238,6 +276,15 @@ __global__ void __launch_bounds__(kWave) vaat_step_kernel(const VaatParams p) {
             for (int d = 0; d < DP; ++d) x[d] = (d == idx) ? cur : x[d];
         }
         last_accept = take ? 1 : 0;
+        if constexpr (RECORD) {
+            if (recorded) {
+                double now = 0.0;                                       // fAccepted[idx]: the old value on a rejection
+#pragma unroll
+                for (int d = 0; d < DP; ++d) now = (d == idx) ? x[d] : now;
+                vaat_record_step(row, logl, logl_proposed, step_rms, last_accept, trials, successes, naccept,
+                                 step_rms_trials, idx, proposed_value, now, step, qlen);
+            }
+        }
         if (p.save_x != nullptr && (s + 1) % p.save_stride == 0 && active) {
             const size_t slot = (size_t)((s + 1) / p.save_stride - 1);
 #pragma unroll

@@ -5,6 +5,11 @@ namespace smcmc {
 
 template <int LIKE>
 static hipError_t go_vaat_large(const VaatParams& p, bool exact, hipStream_t s) {
+    if (p.record != nullptr) {   // smcmc_vaat_step_recorded: the instantiations that write a row per step
+        if (exact) hipLaunchKernelGGL(HIP_KERNEL_NAME(vaat_large_kernel<LIKE, true, true>), dim3(p.npad / kWave), dim3(kWave), 0, s, p);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(vaat_large_kernel<LIKE, false, true>), dim3(p.npad / kWave), dim3(kWave), 0, s, p);
+        return hipGetLastError();
+    }
     if (exact) hipLaunchKernelGGL(HIP_KERNEL_NAME(vaat_large_kernel<LIKE, true>), dim3(p.npad / kWave), dim3(kWave), 0, s, p);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(vaat_large_kernel<LIKE, false>), dim3(p.npad / kWave), dim3(kWave), 0, s, p);
     return hipGetLastError();

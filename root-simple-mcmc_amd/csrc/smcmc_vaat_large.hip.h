@@ -7,7 +7,7 @@
 
 namespace smcmc {
 
-template <int LIKE, bool EXACT>
+template <int LIKE, bool EXACT, bool RECORD = false>
 __global__ void __launch_bounds__(kWave) vaat_large_kernel(const VaatParams p) {
     const int lane = threadIdx.x;
     const int chain = blockIdx.x * kWave + lane;
@@ -61,9 +61,11 @@ __global__ void __launch_bounds__(kWave) vaat_large_kernel(const VaatParams p) {
     int step_rms_trials = li[SMCMC_LANE_STEP_RMS_TRIALS * NP];
     int last_accept = li[SMCMC_LANE_LAST_ACCEPT * NP];
     int last_index = li[kVaatLaneLastIndex * NP];
+    const bool recorded = RECORD && active && chain == p.record_chain;   // one lane of one wavefront
 
     for (int s = 0; s < p.nsteps; ++s) {
         const uint64_t step = (uint64_t)(p.step0 + (uint32_t)s + 1u);
+        double* row = RECORD ? p.record + (size_t)s * SMCMC_VAAT_REC_COUNT_ : nullptr;
         ++trials;
         const bool accepted = (logl != last_value);
         if (accepted) ++successes;
@@ -74,6 +76,9 @@ __global__ void __launch_bounds__(kWave) vaat_large_kernel(const VaatParams p) {
             double acc = p.acceptance[k], sg = p.sigma[k];
             vaat_adapt(at, acc, sg, accepted, p.acc_window, p.rigidity, p.target);
             p.acc_trials[k] = at; p.acceptance[k] = acc; p.sigma[k] = sg;
+            if constexpr (RECORD) if (recorded) vaat_record_adapt(row, last_index, sg, acc, at);
+        } else {
+            if constexpr (RECORD) if (recorded) vaat_record_adapt(row, -1, 0.0, 0.0, 0);
         }
         if (qlen == 0) shuffle(step);
         const int idx = q[(size_t)(qlen - 1) * NP];
@@ -97,6 +102,10 @@ __global__ void __launch_bounds__(kWave) vaat_large_kernel(const VaatParams p) {
             *cell = cur;
         }
         last_accept = take ? 1 : 0;
+        if constexpr (RECORD)
+            if (recorded)
+                vaat_record_step(row, logl, logl_proposed, step_rms, last_accept, trials, successes, naccept,
+                                 step_rms_trials, idx, proposed_value, *cell, step, qlen);
         if (p.save_x != nullptr && (s + 1) % p.save_stride == 0 && active) {
             const size_t slot = (size_t)((s + 1) / p.save_stride - 1);
             for (int d = 0; d < D; ++d) p.save_x[(slot * D + d) * NP + chain] = p.x[(size_t)d * NP + chain];

@@ -1377,6 +1377,21 @@ class VaatEngine:
 
     def Step(self, nsteps=1): self._check(self._lib.smcmc_vaat_step(self._h, int(nsteps)))
 
+    def snapshot(self): self._check(self._lib.smcmc_vaat_snapshot(self._h))
+    def rollback(self): self._check(self._lib.smcmc_vaat_rollback(self._h))
+
+    @property
+    def record_stride(self): return self._lib.smcmc_vaat_record_stride(self._h)
+
+    def StepRecorded(self, nsteps, chain=0):
+        """Step(nsteps) of every chain in one launch with the per-step record of one chain (smcmc_vaat_step_recorded):
+        an [nsteps, record_stride] array, a row = the scalars VAAT_RECORD_FIELDS after that step.  A step moves the
+        coordinate `index` to `accepted_value` and adapts the width of dimension `adapt_index` only, so the rows and the
+        state before the call give the chain after every step."""
+        rec = np.zeros((max(int(nsteps), 0), self.record_stride))
+        self._check(self._lib.smcmc_vaat_step_recorded(self._h, int(nsteps), int(chain), _ptr(rec)))
+        return rec
+
     def step_save(self, nsteps, stride, save_x_ptr, save_logl_ptr=None):
         self._check(self._lib.smcmc_vaat_step_save(self._h, int(nsteps), int(stride), C.c_void_p(int(save_x_ptr)),
                                                    C.c_void_p(int(save_logl_ptr)) if save_logl_ptr else None))
