@@ -608,8 +608,14 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     // Coordinate 0 of the accepted point, which UpdateState compares with the step before.  BOUNDARY: carried in a register
     // from commit to commit (read back from LDS at the top of a step it was a read and a full wait behind the commit's
     // writes); otherwise read at the top of every step.
+    // With the moment fold (TOP_FREE) the read is final before the loop (the empty statement uses the value): left in
+    // flight, the compiler's wait for it stood inside the loop, a full `s_waitcnt lgkmcnt(0)` at the top of every step,
+    // right behind the commit's writes -- and the reload of the accepted point goes out at the top of the step (below).
+    // The kernel without the fold measured 0.7 % slower with the two (profiles/step_boundary_notes.md) and keeps its top.
+    constexpr bool TOP_FREE = BOUNDARY && MOMENTS;
     double x0 = 0.0;
     if constexpr (BOUNDARY) x0 = xcol[0];
+    if constexpr (TOP_FREE) asm volatile("" : "+v"(x0));
 
     // StepRMS window, likelihood, Metropolis test and accept copy of one step
     // (TSimpleMCMC.H:391-406, 410-491) for the proposal held in xp.
@@ -763,6 +769,15 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         SMCMC_PROF_MARK(PROF_LOOP);
         SMCMC_PROF_MARK(PROF_STAMP);
 
+        // TOP_FREE: the proposal starts from the accepted point, and its reload goes out here, in front of A: behind the
+        // commit of the step before in program order (one wavefront, LDS operations execute in issue order), so that the
+        // commit's writes and these reads are on their way under A's divisions and `pow`.  Issued behind A they came back
+        // under nothing (the compiler does not lift them over A's branches).
+        if constexpr (TOP_FREE) {
+#pragma unroll
+            for (int d = 0; d < DP; ++d) xp[d] = xcol[d * kXStride];
+        }
+
         // ---- A: UpdateState, scalar half (TSimpleMCMC.H:1723-1776) ----
         ++trials;
         if constexpr (!BOUNDARY) x0 = xcol[0];
@@ -807,8 +822,10 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
             fetch_operands<T, 0>(xaddr, raw);
             if constexpr (STRIP) fetch_operand<0>(xsaddr, raws);
         }
+        if constexpr (!TOP_FREE) {
 #pragma unroll
-        for (int d = 0; d < DP; ++d) xp[d] = xcol[d * kXStride];
+            for (int d = 0; d < DP; ++d) xp[d] = xcol[d * kXStride];
+        }
         uint32_t uword = 0;
         // The LDS image of U never changes, so the compiler would hoist all of its reads out
         // of the step loop and spill them; reading through a pointer it cannot see through
