@@ -1,9 +1,8 @@
 // smcmc_autocorr_grid.hip -- the lagged-product sums of a saved trace on a lag grid k_i = lag_first + i * lag_step:
 // what MakeAutocorrelation.C:98-124 evaluates (lags 1, 1 + lagStep, ... < maxLag, about 200 of them spread over up to
-// 30 000 slots), where smcmc_autocorr.hip covers the 64 consecutive lags 0 .. 63 only.  The inner block is that
-// kernel's: one lane owns one chain of one dimension, a wavefront covers 64 chains and 32 lags (one pass; the passes of
-// a call are grid z), and everything sits in registers with static indices -- 16 loaded values, a sliding window of
-// the 47 values the 32 lags reach back to, 32 accumulators, 512 fused multiply-adds per 16 loaded values, no LDS.
+// 30 000 slots), where smcmc_autocorr.hip covers the 64 consecutive lags 0 .. 63 only.  The inner block is the lagged
+// register block of smcmc_trace_reduce.hip.h, the one that kernel uses: one lane owns one chain of one dimension, a
+// wavefront covers 64 chains and 32 lags (one pass; the passes of a call are grid z).
 // A grid of step S keeps that shape because the slots are walked by residue class: for t = r + a S (0 <= r < S) the
 // partner of lag k0 + i S is y[(r - k0) + (a - i) S], so per residue r the sums are the contiguous-lag recurrence
 //   acc[i] += u[a] * w[a - i],     u[a] = y[r + a S],   w[a] = y[r - k0 + a S]   (0 before the first slot)
@@ -27,13 +26,12 @@
 
 #include "smcmc.h"
 #include "smcmc_host.hpp"
+#include "smcmc_trace_reduce.hip.h"
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kPassLags = 32;                // lags per wavefront
-constexpr int kBlock = 16;                   // decimated slots per register block
-constexpr int kWin = kBlock + kPassLags - 1; // w[a0 - 31 .. a0 + 15]
+// kWave, kPassLags, kBlock (decimated slots here), LaggedBlock: its window is w[a0 - 31 .. a0 + 15]
+using namespace smcmc::reduce;
 
 // partial[cb][d][0 .. nrows - 1] the rows of the grid (nrows = 32 * passes), [nrows] sum, [nrows + 1] sumsq
 __global__ void __launch_bounds__(kWave) autocorr_grid_partial_kernel(const double* __restrict__ trace, int nslots, int dim,
@@ -56,15 +54,13 @@ __global__ void __launch_bounds__(kWave) autocorr_grid_partial_kernel(const doub
     auto y = [&](int64_t t) __attribute__((always_inline)) {
         return (active && t >= 0 && t < nslots) ? src[(size_t)t * slot_stride] - c0 : 0.0;
     };
-    double win[kWin], acc[kPassLags], v[kBlock];
-#pragma unroll
-    for (int k = 0; k < kPassLags; ++k) acc[k] = 0.0;
+    LaggedBlock b;
+    b.clear_sums();
     double sum = 0.0, sumsq = 0.0;
     if (sums || k0 < nslots) {
         const int64_t nres = S < nslots ? S : nslots;
         for (int64_t r = 0; r < nres; ++r) {
-#pragma unroll
-            for (int i = 0; i < kWin; ++i) win[i] = 0.0;
+            b.clear_window();
             // the first a with r - k0 + a S >= 0: before it every partner of every lag of the pass is 0
             int64_t a = 0;
             if (!sums && k0 > r) a = (int64_t)((uint32_t)(k0 - r - 1) / (uint32_t)lag_step) + 1;
@@ -72,23 +68,17 @@ __global__ void __launch_bounds__(kWave) autocorr_grid_partial_kernel(const doub
 #pragma unroll
                 for (int j = 0; j < kBlock; ++j) {
                     const int64_t t = t0 + j * S;
-                    v[j] = y(t);
-                    win[kPassLags - 1 + j] = same ? v[j] : y(t - k0);
+                    b.v[j] = y(t);
+                    b.partner(j) = same ? b.v[j] : y(t - k0);
                 }
                 if (sums) {
 #pragma unroll
                     for (int j = 0; j < kBlock; ++j) {
-                        sum += v[j];
-                        sumsq = __builtin_fma(v[j], v[j], sumsq);
+                        sum += b.v[j];
+                        sumsq = __builtin_fma(b.v[j], b.v[j], sumsq);
                     }
                 }
-                // acc[i] += u[a0 + j] * w[a0 + j - i]
-#pragma unroll
-                for (int j = 0; j < kBlock; ++j)
-#pragma unroll
-                    for (int i = 0; i < kPassLags; ++i) acc[i] = __builtin_fma(v[j], win[kPassLags - 1 + j - i], acc[i]);
-#pragma unroll
-                for (int i = 0; i < kPassLags - 1; ++i) win[i] = win[i + kBlock];
+                b.fold();   // acc[i] += u[a0 + j] * w[a0 + j - i]
             }
         }
     }
@@ -97,13 +87,11 @@ __global__ void __launch_bounds__(kWave) autocorr_grid_partial_kernel(const doub
     for (int off = 32; off >= 1; off >>= 1) {
         sum += __shfl_xor(sum, off, kWave);
         sumsq += __shfl_xor(sumsq, off, kWave);
-#pragma unroll
-        for (int k = 0; k < kPassLags; ++k) acc[k] += __shfl_xor(acc[k], off, kWave);
+        b.butterfly(off);
     }
     if (lane == 0) {
         double* out = partial + ((size_t)cb * dim + d) * ((size_t)nrows + 2);
-#pragma unroll
-        for (int k = 0; k < kPassLags; ++k) out[pass * kPassLags + k] = acc[k];
+        b.store(out + pass * kPassLags);
         if (sums) {
             out[nrows] = sum;
             out[nrows + 1] = sumsq;
@@ -111,48 +99,31 @@ __global__ void __launch_bounds__(kWave) autocorr_grid_partial_kernel(const doub
     }
 }
 
-// out[i][d], i < nlags the rows, then sum, then sumsq: the chain blocks added ascending
-__global__ void autocorr_grid_reduce_kernel(const double* __restrict__ partial, int nblocks, int dim, int nlags, int nrows,
-                                            double* __restrict__ out) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= dim * (nlags + 2)) return;
-    const int d = idx / (nlags + 2), k = idx % (nlags + 2);
-    const int col = k < nlags ? k : nrows + (k - nlags);
-    double s = 0.0;
-    for (int cb = 0; cb < nblocks; ++cb) s += partial[((size_t)cb * dim + d) * ((size_t)nrows + 2) + col];
-    out[(size_t)k * dim + d] = s;
-}
-
 }  // namespace
 
 extern "C" int smcmc_autocorrelation_grid_sums(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
                                                int nchains_padded, const double* centre, int lag_first, int lag_step,
                                                int nlags, double* sum, double* sumsq, double* lagged, void* stream) {
-    if (!trace_device || !sum || !sumsq || !lagged) return SMCMC_ERR_INVALID;
-    if (nslots < 1 || dim < 1 || dim_stride < dim || nchains < 1 || nchains_padded < nchains || nchains_padded % kWave != 0)
+    if (bad_trace_shape(trace_device, nslots, dim, dim_stride, nchains, nchains_padded) || !sum || !sumsq || !lagged)
         return SMCMC_ERR_INVALID;
     if (lag_first < 0 || lag_step < 1 || nlags < 1 || nlags > SMCMC_AUTOCORR_GRID_MAX_LAGS) return SMCMC_ERR_INVALID;
     if ((int64_t)lag_first + (int64_t)(nlags - 1) * lag_step > INT32_MAX) return SMCMC_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return SMCMC_ERR_NO_DEVICE;
+    if (no_device()) return SMCMC_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     const int nblocks = nchains_padded / kWave;
     const int npasses = (nlags + kPassLags - 1) / kPassLags;
     const int nrows = npasses * kPassLags;
     const size_t nout = (size_t)dim * (nlags + 2);
     smcmc::DeviceBuffer<double> d_centre, d_partial, d_out;
-    if (d_centre.allocate(dim) != hipSuccess || d_partial.allocate((size_t)nblocks * dim * (nrows + 2)) != hipSuccess ||
-        d_out.allocate(nout) != hipSuccess)
+    if (centre_on_device(d_centre, centre, dim, s) != hipSuccess ||
+        d_partial.allocate((size_t)nblocks * dim * (nrows + 2)) != hipSuccess || d_out.allocate(nout) != hipSuccess)
         return SMCMC_ERR_HIP;
-    const hipError_t c = centre ? hipMemcpyAsync(d_centre, centre, sizeof(double) * dim, hipMemcpyHostToDevice, s)
-                                : hipMemsetAsync(d_centre, 0, sizeof(double) * dim, s);
-    if (c != hipSuccess) return SMCMC_ERR_HIP;
     hipLaunchKernelGGL(autocorr_grid_partial_kernel, dim3(nblocks, dim, npasses), dim3(kWave), 0, s, trace_device, nslots, dim,
                        (size_t)dim_stride, nchains, (size_t)nchains_padded, d_centre.get(), lag_first, lag_step, nrows,
                        d_partial.get());
     if (hipGetLastError() != hipSuccess) return SMCMC_ERR_HIP;
-    hipLaunchKernelGGL(autocorr_grid_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, d_partial.get(),
-                       nblocks, dim, nlags, nrows, d_out.get());
+    // out[i][d], i < nlags the rows, then sum, then sumsq: the chain blocks added ascending
+    launch_ordered_rows_reduce(s, d_partial.get(), nblocks, dim, nlags + 2, nrows + 2, nrows, d_out.get());
     if (hipGetLastError() != hipSuccess) return SMCMC_ERR_HIP;
     if (hipMemcpyAsync(lagged, d_out, sizeof(double) * dim * nlags, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(sum, d_out + (size_t)dim * nlags, sizeof(double) * dim, hipMemcpyDeviceToHost, s) != hipSuccess ||

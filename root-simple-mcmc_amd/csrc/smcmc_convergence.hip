@@ -10,13 +10,12 @@
 // stored as [S][dim][nchains_padded] (0 in the lanes >= nchains, by a select: the padding is not read), then s1 and s1^2
 // go through a butterfly over the wavefront into the block's partial sums.
 //
-// Pass 2, within_partial_kernel<K0>: the register shape of autocorr_partial_kernel<K0> (smcmc_autocorr.hip): the 16
-// values of the current block of slots, a sliding window of the 47 values that 32 lags reach back to, 32 accumulators,
-// static indices, no LDS; one launch for the lags 0..31 and one for 32..63.  The value is z_t = (x - centre) - s1 / L,
+// Pass 2, within_partial_kernel<K0>: the lagged register block of smcmc_trace_reduce.hip.h, as autocorr_partial_kernel<K0>
+// (smcmc_autocorr.hip) uses it; one launch for the lags 0..31 and one for 32..63.  The value is z_t = (x - centre) - s1 / L,
 // the lane's own mean taken off with the two subtractions of the definition, and a wavefront owns one segment: its
 // window starts empty at the segment's first slot, so no lag reaches across it.
 //
-// within_reduce_kernel adds the block partials in order.
+// ordered_rows_reduce_kernel (smcmc_trace_reduce.hip.h) adds the block partials in order.
 // Summation order, fixed for a shape: slots ascending per lane; a butterfly over the 64 chains of a wavefront (offsets
 // 32, 16, .., 1); then one running sum over the blocks of 64 chains ascending within a segment, the segments ascending.
 // The same bits on every run.
@@ -25,14 +24,12 @@
 
 #include "smcmc.h"
 #include "smcmc_host.hpp"
+#include "smcmc_trace_reduce.hip.h"
 
 namespace {
 
 constexpr int kLags = SMCMC_AUTOCORR_LAGS;   // lags 0 .. 63
-constexpr int kWave = 64;
-constexpr int kPassLags = 32;                // lags per wavefront
-constexpr int kBlock = 16;                   // slots per register block
-constexpr int kWin = kBlock + kPassLags - 1; // z[t0 - K0 - 31 .. t0 - K0 + 15]
+using namespace smcmc::reduce;               // kWave, kPassLags, kBlock, LaggedBlock: its window is z[t0 - K0 - 31 .. t0 - K0 + 15]
 constexpr int kRows = kLags + 2;             // a partial: within[0 .. 63], sum, sumsq_of_sums
 constexpr int kMaxSegments = 65535;          // the grid's z extent
 static_assert(kLags == 2 * kPassLags, "two passes cover the lags");
@@ -135,74 +132,40 @@ __global__ void __launch_bounds__(kWave) within_partial_kernel(const double* __r
         const double r = (p.src[(size_t)t * slot_stride] - c0) - mean;
         return p.active ? r : 0.0;
     };
-    double win[kWin], acc[kPassLags], v[kBlock];
+    LaggedBlock b;
+    b.clear_window();                                              // the segment's first slot: nothing behind it
+    b.clear_sums();
+    // the partners of the block at t0, acc[kk] += z[t0 + j] * z[t0 + j - K0 - kk]: the lagged block of the second launch
+    // lies K0 = 2 kBlock slots back, wholly before the segment or wholly inside it
+    auto partners = [&](int t0) __attribute__((always_inline)) {
+        if (K0 == 0) {
 #pragma unroll
-    for (int i = 0; i < kWin; ++i) win[i] = 0.0;                   // the segment's first slot: nothing behind it
+            for (int j = 0; j < kBlock; ++j) b.partner(j) = b.v[j];
+        } else if (t0 >= K0) {
 #pragma unroll
-    for (int k = 0; k < kPassLags; ++k) acc[k] = 0.0;
-    // the lagged block of the second launch lies K0 = 2 kBlock slots back: wholly before the segment or wholly inside it
-    auto fold = [&]() __attribute__((always_inline)) {
-        // acc[kk] += z[t0 + j] * z[t0 + j - K0 - kk]
+            for (int j = 0; j < kBlock; ++j) b.partner(j) = z(t0 - K0 + j);
+        } else {
 #pragma unroll
-        for (int j = 0; j < kBlock; ++j)
-#pragma unroll
-            for (int kk = 0; kk < kPassLags; ++kk) acc[kk] = __builtin_fma(v[j], win[kPassLags - 1 + j - kk], acc[kk]);
-#pragma unroll
-        for (int i = 0; i < kPassLags - 1; ++i) win[i] = win[i + kBlock];
+            for (int j = 0; j < kBlock; ++j) b.partner(j) = 0.0;
+        }
     };
     const int whole = L / kBlock * kBlock;
     for (int t0 = 0; t0 < whole; t0 += kBlock) {                   // whole blocks: every load unconditional
 #pragma unroll
-        for (int j = 0; j < kBlock; ++j) v[j] = z(t0 + j);
-        if (K0 == 0) {
-#pragma unroll
-            for (int j = 0; j < kBlock; ++j) win[kPassLags - 1 + j] = v[j];
-        } else if (t0 >= K0) {
-#pragma unroll
-            for (int j = 0; j < kBlock; ++j) win[kPassLags - 1 + j] = z(t0 - K0 + j);
-        } else {
-#pragma unroll
-            for (int j = 0; j < kBlock; ++j) win[kPassLags - 1 + j] = 0.0;
-        }
-        fold();
+        for (int j = 0; j < kBlock; ++j) b.v[j] = z(t0 + j);
+        partners(t0);
+        b.fold();
     }
     if (whole < L) {                                               // the last, partial block
 #pragma unroll
-        for (int j = 0; j < kBlock; ++j) v[j] = whole + j < L ? z(whole + j) : 0.0;
-        if (K0 == 0) {
-#pragma unroll
-            for (int j = 0; j < kBlock; ++j) win[kPassLags - 1 + j] = v[j];
-        } else if (whole >= K0) {
-#pragma unroll
-            for (int j = 0; j < kBlock; ++j) win[kPassLags - 1 + j] = z(whole - K0 + j);
-        } else {
-#pragma unroll
-            for (int j = 0; j < kBlock; ++j) win[kPassLags - 1 + j] = 0.0;
-        }
-        fold();
+        for (int j = 0; j < kBlock; ++j) b.v[j] = whole + j < L ? z(whole + j) : 0.0;
+        partners(whole);
+        b.fold();
     }
     // butterfly over the wavefront's chains
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < kPassLags; ++k) acc[k] += __shfl_xor(acc[k], off, kWave);
-    }
-    if (threadIdx.x == 0) {
-        double* out = partial + p.partial_at + K0;
-#pragma unroll
-        for (int k = 0; k < kPassLags; ++k) out[k] = acc[k];
-    }
-}
-
-// out[row][d] = one running sum over the segments ascending and, within a segment, the live blocks ascending
-__global__ void within_reduce_kernel(const double* __restrict__ partial, long long npieces, int dim, double* __restrict__ out) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= dim * kRows) return;
-    const int d = idx / kRows, row = idx % kRows;
-    double s = 0.0;
-#pragma unroll 8
-    for (long long p = 0; p < npieces; ++p) s += partial[((size_t)p * dim + d) * kRows + row];
-    out[(size_t)row * dim + d] = s;
+    for (int off = 32; off >= 1; off >>= 1) b.butterfly(off);
+    if (threadIdx.x == 0) b.store(partial + p.partial_at + K0);
 }
 
 }  // namespace
@@ -210,26 +173,22 @@ __global__ void within_reduce_kernel(const double* __restrict__ partial, long lo
 extern "C" int smcmc_trace_convergence(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
                                        int nchains_padded, int nsegments, const double* centre, double* chain_sums_device,
                                        double* sum, double* sumsq_of_sums, double* within, void* stream) {
-    if (!trace_device || !sum || !sumsq_of_sums || !within) return SMCMC_ERR_INVALID;
-    if (nsegments < 1 || nslots / nsegments < 2 || dim < 1 || dim > smcmc_max_dim() || dim_stride < dim || nchains < 1 ||
-        nchains_padded < nchains || nchains_padded % kWave != 0)
+    if (!sum || !sumsq_of_sums || !within) return SMCMC_ERR_INVALID;
+    if (nsegments < 1 || nslots / nsegments < 2 ||
+        bad_trace_shape(trace_device, nslots, dim, dim_stride, nchains, nchains_padded, smcmc_max_dim()))
         return SMCMC_ERR_INVALID;
     if (nsegments > kMaxSegments) return SMCMC_ERR_UNSUPPORTED;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return SMCMC_ERR_NO_DEVICE;
+    if (no_device()) return SMCMC_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     const int S = nsegments, L = nslots / S, first_slot = nslots - S * L;
     const int nblocks = nchains_padded / kWave, nlive = (nchains + kWave - 1) / kWave;
     const size_t nout = (size_t)dim * kRows;
     smcmc::DeviceBuffer<double> d_centre, d_partial, d_out, d_sums;
-    if (d_centre.allocate(dim) != hipSuccess || d_partial.allocate(nout * nlive * S) != hipSuccess ||
+    if (centre_on_device(d_centre, centre, dim, s) != hipSuccess || d_partial.allocate(nout * nlive * S) != hipSuccess ||
         d_out.allocate(nout) != hipSuccess)
         return SMCMC_ERR_HIP;
     if (!chain_sums_device && d_sums.allocate((size_t)S * dim * nchains_padded) != hipSuccess) return SMCMC_ERR_HIP;
     double* sums = chain_sums_device ? chain_sums_device : d_sums.get();
-    const hipError_t c = centre ? hipMemcpyAsync(d_centre, centre, sizeof(double) * dim, hipMemcpyHostToDevice, s)
-                                : hipMemsetAsync(d_centre, 0, sizeof(double) * dim, s);
-    if (c != hipSuccess) return SMCMC_ERR_HIP;
     hipLaunchKernelGGL(chain_sums_kernel, dim3(nblocks, dim, S), dim3(kWave), 0, s, trace_device, first_slot, L, dim,
                        (size_t)dim_stride, nchains, (size_t)nchains_padded, nlive, d_centre.get(), sums, d_partial.get());
     if (hipGetLastError() != hipSuccess) return SMCMC_ERR_HIP;
@@ -239,8 +198,8 @@ extern "C" int smcmc_trace_convergence(const double* trace_device, int nslots, i
     hipLaunchKernelGGL(within_partial_kernel<kPassLags>, dim3(nlive, dim, S), dim3(kWave), 0, s, trace_device, first_slot, L,
                        dim, (size_t)dim_stride, nchains, (size_t)nchains_padded, nlive, d_centre.get(), sums, d_partial.get());
     if (hipGetLastError() != hipSuccess) return SMCMC_ERR_HIP;
-    hipLaunchKernelGGL(within_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, d_partial.get(), (long long)nlive * S,
-                       dim, d_out.get());
+    // out[row][d] = one running sum over the segments ascending and, within a segment, the live blocks ascending
+    launch_ordered_rows_reduce(s, d_partial.get(), (long long)nlive * S, dim, kRows, kRows, kLags, d_out.get());
     if (hipGetLastError() != hipSuccess) return SMCMC_ERR_HIP;
     if (hipMemcpyAsync(within, d_out, sizeof(double) * dim * kLags, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(sum, d_out + (size_t)dim * kLags, sizeof(double) * dim, hipMemcpyDeviceToHost, s) != hipSuccess ||

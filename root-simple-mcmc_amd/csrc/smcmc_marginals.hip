@@ -27,10 +27,11 @@
 
 #include "smcmc.h"
 #include "smcmc_host.hpp"
+#include "smcmc_trace_reduce.hip.h"
 
 namespace {
 
-constexpr int kWave = 64;
+using smcmc::reduce::kWave;
 constexpr int kRangeBlock = 8;        // sampled slots in flight per lane (ranges)
 constexpr int kFillThreads1 = 256;    // chains per workgroup, 1-D fill
 constexpr int kFillThreads2 = 1024;   // chains per workgroup, pair fill (one workgroup per CU: the tables fill its LDS)
@@ -216,10 +217,7 @@ __global__ void __launch_bounds__(kFillThreads2) marginal_fill2_kernel(const dou
     }
 }
 
-bool bad_trace_shape(const void* trace, int nslots, int dim, int dim_stride, int nchains, int nchains_padded) {
-    return !trace || nslots < 1 || dim < 1 || dim > 65535 /* the grid's y extent */ || dim_stride < dim || nchains < 1 || nchains_padded < nchains ||
-           nchains_padded % kWave != 0;
-}
+constexpr int kMaxDim = 65535;        // the grid's y extent
 
 bool bad_axis(double lo, double hi) { return !std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi); }
 
@@ -246,10 +244,10 @@ int fill_copies(int stride) {
 
 extern "C" int smcmc_trace_ranges(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
                                   int nchains_padded, int sample_stride, double* lo, double* hi, void* stream) {
-    if (bad_trace_shape(trace_device, nslots, dim, dim_stride, nchains, nchains_padded) || sample_stride < 1 || !lo || !hi)
+    if (smcmc::reduce::bad_trace_shape(trace_device, nslots, dim, dim_stride, nchains, nchains_padded, kMaxDim) ||
+        sample_stride < 1 || !lo || !hi)
         return SMCMC_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return SMCMC_ERR_NO_DEVICE;
+    if (smcmc::reduce::no_device()) return SMCMC_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     const int nblocks = (nchains + kWave - 1) / kWave;
     smcmc::DeviceBuffer<double> d_partial, d_out;
@@ -271,7 +269,8 @@ extern "C" int smcmc_marginal_histograms(const double* trace_device, int nslots,
                                          int nchains_padded, int n1, const double* lo1, const double* hi1,
                                          uint64_t* counts1, int npair_dims, const int32_t* pair_dims, int n2,
                                          const double* lo2, const double* hi2, uint64_t* counts2, void* stream) {
-    if (bad_trace_shape(trace_device, nslots, dim, dim_stride, nchains, nchains_padded)) return SMCMC_ERR_INVALID;
+    if (smcmc::reduce::bad_trace_shape(trace_device, nslots, dim, dim_stride, nchains, nchains_padded, kMaxDim))
+        return SMCMC_ERR_INVALID;
     if (n1 < 0 || npair_dims < 0) return SMCMC_ERR_INVALID;
     const bool do1 = n1 > 0 && counts1, do2 = npair_dims > 0;
     if (!do1 && !do2) return SMCMC_ERR_INVALID;   // nothing asked for
@@ -287,8 +286,7 @@ extern "C" int smcmc_marginal_histograms(const double* trace_device, int nslots,
         for (int p = 0; p < P; ++p)
             if (pair_dims[p] < 0 || pair_dims[p] >= dim || bad_axis(lo2[p], hi2[p])) return SMCMC_ERR_INVALID;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return SMCMC_ERR_NO_DEVICE;
+    if (smcmc::reduce::no_device()) return SMCMC_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     const int chunk = fill_chunk(nslots);
     const unsigned nchunks = (unsigned)((nslots + chunk - 1) / chunk);

@@ -39,12 +39,13 @@
 #include "smcmc_detmath.h"
 #include "smcmc_host.hpp"
 #include "smcmc_proposal.hpp"
+#include "smcmc_trace_reduce.hip.h"
 
 namespace {
 
 using smcmc::f64x4;
 
-constexpr int kWave = 64;
+using smcmc::reduce::kWave;
 constexpr int kPitch = kWave + 2;     // doubles per LDS row: the 64 chains of a unit + 2 (row stride = 2 mod 32 bank pairs)
 constexpr int kBlockRows = 64;        // rows of y per tile block: four operand tiles
 constexpr int kQuads = kWave / 4;     // matrix instructions per tile and unit
@@ -244,19 +245,14 @@ __global__ void __launch_bounds__(256) cholesky_chain_kernel(const double* __res
     }
 }
 
-bool bad_trace_shape(const void* trace, int nslots, int dim, int dim_stride, int nchains, int nchains_padded) {
-    return !trace || nslots < 1 || dim < 1 || dim > smcmc_max_dim() || dim_stride < dim || nchains < 1 ||
-           nchains_padded < nchains || nchains_padded % kWave != 0;
-}
-
 }  // namespace
 
 extern "C" int smcmc_trace_moments(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
                                    int nchains_padded, const double* centre, double* sum, double* sumsq, void* stream) {
-    if (bad_trace_shape(trace_device, nslots, dim, dim_stride, nchains, nchains_padded) || !sum || !sumsq)
+    if (smcmc::reduce::bad_trace_shape(trace_device, nslots, dim, dim_stride, nchains, nchains_padded, smcmc_max_dim()) ||
+        !sum || !sumsq)
         return SMCMC_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return SMCMC_ERR_NO_DEVICE;
+    if (smcmc::reduce::no_device()) return SMCMC_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     const int n = dim + 1;                                        // rows of y = (x - centre, 1)
     const int B = (n + kBlockRows - 1) / kBlockRows;              // tile blocks
@@ -269,13 +265,10 @@ extern "C" int smcmc_trace_moments(const double* trace_device, int nslots, int d
     const int nwg_d = workgroups(4), nwg_o = workgroups(2), npairs_o = B * (B - 1) / 2;
     const size_t tile = 4 * kWave;
     smcmc::DeviceBuffer<double> d_centre, d_pdiag, d_poff, d_E;
-    if (d_centre.allocate(dim) != hipSuccess || d_pdiag.allocate((size_t)B * nwg_d * (ta * (ta + 1) / 2) * tile) != hipSuccess ||
+    if (smcmc::reduce::centre_on_device(d_centre, centre, dim, s) != hipSuccess || d_pdiag.allocate((size_t)B * nwg_d * (ta * (ta + 1) / 2) * tile) != hipSuccess ||
         d_E.allocate((size_t)n * n) != hipSuccess)
         return SMCMC_ERR_HIP;
     if (npairs_o && d_poff.allocate((size_t)npairs_o * nwg_o * 16 * tile) != hipSuccess) return SMCMC_ERR_HIP;
-    const hipError_t c = centre ? hipMemcpyAsync(d_centre, centre, sizeof(double) * dim, hipMemcpyHostToDevice, s)
-                                : hipMemsetAsync(d_centre, 0, sizeof(double) * dim, s);
-    if (c != hipSuccess) return SMCMC_ERR_HIP;
     hipError_t e = hipSuccess;
     switch (ta) {
 #define SMCMC_TM_CASE(t)                                                                                              \
@@ -310,13 +303,13 @@ extern "C" int smcmc_trace_moments(const double* trace_device, int nslots, int d
 extern "C" int smcmc_cholesky_chain(const double* mean, const double* covariance, int dim, int nslots, int nchains,
                                     int nchains_padded, int dim_stride, uint64_t seed, uint32_t chain_offset,
                                     double* trace_device, double* decomposition, void* stream) {
-    if (bad_trace_shape(trace_device, nslots, dim, dim_stride, nchains, nchains_padded) || !mean || !covariance)
+    if (smcmc::reduce::bad_trace_shape(trace_device, nslots, dim, dim_stride, nchains, nchains_padded, smcmc_max_dim()) ||
+        !mean || !covariance)
         return SMCMC_ERR_INVALID;
     smcmc::SharedProposal prop(dim);
     prop.cov.assign(covariance, covariance + (size_t)dim * dim);
     if (!prop.choleskyOnly()) return SMCMC_ERR_RUNTIME;          // "Decomposition of the covariance has failed" :41-45
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return SMCMC_ERR_NO_DEVICE;
+    if (smcmc::reduce::no_device()) return SMCMC_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     const int jb = dim <= 16 ? 16 : dim <= 32 ? 32 : 64;
     const int pitch = (dim + jb - 1) / jb * jb;

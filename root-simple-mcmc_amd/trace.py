@@ -1,0 +1,645 @@
+"""The reducers over a saved trace: what they return and the methods the engines share to call them.
+
+A saved trace is [slot][dim_stride][nchains_padded] doubles on the device: Engine.StepSave writes dim_stride =
+dim_padded rows per slot, HmcEngine.StepSave / copy_positions and VaatEngine.step_save write dim_stride = dim.  The
+reducers of the HIP library (smcmc_autocorrelation_sums, smcmc_autocorrelation_grid_sums, smcmc_trace_ranges,
+smcmc_marginal_histograms, smcmc_trace_moments, smcmc_trace_convergence; include/smcmc.h) take any of them.  The result
+classes are host-side numpy over the raw sums and have nothing to do with any engine; `TraceReducers` gives an engine
+class the six methods that call the library on a trace of its own layout.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from ._capi import SmcmcError
+
+_dp = C.POINTER(C.c_double)
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _ptr(a):
+    return a.ctypes.data_as(_dp)
+
+
+class TraceReducers:
+    """The reducers over a saved trace as methods of an engine (Engine, HmcEngine, VaatEngine).  The engine class
+    provides _lib, _check, dim, nchains, nchains_padded and one hook, `_trace_dim_stride`: the rows a slot of the traces
+    it writes holds (dim_padded for Engine.StepSave, dim for HmcEngine.StepSave / copy_positions and
+    VaatEngine.step_save).  Where a docstring says "a trace StepSave wrote", read the engine's own call."""
+
+    def _trace_shape(self):
+        return self.dim, self._trace_dim_stride, self.nchains, self.nchains_padded
+
+    def AutocorrelationSums(self, trace_ptr, nslots, centre=None, stream=0):
+        """Lagged-product sums of a trace StepSave wrote ([slot][dim_padded][nchains_padded] on the device), pooled
+        over slots and chains about `centre` (default: the origin, as the macro has it): the inputs of the reference's
+        autocorrelation (MakeAutocorrelation.C:108-148).  Returns an Autocorrelation."""
+        c = _f64(np.zeros(self.dim) if centre is None else centre)
+        s = np.zeros(self.dim)
+        lagged = np.zeros((_capi.AUTOCORR_LAGS, self.dim))
+        self._check(self._lib.smcmc_autocorrelation_sums(C.c_void_p(int(trace_ptr)), int(nslots), *self._trace_shape(),
+                                                         _ptr(c), _ptr(s), _ptr(lagged), C.c_void_p(int(stream))))
+        return Autocorrelation(s, lagged, int(nslots), self.nchains)
+
+    def AutocorrelationGrid(self, trace_ptr, nslots, lag_first=1, lag_step=1, nlags=64, centre=None, stream=0):
+        """The pooled sums of a trace StepSave wrote on the lags lag_first + i lag_step, i < nlags, taken on the device
+        (smcmc_autocorrelation_grid_sums): as far back along the chain as the caller asks, where AutocorrelationSums
+        stops at lag 63.  More than 512 lags are taken in several calls.  Returns an AutocorrelationGrid."""
+        return _autocorrelation_grid(self._lib, self._check, trace_ptr, nslots, *self._trace_shape(), lag_first, lag_step,
+                                     nlags, centre, stream)
+
+    def MakeAutocorrelation(self, trace_ptr, nslots, stream=0, centre=None, plan=None):
+        """MakeAutocorrelation.C over a trace StepSave wrote: the macro's plan for entries = nslots
+        (autocorrelation_plan), the device sums over the last `trials` slots on its lag grid, its bins.  centre: the
+        reference point of the sums (default: the origin, as the macro has it).  plan: another AutocorrelationPlan for
+        entries = nslots, e.g. autocorrelation_plan(nslots, depth, bins, precision) with constants of the caller's own.
+        Returns a MacroAutocorrelation."""
+        return _make_autocorrelation(self._lib, self._check, trace_ptr, nslots, *self._trace_shape(), centre, stream, plan)
+
+    def Marginals(self, trace_ptr, nslots, n1=100, n2=50, pair_dims=None, sample_stride=None, ranges=None, stream=0):
+        """The histograms of TestMarginalization.C over a trace StepSave wrote, counted on the device: the ranges of the
+        dimensions over every sample_stride-th slot (default: the macro's stride; skipped when `ranges` = (lo, hi) is
+        given, e.g. the merged ranges of several ranks), then n1 bins over [absMin, absMax) for every dimension and
+        n2 x n2 bins for every ordered pair of pair_dims (default: the first min(dim, 10) dimensions) over the
+        dimensions' ranges widened by 5 %.  Returns a Marginals."""
+        return _marginals(self._lib, self._check, trace_ptr, nslots, *self._trace_shape(), n1, n2, pair_dims, sample_stride,
+                          ranges, stream)
+
+    def TraceMoments(self, trace_ptr, nslots, centre=None, stream=0):
+        """The sums behind the mean and covariance of a trace StepSave wrote (MakeCovariance.C:63-89), taken on the
+        device over every slot of every chain about `centre` (default: the origin, as the macro has it; the mean of
+        the run conditions the covariance better).  Returns a TraceMoments."""
+        return _trace_moments(self._lib, self._check, trace_ptr, nslots, *self._trace_shape(), centre, stream)
+
+    def Convergence(self, trace_ptr, nslots, nsegments=2, centre=None, stream=0):
+        """The sums behind split R-hat and the multi-chain effective sample size of a trace StepSave wrote
+        (smcmc_trace_convergence), taken on the device: every chain cut into `nsegments` segments (2: split R-hat, 1: the
+        plain form), each about its own mean.  Pass a `centre` near the mean, e.g. TraceMoments(...).mean from one
+        earlier pass: the variance of the segment means cancels like any E[yy] - E[y]^2.  Returns a Convergence."""
+        return _convergence(self._lib, self._check, trace_ptr, nslots, *self._trace_shape(), nsegments, centre, stream)
+
+
+class Autocorrelation:
+    """a(lag) = (E[x_t x_(t-lag)] - mean^2) / var per dimension (MakeAutocorrelation.C:127-139) from the pooled sums
+    of Engine.AutocorrelationSums; sums of several ranks add (`+`)."""
+
+    def __init__(self, total, lagged, nslots, nchains):
+        self.sum, self.lagged, self.nslots, self.nchains = np.array(total), np.array(lagged), nslots, nchains
+
+    def __add__(self, other):
+        if self.nslots != other.nslots:
+            raise ValueError("traces of different lengths do not pool")
+        return Autocorrelation(self.sum + other.sum, self.lagged + other.lagged, self.nslots, self.nchains + other.nchains)
+
+    def rho(self):
+        """[lag][dim]"""
+        nlag = min(self.lagged.shape[0], self.nslots)
+        n = (self.nslots - np.arange(nlag))[:, None] * float(self.nchains)
+        mean = self.sum / n[0]
+        var = self.lagged[0] / n[0] - mean * mean
+        return (self.lagged[:nlag] / n - mean * mean) / var
+
+    def tau(self):
+        """Integrated autocorrelation time per dimension in slots: 1 + 2 sum rho, the sum cut where a pair of
+        consecutive lags turns negative (initial positive sequence)."""
+        rho = self.rho()
+        out = np.ones(rho.shape[1])
+        for d in range(rho.shape[1]):
+            for k in range(1, rho.shape[0] - 1, 2):
+                pair = rho[k, d] + rho[k + 1, d]
+                if pair < 0:
+                    break
+                out[d] += 2.0 * pair
+        return out
+
+
+class AutocorrelationGrid:
+    """The pooled sums of smcmc_autocorrelation_grid_sums (include/smcmc.h) on the lags `lags` = lag_first + i lag_step:
+    sum[dim], sumsq[dim] (lag 0) and lagged[lag][dim] about one reference point.
+      counts   terms per lag, max(nslots - lag, 0) * nchains
+      rho()    [lag][dim], (lagged / counts - mean^2) / (sumsq / n - mean^2); NaN for a lag beyond the trace
+    Sums of several ranks add (`+`) when the grid and nslots agree."""
+
+    def __init__(self, lags, total, sumsq, lagged, nslots, nchains):
+        self.lags = np.array(lags, dtype=np.int64)
+        self.sum, self.sumsq, self.lagged = _f64(total).copy(), _f64(sumsq).copy(), _f64(lagged).copy()
+        self.nslots, self.nchains = int(nslots), int(nchains)
+        if (self.lags.ndim != 1 or self.sum.ndim != 1 or self.sumsq.shape != self.sum.shape
+                or self.lagged.shape != (self.lags.size, self.sum.size)):
+            raise ValueError("lags[lag], sum[dim], sumsq[dim] and lagged[lag][dim] do not fit together")
+
+    @property
+    def counts(self):
+        return np.maximum(self.nslots - self.lags, 0) * float(self.nchains)
+
+    def __add__(self, other):
+        if self.nslots != other.nslots:
+            raise ValueError("traces of different lengths do not pool")
+        if not np.array_equal(self.lags, other.lags):
+            raise ValueError("sums on different lag grids do not add")
+        return AutocorrelationGrid(self.lags, self.sum + other.sum, self.sumsq + other.sumsq, self.lagged + other.lagged,
+                                   self.nslots, self.nchains + other.nchains)
+
+    def rho(self):
+        """[lag][dim]"""
+        n = float(self.nslots) * self.nchains
+        mean = self.sum / n
+        var = self.sumsq / n - mean * mean
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (self.lagged / self.counts[:, None] - mean * mean) / var
+
+
+def _autocorrelation_grid(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchains_padded, lag_first, lag_step,
+                          nlags, centre, stream):
+    """The body of the engines' AutocorrelationGrid methods: calls of at most AUTOCORR_GRID_MAX_LAGS lags each, the rows
+    concatenated (a row's bits do not depend on the call it is taken in)."""
+    c = None if centre is None else _f64(centre)
+    if c is not None and c.shape != (dim,):
+        raise ValueError("centre must be [dim]")
+    nslots, lag_first, lag_step, nlags = int(nslots), int(lag_first), int(lag_step), int(nlags)
+    if nlags < 1:
+        raise ValueError("nlags must be at least 1")
+    total, sumsq, lagged = np.zeros(dim), np.zeros(dim), np.zeros((nlags, dim))
+    for i0 in range(0, nlags, _capi.AUTOCORR_GRID_MAX_LAGS):
+        n = min(_capi.AUTOCORR_GRID_MAX_LAGS, nlags - i0)
+        rows = np.zeros((n, dim))
+        check(lib.smcmc_autocorrelation_grid_sums(C.c_void_p(int(trace_ptr)), nslots, dim, dim_stride, nchains,
+                                                  nchains_padded, None if c is None else _ptr(c),
+                                                  lag_first + i0 * lag_step, lag_step, n, _ptr(total), _ptr(sumsq),
+                                                  _ptr(rows), C.c_void_p(int(stream))))
+        lagged[i0:i0 + n] = rows
+    return AutocorrelationGrid(lag_first + lag_step * np.arange(nlags), total, sumsq, lagged, nslots, nchains)
+
+
+class AutocorrelationPlan:
+    """The constants MakeAutocorrelation.C derives from the number of entries (autocorrelation_plan): entries, depth,
+    max_lag, bins, lag_step, trials, lags[lag], lag_bins[lag] (0-based bin of each lag) and bin_centres[bin]."""
+
+    def __init__(self, entries, depth, max_lag, bins, lag_step, trials):
+        self.entries, self.depth, self.max_lag, self.bins = entries, depth, max_lag, bins
+        self.lag_step, self.trials = lag_step, trials
+        self.lags = np.arange(1, max_lag, lag_step, dtype=np.int64)
+        # the fixed-width axis of include/smcmc.h over [0, max_lag), filled at lag + 0.5 (:121)
+        self.lag_bins = np.array([int(bins * (lag + 0.5) / max_lag) for lag in self.lags], dtype=np.int64)
+        self.bin_centres = (np.arange(bins) + 0.5) * (float(max_lag) / bins)
+
+    def __eq__(self, other):
+        return (isinstance(other, AutocorrelationPlan)
+                and (self.entries, self.depth, self.max_lag, self.bins, self.lag_step, self.trials)
+                == (other.entries, other.depth, other.max_lag, other.bins, other.lag_step, other.trials))
+
+
+def autocorrelation_plan(entries, depth=30000, bins=100, precision=0.01):
+    """MakeAutocorrelation.C's constants for a tree of `entries` entries (:62, 70-73, 98-99, 104-106):
+      maxLag  = min(int(entries - sqrt(entries)), depth)        bins    = min(bins, maxLag)
+      lagStep = max(1, int(0.5 maxLag / bins))                  trials  = min(int(maxLag + 1 / precision^3), entries)
+      lags 1, 1 + lagStep, ... < maxLag, each in bin int(bins (lag + 0.5) / maxLag).
+    A pure function; returns an AutocorrelationPlan."""
+    entries = int(entries)
+    max_lag = min(int(entries - np.sqrt(float(entries))), int(depth)) if entries > 0 else 0
+    if max_lag < 2:
+        raise ValueError("the macro evaluates no lag below 4 entries")
+    bins = min(int(bins), max_lag)
+    lag_step = max(1, int(0.5 * max_lag / bins))
+    trials = min(int(max_lag + 1.0 / (precision * precision * precision)), entries)
+    return AutocorrelationPlan(entries, int(depth), max_lag, bins, lag_step, trials)
+
+
+class MacroAutocorrelation:
+    """What MakeAutocorrelation.C writes, from pooled device sums over the last plan.trials slots on the macro's lag
+    grid (the engines' MakeAutocorrelation; from_sums is pure).  With n = trials * nchains and y = x - centre:
+      bin_centres      [bin], the centres of the bins over [0, maxLag)
+      mean[d]          centre + sum / n                                          (meanValues, :132)
+      err2[d]          sumsq / n - (sum / n)^2: the "s" error of meanValues, squared (:133)
+      autocorr[d][bin] (v / e - (sum / n)^2) / err2, v and e the sums of `lagged` and of `counts` over the lags that
+                       fall into the bin (:135-139); a bin no lag falls into is 0/0 = NaN, as in the macro
+      average[bin], spread[bin]   mean and population r.m.s. of autocorr over the dimensions (avgCorr, option "S", :146)
+    Sums of several ranks add (`+`) when the plan and the centre agree.
+    Deviations from the macro, on purpose (include/smcmc.h states them): its ring buffer holds floats, so every value is
+    rounded to single precision before it is multiplied, and the values here are doubles; its TH1F sums are floats, and
+    these are doubles; it reads one chain, and here the chains are pooled into one sum, so one chain is the macro.  The
+    macro's reference point is the origin (centre = None); another centre changes autocorr only through the edges of
+    the lagged sums, O(lag / trials)."""
+
+    def __init__(self, plan, total, sumsq, lagged, nchains, centre=None):
+        self.plan, self.nchains = plan, int(nchains)
+        self.sum, self.sumsq, self.lagged = _f64(total).copy(), _f64(sumsq).copy(), _f64(lagged).copy()
+        self.centre = np.zeros(self.sum.size) if centre is None else _f64(centre).copy()
+        if (self.sum.ndim != 1 or self.sumsq.shape != self.sum.shape or self.centre.shape != self.sum.shape
+                or self.lagged.shape != (plan.lags.size, self.sum.size)):
+            raise ValueError("sum[dim], sumsq[dim], centre[dim] and lagged[lag][dim] do not fit the plan")
+
+    @classmethod
+    def from_sums(cls, plan, total, sumsq, lagged, nchains, centre=None):
+        return cls(plan, total, sumsq, lagged, nchains, centre)
+
+    def __add__(self, other):
+        if self.plan != other.plan:
+            raise ValueError("sums of different plans do not add")
+        if not np.array_equal(self.centre, other.centre):
+            raise ValueError("sums about different centres do not add")
+        return MacroAutocorrelation(self.plan, self.sum + other.sum, self.sumsq + other.sumsq, self.lagged + other.lagged,
+                                    self.nchains + other.nchains, self.centre)
+
+    @property
+    def counts(self):
+        """[lag]: the macro's fills per lag (`fills <= lag` breaks, :118), times the chains"""
+        return (self.plan.trials - self.plan.lags) * float(self.nchains)
+
+    @property
+    def bin_centres(self):
+        return self.plan.bin_centres
+
+    @property
+    def _ymean(self):
+        return self.sum / (float(self.plan.trials) * self.nchains)
+
+    @property
+    def mean(self):
+        return self.centre + self._ymean
+
+    @property
+    def err2(self):
+        m = self._ymean
+        return self.sumsq / (float(self.plan.trials) * self.nchains) - m * m
+
+    @property
+    def autocorr(self):
+        """[dim][bin]"""
+        dim, bins = self.sum.size, self.plan.bins
+        v, e = np.zeros((dim, bins)), np.zeros(bins)
+        counts = self.counts
+        for i, b in enumerate(self.plan.lag_bins):      # lags ascending, as the macro fills them
+            v[:, b] += self.lagged[i]
+            e[b] += counts[i]
+        m = self._ymean
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (v / e[None, :] - (m * m)[:, None]) / self.err2[:, None]
+
+    @property
+    def average(self):
+        return self.autocorr.mean(axis=0)
+
+    @property
+    def spread(self):
+        return self.autocorr.std(axis=0)
+
+
+def _make_autocorrelation(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchains_padded, centre, stream, plan):
+    """The body of the engines' MakeAutocorrelation methods."""
+    if plan is None:
+        plan = autocorrelation_plan(int(nslots))
+    elif plan.entries != int(nslots):
+        raise ValueError("the plan is for %d entries, the trace has %d slots" % (plan.entries, int(nslots)))
+    first = int(trace_ptr) + 8 * (plan.entries - plan.trials) * dim_stride * nchains_padded   # the last `trials` slots
+    g = _autocorrelation_grid(lib, check, first, plan.trials, dim, dim_stride, nchains, nchains_padded, 1, plan.lag_step,
+                              plan.lags.size, centre, stream)
+    return MacroAutocorrelation.from_sums(plan, g.sum, g.sumsq, g.lagged, nchains, centre)
+
+
+class Marginals:
+    """The marginal distributions of a trace as TestMarginalization.C histograms them, from the device counts of
+    smcmc_trace_ranges / smcmc_marginal_histograms (include/smcmc.h has the bin rule):
+      lo, hi [dim]                 the ranges of the dimensions over the sampled slots (macro :45-63)
+      n1, lo1, hi1 [dim]; counts1 [dim][n1 + 2]               the 1-D axes and counts (0 / n1 + 1: under- / overflow)
+      pair_dims [P]; n2, lo2, hi2 [P]; counts2 [P][P][n2 + 2][n2 + 2]   table (p, q): x = pair_dims[p], y = pair_dims[q]
+    Counts are unsigned 64-bit integers and exact.  Counts of several ranks filled on identical axes add (`+`); their
+    ranges combine beforehand with merge_ranges.  Everything derived here is host-side numpy."""
+
+    def __init__(self, lo, hi, nslots, nchains, lo1=None, hi1=None, counts1=None, pair_dims=None, lo2=None, hi2=None,
+                 counts2=None):
+        self.lo, self.hi, self.nslots, self.nchains = _f64(lo), _f64(hi), int(nslots), int(nchains)
+        self.lo1 = None if lo1 is None else _f64(lo1)
+        self.hi1 = None if hi1 is None else _f64(hi1)
+        self.counts1 = None if counts1 is None else np.array(counts1, dtype=np.uint64)
+        self.pair_dims = None if pair_dims is None else np.array(pair_dims, dtype=np.int32)
+        self.lo2 = None if lo2 is None else _f64(lo2)
+        self.hi2 = None if hi2 is None else _f64(hi2)
+        self.counts2 = None if counts2 is None else np.array(counts2, dtype=np.uint64)
+
+    @property
+    def n1(self): return 0 if self.counts1 is None else self.counts1.shape[1] - 2
+
+    @property
+    def n2(self): return 0 if self.counts2 is None else self.counts2.shape[2] - 2
+
+    @staticmethod
+    def _edges(lo, hi, n):
+        return lo[:, None] + (hi - lo)[:, None] * (np.arange(n + 1) / float(n))[None, :]
+
+    @property
+    def edges1(self):
+        """[dim][n1 + 1]: the bin edges of every 1-D axis (for plotting; the counting used the bin rule, not these)."""
+        return None if self.counts1 is None else self._edges(self.lo1, self.hi1, self.n1)
+
+    @property
+    def edges2(self):
+        """[P][n2 + 1]: the bin edges of the axis of every pair dimension."""
+        return None if self.counts2 is None else self._edges(self.lo2, self.hi2, self.n2)
+
+    @staticmethod
+    def _same(a, b):
+        return (a is None and b is None) or (a is not None and b is not None and a.shape == b.shape and np.array_equal(a, b))
+
+    def __add__(self, other):
+        if self.nslots != other.nslots:
+            raise ValueError("traces of different lengths do not pool")
+        for name in ("lo", "hi", "lo1", "hi1", "pair_dims", "lo2", "hi2"):
+            if not self._same(getattr(self, name), getattr(other, name)):
+                raise ValueError("histograms add only on identical bins and ranges (%s differs)" % name)
+        if (self.n1, self.n2) != (other.n1, other.n2):
+            raise ValueError("histograms add only on identical bins and ranges (the numbers of bins differ)")
+        return Marginals(self.lo, self.hi, self.nslots, self.nchains + other.nchains, self.lo1, self.hi1,
+                         None if self.counts1 is None else self.counts1 + other.counts1, self.pair_dims, self.lo2, self.hi2,
+                         None if self.counts2 is None else self.counts2 + other.counts2)
+
+    @staticmethod
+    def merge_ranges(ranges):
+        """(lo, hi) over several ranks' (lo, hi) pairs (or Marginals): the ranges of the whole ensemble."""
+        pairs = [(r.lo, r.hi) if isinstance(r, Marginals) else (_f64(r[0]), _f64(r[1])) for r in ranges]
+        lo, hi = pairs[0][0].copy(), pairs[0][1].copy()
+        for a, b in pairs[1:]:
+            lo, hi = np.minimum(lo, a), np.maximum(hi, b)
+        return lo, hi
+
+    @staticmethod
+    def macro_sample_stride(nslots):
+        """The stride of the macro's range loop (`entry += 0.001*entries` on an int, then ++entry; :54-62)."""
+        return 1 + int(0.001 * int(nslots))
+
+    @staticmethod
+    def macro_axes(lo, hi, pair_dims):
+        """The macro's axes from per-dimension ranges: ((absMin, absMax) of :52-53, 59-60, (lo2, hi2) of the pair
+        dimensions: the dimension's range widened by 5 % of its width on both sides, :85-89)."""
+        lo, hi = _f64(lo), _f64(hi)
+        abs_min = min(1e20, float(np.min(lo)))
+        abs_max = max(-1e20, float(np.max(hi)))
+        p = np.asarray(pair_dims, dtype=np.int64)
+        r = 0.05 * (hi[p] - lo[p])
+        return (abs_min, abs_max), (lo[p] - r, hi[p] + r)
+
+    def macro_ranges(self, pair_dims=None):
+        """macro_axes of this object's ranges (pair_dims: its own, or the macro's first min(dim, 10) dimensions)."""
+        if pair_dims is None:
+            pair_dims = self.pair_dims if self.pair_dims is not None else np.arange(min(self.lo.size, 10))
+        return self.macro_axes(self.lo, self.hi, pair_dims)
+
+    def density(self, d):
+        """[n1]: the in-range counts of dimension d over (all points x bin width): a density that integrates to the
+        in-range fraction."""
+        c = self.counts1[d].astype(np.float64)
+        return c[1:-1] / (c.sum() * (self.hi1[d] - self.lo1[d]) / self.n1)
+
+    def quantile(self, d, q):
+        """The q-quantile of dimension d from its histogram: linear interpolation inside the bin where the cumulative
+        count crosses q x (all points); underflow counts as sitting on lo1[d], overflow on hi1[d].  The resolution is
+        one bin."""
+        c = self.counts1[d].astype(np.float64)
+        n, lo, hi = self.n1, float(self.lo1[d]), float(self.hi1[d])
+        target = float(q) * c.sum()
+        cum = np.cumsum(c[:-1])                 # cum[k]: points below edge k (the underflow included)
+        if target <= cum[0]:
+            return lo
+        if target > cum[n]:
+            return hi
+        k = int(np.searchsorted(cum, target, side="left"))     # first edge with cum >= target: inside bin k
+        return lo + (hi - lo) * ((k - 1) + (target - cum[k - 1]) / c[k]) / n
+
+    def interval(self, d, level=0.68):
+        """The central credible interval of dimension d holding `level` of the points (to one bin)."""
+        return self.quantile(d, 0.5 * (1.0 - level)), self.quantile(d, 0.5 * (1.0 + level))
+
+
+def _marginals(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchains_padded, n1, n2, pair_dims, sample_stride,
+               ranges, stream):
+    """Ranges (unless given) and then the fill with the macro's axes: the body of the engines' Marginals methods."""
+    up = C.POINTER(C.c_uint64)
+    trace, nslots, st = C.c_void_p(int(trace_ptr)), int(nslots), C.c_void_p(int(stream))
+    if pair_dims is None:
+        pair_dims = np.arange(min(dim, 10))                        # the macro's "only doing 10" (:39-43)
+    pair_dims = np.ascontiguousarray(pair_dims, dtype=np.int32)
+    if ranges is None:
+        if sample_stride is None:
+            sample_stride = Marginals.macro_sample_stride(nslots)
+        lo, hi = np.zeros(dim), np.zeros(dim)
+        check(lib.smcmc_trace_ranges(trace, nslots, dim, dim_stride, nchains, nchains_padded, int(sample_stride), _ptr(lo),
+                                     _ptr(hi), st))
+    else:
+        lo, hi = _f64(ranges[0]), _f64(ranges[1])
+        if lo.shape != (dim,) or hi.shape != (dim,):
+            raise ValueError("ranges must be (lo[dim], hi[dim])")
+    (abs_min, abs_max), (lo2, hi2) = Marginals.macro_axes(lo, hi, pair_dims)
+    lo1, hi1 = np.full(dim, abs_min), np.full(dim, abs_max)
+    lo2, hi2 = _f64(lo2), _f64(hi2)
+    P = int(pair_dims.size)
+    counts1 = np.zeros((dim, n1 + 2), dtype=np.uint64) if n1 else None
+    counts2 = np.zeros((P, P, n2 + 2, n2 + 2), dtype=np.uint64) if P else None
+    check(lib.smcmc_marginal_histograms(trace, nslots, dim, dim_stride, nchains, nchains_padded, int(n1), _ptr(lo1), _ptr(hi1),
+                                        counts1.ctypes.data_as(up) if n1 else None, P,
+                                        pair_dims.ctypes.data_as(C.POINTER(C.c_int32)), int(n2), _ptr(lo2), _ptr(hi2),
+                                        counts2.ctypes.data_as(up) if P else None, st))
+    return Marginals(lo, hi, nslots, nchains, lo1 if n1 else None, hi1 if n1 else None, counts1,
+                     pair_dims if P else None, lo2 if P else None, hi2 if P else None, counts2)
+
+
+class TraceMoments:
+    """The mean and covariance of a saved trace as MakeCovariance.C:63-89 takes them, from the raw sums of
+    smcmc_trace_moments about `centre`: sum[d] = sum y_d, sumsq[i][j] = sum y_i y_j, y = x - centre, over
+    n = nslots * nchains points.
+      mean         centre + sum / n
+      covariance   sumsq / n - (sum / n)(sum / n)^T: the macro's :84 taken about the centre (a covariance does not
+                   depend on the point it is taken about; about a point near the mean the difference cancels less)
+      spread       sqrt(diag covariance): the errors of the macro's TProfile in its "S" option (:58-60)
+      correlation  covariance / (spread_i spread_j)
+    Sums of several ranks add (`+`): the right operand is re-centred on the left one's centre first."""
+
+    def __init__(self, total, sumsq, nslots, nchains, centre=None):
+        self.sum, self.sumsq = _f64(total).copy(), _f64(sumsq).copy()
+        self.nslots, self.nchains = int(nslots), int(nchains)
+        self.centre = np.zeros(self.sum.size) if centre is None else _f64(centre).copy()
+        if self.sumsq.shape != (self.sum.size, self.sum.size) or self.centre.shape != self.sum.shape:
+            raise ValueError("sum[dim], sumsq[dim][dim] and centre[dim] do not fit together")
+
+    @property
+    def n(self):
+        return float(self.nslots) * float(self.nchains)
+
+    def about(self, centre):
+        """The same sums taken about another point: with s = old centre - new centre, y' = y + s."""
+        centre = _f64(centre)
+        s, n = self.centre - centre, self.n
+        total = self.sum + n * s
+        sumsq = self.sumsq + np.outer(s, self.sum) + np.outer(self.sum, s) + n * np.outer(s, s)
+        return TraceMoments(total, sumsq, self.nslots, self.nchains, centre)
+
+    def __add__(self, other):
+        if self.nslots != other.nslots:
+            raise ValueError("traces of different lengths do not pool")
+        o = other if np.array_equal(other.centre, self.centre) else other.about(self.centre)
+        return TraceMoments(self.sum + o.sum, self.sumsq + o.sumsq, self.nslots, self.nchains + o.nchains, self.centre)
+
+    @property
+    def mean(self):
+        return self.centre + self.sum / self.n
+
+    @property
+    def covariance(self):
+        m = self.sum / self.n
+        return self.sumsq / self.n - np.outer(m, m)
+
+    @property
+    def spread(self):
+        return np.sqrt(np.diag(self.covariance))
+
+    @property
+    def correlation(self):
+        s = self.spread
+        return self.covariance / np.outer(s, s)
+
+
+def _trace_moments(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchains_padded, centre, stream):
+    """The body of the engines' TraceMoments methods."""
+    c = None if centre is None else _f64(centre)
+    if c is not None and c.shape != (dim,):
+        raise ValueError("centre must be [dim]")
+    total, sumsq = np.zeros(dim), np.zeros((dim, dim))
+    check(lib.smcmc_trace_moments(C.c_void_p(int(trace_ptr)), int(nslots), dim, dim_stride, nchains, nchains_padded,
+                                  None if c is None else _ptr(c), _ptr(total), _ptr(sumsq), C.c_void_p(int(stream))))
+    return TraceMoments(total, sumsq, nslots, nchains, c)
+
+
+class Convergence:
+    """Split R-hat and the multi-chain effective sample size of a saved trace, from the raw sums of
+    smcmc_trace_convergence (include/smcmc.h has the definition): every chain is cut into segments of L slots, M
+    segment-chains in all, y = x - centre, s1_m the sum of segment-chain m and z = y - s1_m / L:
+      sum[d] = sum_m s1_m,  sumsq_of_sums[d] = sum_m s1_m^2,  within[k][d] = sum_m sum_{t >= k} z_t z_(t-k)
+      W             within[0] / (M (L - 1)): the mean within-chain variance
+      var_of_means  (sumsq_of_sums / L^2 - (sum / L)^2 / M) / (M - 1): the variance of the segment means (B / L)
+      var_plus      (L - 1) / L W + var_of_means
+      rhat()        sqrt(var_plus / W) (Gelman-Rubin; the split form when the segments are halves); NaN where W is 0 or
+                    M < 2
+      rho()         [lag][dim], 1 - (W - within[k] / (M L)) / var_plus for the lags below min(64, L)
+      tau()         Geyer's initial monotone sequence (BDA3 section 11.5, Vehtari et al. 2021): the pairs
+                    P_j = rho[2j] + rho[2j + 1] up to the first negative one, P_j = min(P_j, P_(j-1)), -1 + 2 sum P_j
+      ess()         M L / tau()
+      truncated()   per dimension: the pairs ran out at the last available lag before one turned negative (the
+                    autocorrelation outlives the 64 lags, or L): ess() is then an upper bound
+      mean()        centre + sum / (M L)
+    sumsq_of_sums / L^2 - (sum / L)^2 / M cancels like any E[yy] - E[y]^2: take the sums about a centre near the mean,
+    e.g. TraceMoments(...).mean from one earlier pass.  Sums of several ranks add (`+`) when L and the centre agree."""
+
+    def __init__(self, total, sumsq_of_sums, within, L, M, centre=None):
+        self.sum, self.sumsq_of_sums, self.within = _f64(total).copy(), _f64(sumsq_of_sums).copy(), _f64(within).copy()
+        self.L, self.M = int(L), int(M)
+        self.centre = np.zeros(self.sum.size) if centre is None else _f64(centre).copy()
+        if (self.sum.ndim != 1 or self.sumsq_of_sums.shape != self.sum.shape or self.centre.shape != self.sum.shape
+                or self.within.ndim != 2 or self.within.shape[1] != self.sum.size):
+            raise ValueError("sum[dim], sumsq_of_sums[dim], within[lag][dim] and centre[dim] do not fit together")
+
+    def __add__(self, other):
+        if self.L != other.L:
+            raise ValueError("segments of different lengths do not pool")
+        if not np.array_equal(self.centre, other.centre):
+            raise ValueError("sums about different centres do not add")
+        return Convergence(self.sum + other.sum, self.sumsq_of_sums + other.sumsq_of_sums, self.within + other.within,
+                           self.L, self.M + other.M, self.centre)
+
+    @property
+    def W(self):
+        return self.within[0] / (float(self.M) * (self.L - 1))
+
+    @property
+    def var_of_means(self):
+        if self.M < 2:
+            return np.full(self.sum.size, np.nan)
+        L, M = float(self.L), float(self.M)
+        return (self.sumsq_of_sums / (L * L) - (self.sum / L) ** 2 / M) / (M - 1.0)
+
+    @property
+    def var_plus(self):
+        return (self.L - 1.0) / self.L * self.W + self.var_of_means
+
+    def rhat(self):
+        W = self.W
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(W == 0.0, np.nan, np.sqrt(self.var_plus / W))
+
+    def rho(self):
+        """[lag][dim]"""
+        nlag = min(self.within.shape[0], self.L)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return 1.0 - (self.W[None, :] - self.within[:nlag] / (float(self.M) * self.L)) / self.var_plus[None, :]
+
+    def _geyer(self):
+        """(tau[dim], truncated[dim])"""
+        rho = self.rho()
+        npairs, dim = rho.shape[0] // 2, rho.shape[1]
+        tau, truncated = np.empty(dim), np.zeros(dim, dtype=bool)
+        for d in range(dim):
+            total, last, j = 0.0, np.inf, 0
+            while j < npairs:
+                pair = rho[2 * j, d] + rho[2 * j + 1, d]
+                if pair < 0.0:
+                    break
+                last = min(pair, last) if pair == pair else pair           # a NaN pair makes tau NaN
+                total += last
+                j += 1
+            tau[d], truncated[d] = -1.0 + 2.0 * total, j == npairs
+        return tau, truncated
+
+    def tau(self):
+        return self._geyer()[0]
+
+    def truncated(self):
+        return self._geyer()[1]
+
+    def ess(self):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return float(self.M) * self.L / self.tau()
+
+    def mean(self):
+        return self.centre + self.sum / (float(self.M) * self.L)
+
+
+def _convergence(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchains_padded, nsegments, centre, stream):
+    """The body of the engines' Convergence methods."""
+    c = None if centre is None else _f64(centre)
+    if c is not None and c.shape != (dim,):
+        raise ValueError("centre must be [dim]")
+    nslots, nsegments = int(nslots), int(nsegments)
+    total, sumsq, within = np.zeros(dim), np.zeros(dim), np.zeros((_capi.AUTOCORR_LAGS, dim))
+    check(lib.smcmc_trace_convergence(C.c_void_p(int(trace_ptr)), nslots, dim, dim_stride, nchains, nchains_padded,
+                                      nsegments, None if c is None else _ptr(c), None, _ptr(total), _ptr(sumsq),
+                                      _ptr(within), C.c_void_p(int(stream))))
+    return Convergence(total, sumsq, within, nslots // nsegments, nsegments * nchains, c)
+
+
+def cholesky_chain(mean, covariance, nslots, nchains, seed=20240607, chain_offset=0, dim_stride=None, stream=0):
+    """The Gaussian stand-in chain of CholeskyChain.C:18-66, filled on the device: covariance = U^T U, every
+    (slot, chain) one draw mean + sum_i r_i U(i, :) on the random stream (seed, chain_offset + chain, slot).  Returns
+    (trace, U): a torch tensor [nslots][dim_stride][nchains_padded] on the current device (rows >= dim and lanes >=
+    nchains are NaN), which the reducers take as it is through trace.data_ptr(), and the decomposition [dim][dim].
+    A covariance that is not positive definite raises SmcmcError (SMCMC_ERR_RUNTIME)."""
+    import torch
+    lib = _capi.load()
+    mean, covariance = _f64(mean), _f64(covariance)
+    dim = mean.size
+    if mean.ndim != 1 or covariance.shape != (dim, dim):
+        raise ValueError("mean must be [dim] and covariance [dim][dim]")
+    dim_stride = dim if dim_stride is None else int(dim_stride)
+    nchains, nslots = int(nchains), int(nslots)
+    npad = (nchains + 63) // 64 * 64
+    if not torch.cuda.is_available():   # the fill is a device kernel: there is no host version of it
+        raise SmcmcError(_capi.ERR_NO_DEVICE, lib.smcmc_status_string(_capi.ERR_NO_DEVICE).decode())
+    trace = torch.full((nslots, dim_stride, npad), float("nan"), dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    U = np.zeros((dim, dim))
+    st = lib.smcmc_cholesky_chain(_ptr(mean), _ptr(covariance), dim, nslots, nchains, npad, dim_stride, int(seed),
+                                  int(chain_offset), C.c_void_p(trace.data_ptr()), _ptr(U), C.c_void_p(int(stream)))
+    if st != _capi.OK:
+        raise SmcmcError(st, lib.smcmc_status_string(st).decode())
+    return trace, U

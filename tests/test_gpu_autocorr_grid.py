@@ -266,6 +266,10 @@ def test_hmc_and_vaat_traces(gpu):
         assert (m.plan.max_lag, m.plan.bins, m.plan.lag_step) == (56, 56, 1)
         assert m.autocorr.shape == (d, 56) and np.all(np.isnan(m.autocorr[:, 0])) and np.all(np.isfinite(m.autocorr[:, 1:]))
         assert np.array_equal(m.lagged, g.lagged[:55])
+    # the contiguous reducer on the variable-at-a-time trace: the bits of the grid at step 1
+    old = v.AutocorrelationSums(sx.data_ptr(), slots)
+    same = v.AutocorrelationGrid(sx.data_ptr(), slots, lag_first=0, lag_step=1, nlags=64)
+    assert np.array_equal(same.lagged, old.lagged) and np.array_equal(same.sum, old.sum)
 
 
 def test_device_sums_reject_bad_arguments(gpu):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Timing of the device sums behind split R-hat and the multi-chain ESS (smcmc_trace_convergence: chain_sums_kernel,
-within_partial_kernel<0> and <32>, within_reduce_kernel) beside existing code that reads the same bytes in the same
+within_partial_kernel<0> and <32>, ordered_rows_reduce_kernel) beside existing code that reads the same bytes in the same
 process: the autocorrelation reducer (smcmc_autocorrelation_sums: autocorr_partial_kernel<0> and <32>, whose register
 shape the second pass shares, and its reduction).
 
