@@ -39,9 +39,19 @@ namespace smcmc {
 // moment contraction within 4 x 4 tiles.  build.py reads this list.
 #define SMCMC_FOR_EACH_DP(X) X(7) X(15) X(31) X(47) X(50) X(63)
 
+#define SMCMC_DP_ENTRY(n) n,
+constexpr int kDpMacroList[] = {SMCMC_FOR_EACH_DP(SMCMC_DP_ENTRY)};
+#undef SMCMC_DP_ENTRY
+constexpr bool dp_lists_agree() {
+    if (sizeof(kDpMacroList) / sizeof(kDpMacroList[0]) != (size_t)kNumDpFamilies) return false;
+    for (int f = 0; f < kNumDpFamilies; ++f)
+        if (kDpMacroList[f] != kDpFamilies[f]) return false;
+    return true;
+}
+static_assert(dp_lists_agree(), "kDpFamilies of smcmc_step_deal.h restates SMCMC_FOR_EACH_DP: keep the two alike");
+
 constexpr int kWave = 64;
-constexpr int kXStride = 66;   // doubles per LDS row: stride = 2 (mod 32) keeps both the lane=chain
-                               // ds_read/ds_write_b64 and the MFMA-operand ds_read_b64 conflict-free
+// (kXStride, the doubles per LDS row of the accepted point, lives with its layout: XLayout of smcmc_step_deal.h)
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
@@ -157,16 +167,17 @@ __device__ __forceinline__ void piece_ready(f64x2 (&q)[kPiece / 2]) {
 // accepted point per lane (plus the strip's), inline assembly like the piece reads -- issued in the middle of a piece,
 // covered by the next piece's piece_ready, consumed pieces later (operands_ready ties them behind that wait).  Read and
 // used on the spot they cost the LDS latency sixteen times per step.
-template <int T, int KK, int t = 0>
+// KQ: bytes from a k-quad's four lanes of the image to the next one's (4 * 8 * XLayout::LANE).
+template <int T, int KK, int KQ, int t = 0>
 __device__ __forceinline__ void fetch_operands(const uint32_t (&xaddr)[T], double (&raw)[T]) {
     if constexpr (t < T) {
-        asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(raw[t]) : "v"(xaddr[t]), "n"(32 * KK));
-        fetch_operands<T, KK, t + 1>(xaddr, raw);
+        asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(raw[t]) : "v"(xaddr[t]), "n"(KQ * KK));
+        fetch_operands<T, KK, KQ, t + 1>(xaddr, raw);
     }
 }
-template <int KK>
+template <int KK, int KQ>
 __device__ __forceinline__ void fetch_operand(uint32_t addr, double& raw) {
-    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(raw) : "v"(addr), "n"(32 * KK));
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(raw) : "v"(addr), "n"(KQ * KK));
 }
 template <int T, int t = 0>
 __device__ __forceinline__ void operands_ready(double (&raw)[T], double& raws) {
@@ -396,21 +407,21 @@ __device__ __forceinline__ double loglike(const double (&p)[DP], cptr_f64 prm, i
 // SPECIAL = the variant that also knows uniform per-dimension proposals, the scan of one dimension
 // (TSimpleMCMC.H:685-716) and the read-back of the proposed point (:514); kept out of the common kernels, whose
 // register allocation it disturbs.
-// The quadratic form (TDummyLogLikelihood.H:24-28) of a point held in a column of LDS, xq[j * kXStride]:
-// the D^2-term running sum needs every p[j] for every i, which a register array can only give to fully
+// The quadratic form (TDummyLogLikelihood.H:24-28) of a point held in a column of LDS, xq[XL::row(j)] (XL: its
+// XLayout): the D^2-term running sum needs every p[j] for every i, which a register array can only give to fully
 // unrolled code (50 x 50 terms: minutes of compile time per kernel) -- a rolled outer loop indexes it
 // dynamically and the compiler moves it to scratch memory.  From LDS the outer loop can stay rolled.
-template <int DP, bool EXACT>
+template <int DP, bool EXACT, typename XL>
 __device__ __forceinline__ double loglike_quadform_lds(const double* xq, cptr_f64 prm) {
     double logl = 0.0;
 #pragma nounroll
     for (int i = 0; i < DP; ++i) {
-        const double h = 0.5 * xq[i * kXStride];
+        const double h = 0.5 * xq[XL::row(i)];
         cptr_f64 ep = prm + i * DP;
 #pragma unroll
         for (int j = 0; j < DP; ++j) {
             const double e = ep[j];
-            const double pj = xq[j * kXStride];
+            const double pj = xq[XL::row(j)];
             if constexpr (EXACT) logl -= h * e * pj;
             else logl = SMCMC_FMA(-(h * e), pj, logl);
         }
@@ -475,9 +486,22 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     constexpr int T = Geo<DP>::T;
     constexpr int NT = Geo<DP>::NT;
     constexpr int NB = Geo<DP>::NB;
-    constexpr int ROWS = MOMENTS ? Geo<DP>::ROWS_MOMENTS : DP;
     typedef ULayout<DP, FULLU> UL;
-    __shared__ double xs[ROWS * kXStride];   // accepted point, x[row][lane]
+    // The headline's two instantiations (D = 50 family, iso-Gaussian, reference order, triangular decomposition, no
+    // uniform dimensions / scan; with and without the moment fold): what was measured on them alone is theirs alone, and
+    // every other instantiation keeps its code instruction for instruction.
+    constexpr bool HEADLINE = EXACT && !FULLU && !SPECIAL && DP == 50 && LIKE == SMCMC_LIKE_ISO_GAUSS;
+    // PAIRS: the accepted point in row pairs (XLayout): reload, StepRMS batch and commit are 16-byte accesses on one base
+    // address.  FIXED_AW: the accept word taken from the one Philox block that holds it for every dimension the family
+    // serves (AcceptBlock).  A dimension outside that range does not reach this kernel: the engine launches family
+    // pick_dp(dim) (smcmc_host.hpp), the smallest that holds dim, so dim lies above the family before.  Each part on
+    // the symbol it gained on by itself (profiles/step_rowpairs_notes.md): the row pairs on both, the accept block with
+    // the fold only -- alone it moved the kernel without the fold by less than the runs differ.
+    constexpr bool PAIRS = HEADLINE;
+    constexpr bool FIXED_AW = HEADLINE && MOMENTS && AcceptBlock<DP>::FIXED;
+    typedef XLayout<DP, MOMENTS, PAIRS> XL;
+    static_assert(!PAIRS || DP % 2 == 0, "a lane's 16-byte accesses cover whole row pairs of the point");
+    __shared__ alignas(PAIRS ? 16 : 8) double xs[XL::DOUBLES];   // accepted point, x[row][lane]
     __shared__ __attribute__((aligned(16))) double us[UL::SIZE];   // decomposition, every lane reads the same word
     __shared__ __attribute__((aligned(16))) double ntab[384];      // tables of the normal transform: log [64][2], angle over the half circle [128][2]
 
@@ -490,12 +514,41 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     const uint32_t gid = p.chain_offset + (uint32_t)chain;
     const cptr_f64 c0 = as_const(p.c0);
     const cptr_f64 likep = as_const(p.like);
-    double* const xcol = xs + lane;
+    double* const xcol = xs + XL::LANE * lane;   // this lane's column: row d at xcol[XL::row(d)]
+    // PAIRS only (the other layouts go row by row, where they always did): the accepted point from the column into
+    // registers / from registers into the column, a row pair per access
+    auto load_point = [&](double (&dst)[DP]) {
+#pragma unroll
+        for (int q = 0; q < DP / 2; ++q) {
+            const f64x2 v = *(const f64x2*)(xcol + XL::row(2 * q));
+            dst[2 * q] = v[0];
+            dst[2 * q + 1] = v[1];
+        }
+    };
+    auto store_point = [&](const double (&src)[DP]) {
+#pragma unroll
+        for (int q = 0; q < DP / 2; ++q) {
+            f64x2 v;
+            v[0] = src[2 * q];
+            v[1] = src[2 * q + 1];
+            *(f64x2*)(xcol + XL::row(2 * q)) = v;
+        }
+    };
+    (void)load_point;
+    (void)store_point;
 
     // Lanes past the last chain hold x = c0 so that their y = x - c0 is +0 in the
     // moment contraction; they never accept and never store.
+    if constexpr (PAIRS) {
+        // (in pairs as well: an 8-byte write of a column that is 16 bytes from lane to lane is a two-way bank conflict)
+        double xin[DP];
 #pragma unroll
-    for (int d = 0; d < DP; ++d) xcol[d * kXStride] = active ? p.x[(size_t)d * NP + chain] : c0[d];
+        for (int d = 0; d < DP; ++d) xin[d] = active ? p.x[(size_t)d * NP + chain] : c0[d];
+        store_point(xin);
+    } else {
+#pragma unroll
+        for (int d = 0; d < DP; ++d) xcol[XL::row(d)] = active ? p.x[(size_t)d * NP + chain] : c0[d];
+    }
 
     double* lf = p.lane_f64 + chain;
     int32_t* li = p.lane_i32 + chain;
@@ -554,16 +607,26 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
             for (int t = 0; t < T; ++t) accs[t] = p.gacc[(((size_t)group * NT + NT16 + t) * 4) * kWave + lane];
             const int r = 16 * Geo<DP>::T16 + (lane & 3);
             c0s = (r < DP) ? p.c0[r] : 0.0;
-            xsrow = ((r <= DP) ? r : DP) * kXStride + (lane >> 4);
+            xsrow = XL::row((r <= DP) ? r : DP) + XL::LANE * (lane >> 4);
         }
         // row DP carries the constant 1 (sum y and the point count come out of the
         // same contraction); tile rows above it are zero and are not stored
-        xcol[DP * kXStride] = active ? 1.0 : 0.0;
+        // The rows the image holds above it -- in row pairs the ones row's partner -- are +0: no lane reads them (the
+        // operand reads clamp to the ones row), but nothing in the image is left unwritten.  PAIRS: one 16-byte write.
+        if constexpr (PAIRS) {
+            static_assert(XL::HELD == DP + 2, "the ones row and its partner are one pair");
+            f64x2 ones;
+            ones[0] = active ? 1.0 : 0.0;
+            ones[1] = 0.0;
+            *(f64x2*)(xcol + XL::row(DP)) = ones;
+        } else {
+            xcol[XL::row(DP)] = active ? 1.0 : 0.0;
+        }
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             const int r = 16 * t + (lane & 15);
             c0r[t] = (r < DP) ? p.c0[r] : 0.0;
-            xrow[t] = ((r <= DP) ? r : DP) * kXStride + (lane >> 4);
+            xrow[t] = XL::row((r <= DP) ? r : DP) + XL::LANE * (lane >> 4);
         }
     }
     __syncthreads();
@@ -574,6 +637,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     // spilled the prefetched operands behind their reads in one variant or another (the build's listing check
     // refused them)
     constexpr bool OPF = MOMENTS && T >= 3 && kAsmReads<DP> && DP <= 50 && !FULLU && !SPECIAL;
+    constexpr int KQ = 4 * 8 * XL::LANE;   // bytes from a k-quad's four lanes of the image to the next one's
     double raw[OPF ? T : 1], raws = 0.0;
     uint32_t xaddr[OPF ? T : 1], xsaddr = 0;
     if constexpr (OPF) {
@@ -614,7 +678,8 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     // The kernel without the fold measured 0.7 % slower with the two (profiles/step_boundary_notes.md) and keeps its top.
     constexpr bool TOP_FREE = BOUNDARY && MOMENTS;
     double x0 = 0.0;
-    if constexpr (BOUNDARY) x0 = xcol[0];
+    if constexpr (BOUNDARY && PAIRS) x0 = (*(const f64x2*)(xcol + XL::row(0)))[0];   // (the pair: no bank conflict)
+    else if constexpr (BOUNDARY) x0 = xcol[XL::row(0)];
     if constexpr (TOP_FREE) asm volatile("" : "+v"(x0));
 
     // StepRMS window, likelihood, Metropolis test and accept copy of one step
@@ -631,8 +696,8 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         if constexpr (SWAP) {
 #pragma unroll
             for (int d = 0; d < DP; ++d) {
-                const double t = xcol[d * kXStride];
-                xcol[d * kXStride] = xp[d];
+                const double t = xcol[XL::row(d)];
+                xcol[XL::row(d)] = xp[d];
                 xp[d] = t;
             }
         }
@@ -647,8 +712,11 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         double xold[RMS_AHEAD ? DP : 1];
         if constexpr (RMS_AHEAD) {
             if (p.step_rms_window > 0) {
+                if constexpr (PAIRS) load_point(xold);
+                else {
 #pragma unroll
-                for (int d = 0; d < DP; ++d) xold[d] = xcol[d * kXStride];
+                    for (int d = 0; d < DP; ++d) xold[d] = xcol[XL::row(d)];
+                }
             }
             __builtin_amdgcn_sched_barrier(0);
             logl_prop = loglike<DP, LIKE, EXACT>(xp, likep + p.zero * (s + 1), D);
@@ -661,7 +729,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
             for (int d = 0; d < DP; ++d) {
                 double t;
                 if constexpr (RMS_AHEAD) t = xp[d] - xold[d];
-                else t = SWAP ? xcol[d * kXStride] - xp[d] : xp[d] - xcol[d * kXStride];
+                else t = SWAP ? xcol[XL::row(d)] - xp[d] : xp[d] - xcol[XL::row(d)];
                 if constexpr (EXACT) sqr += t * t;
                 else sqr = SMCMC_FMA(t, t, sqr);
             }
@@ -677,10 +745,10 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
             bool dense = p.like_rowptr == nullptr;
             if (!dense) {
                 const QuadCsr csr = {p.like_rowptr + p.zero * (s + 1), p.like_cols, p.like_vals, p.like_rows};
-                logl_prop = quadform_csr<EXACT>([&](int j) { return xcol[j * kXStride]; }, csr, D);
+                logl_prop = quadform_csr<EXACT>([&](int j) { return xcol[XL::row(j)]; }, csr, D);
                 dense = __any(!__builtin_isfinite(logl_prop));
             }
-            if (dense) logl_prop = loglike_quadform_lds<DP, EXACT>(xcol, likep + p.zero * (s + 1));
+            if (dense) logl_prop = loglike_quadform_lds<DP, EXACT, XL>(xcol, likep + p.zero * (s + 1));
         }
         else if constexpr (!RMS_AHEAD) logl_prop = loglike<DP, LIKE, EXACT>(xp, likep + p.zero * (s + 1), D);
         if constexpr (!RMS_AHEAD) SMCMC_PROF_MARK(PROF_LIKE);
@@ -708,8 +776,11 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         }
         SMCMC_PROF_MARK(PROF_TEST);
         if (take != SWAP) {   // plain: commit the proposal on accept; swapped: put the accepted point back on reject
+            if constexpr (PAIRS) store_point(xp);
+            else {
 #pragma unroll
-            for (int d = 0; d < DP; ++d) xcol[d * kXStride] = xp[d];
+                for (int d = 0; d < DP; ++d) xcol[XL::row(d)] = xp[d];
+            }
         }
         SMCMC_PROF_MARK(PROF_COMMIT);
         if constexpr (BOUNDARY) x0 = take ? xp[0] : x0;
@@ -724,7 +795,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         if (p.save_x != nullptr && ((s + 1) % p.save_stride) == 0 && active) {
             const size_t slot = (size_t)((s + 1) / p.save_stride - 1);
 #pragma unroll
-            for (int d = 0; d < DP; ++d) p.save_x[(slot * (size_t)DP + (size_t)d) * NP + chain] = xcol[d * kXStride];
+            for (int d = 0; d < DP; ++d) p.save_x[(slot * (size_t)DP + (size_t)d) * NP + chain] = xcol[XL::row(d)];
             p.save_logl[slot * NP + chain] = logl;
         }
     };
@@ -757,7 +828,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
                 val = p.scan_a + p.scan_b * ((sd & 1u) ? ns : nc);
             }
 #pragma unroll
-            for (int d = 0; d < DP; ++d) xp[d] = ((uint32_t)d == sd) ? val : xcol[d * kXStride];
+            for (int d = 0; d < DP; ++d) xp[d] = ((uint32_t)d == sd) ? val : xcol[XL::row(d)];
             const smcmc_u32x4 ablk = smcmc_draw_block(p.seed, gid, step, aw >> 2, SMCMC_STREAM_STEP);
             finish_step(s, smcmc_select_word(ablk, aw & 3u));
         }
@@ -773,14 +844,15 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         // commit of the step before in program order (one wavefront, LDS operations execute in issue order), so that the
         // commit's writes and these reads are on their way under A's divisions and `pow`.  Issued behind A they came back
         // under nothing (the compiler does not lift them over A's branches).
-        if constexpr (TOP_FREE) {
+        if constexpr (TOP_FREE && PAIRS) load_point(xp);
+        else if constexpr (TOP_FREE) {
 #pragma unroll
-            for (int d = 0; d < DP; ++d) xp[d] = xcol[d * kXStride];
+            for (int d = 0; d < DP; ++d) xp[d] = xcol[XL::row(d)];
         }
 
         // ---- A: UpdateState, scalar half (TSimpleMCMC.H:1723-1776) ----
         ++trials;
-        if constexpr (!BOUNDARY) x0 = xcol[0];
+        if constexpr (!BOUNDARY) x0 = xcol[XL::row(0)];
         const bool moved = (logl != last_value) || (x0 != last_x0);
         if (moved) ++succ;
         acc_rate *= acc_trials;
@@ -819,12 +891,13 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
 
         // ---- B: proposal (TSimpleMCMC.H:709-724) ----
         if constexpr (OPF) {
-            fetch_operands<T, 0>(xaddr, raw);
-            if constexpr (STRIP) fetch_operand<0>(xsaddr, raws);
+            fetch_operands<T, 0, KQ>(xaddr, raw);
+            if constexpr (STRIP) fetch_operand<0, KQ>(xsaddr, raws);
         }
-        if constexpr (!TOP_FREE) {
+        if constexpr (!TOP_FREE && PAIRS) load_point(xp);
+        else if constexpr (!TOP_FREE) {
 #pragma unroll
-            for (int d = 0; d < DP; ++d) xp[d] = xcol[d * kXStride];
+            for (int d = 0; d < DP; ++d) xp[d] = xcol[XL::row(d)];
         }
         uint32_t uword = 0;
         // The LDS image of U never changes, so the compiler would hoist all of its reads out
@@ -860,7 +933,10 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
 
             if constexpr (!PIPE) draw_and_fetch(bc);
             smcmc_u32x4& blk = blks[b & 1];
-            if ((uint32_t)b == (aw >> 2)) uword = smcmc_select_word(blk, aw & 3u);
+            // FIXED_AW: the accept word lies in block AcceptBlock<DP>::BLOCK for every dimension this kernel is launched at
+            if constexpr (FIXED_AW) {
+                if constexpr (b == AcceptBlock<DP>::BLOCK) uword = smcmc_select_word(blk, aw & 3u);
+            } else if ((uint32_t)b == (aw >> 2)) uword = smcmc_select_word(blk, aw & 3u);
             // LDS reads of the block, in this order (they return in issue order): the table entries of its two pairs of
             // normals (issued here, or during the last piece of the block before), then the first piece of U, which
             // stays in flight under the normals' arithmetic
@@ -961,8 +1037,8 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
                             }
                             if constexpr (m + 1 < m_hi) __builtin_amdgcn_sched_barrier(0);
                             if constexpr (kStepDealPlan<DP>.pf_after[m]) {
-                                fetch_operands<T, kk + 1>(xaddr, raw);
-                                fetch_operand<kk + 1>(xsaddr, raws);
+                                fetch_operands<T, kk + 1, KQ>(xaddr, raw);
+                                fetch_operand<kk + 1, KQ>(xsaddr, raws);
                             }
                         });
                     } else {
@@ -978,12 +1054,12 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
 #pragma unroll
                                 for (int t = 0; t < T; ++t) {
                                     if constexpr (OPF) ma[t] = raw[t] - c0r[t];
-                                    else ma[t] = xs[xrow[t] + 4 * kk] - c0r[t];
+                                    else ma[t] = xs[xrow[t] + 4 * XL::LANE * kk] - c0r[t];
                                     if (16 * t + 15 > DP) ma[t] = (16 * t + (lane & 15) <= DP) ? ma[t] : 0.0;   // rows past the ones row
                                 }
                                 if constexpr (STRIP) {
                                     if constexpr (OPF) ms = raws - c0s;
-                                    else ms = xs[xsrow + 4 * kk] - c0s;
+                                    else ms = xs[xsrow + 4 * XL::LANE * kk] - c0s;
                                     ms = (16 * Geo<DP>::T16 + (lane & 3) <= DP) ? ms : 0.0;
                                 }
                             }
@@ -1002,8 +1078,8 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
                                 // (behind the k-quad's first matrix instruction: in its shadow) the next k-quad's first
                                 // matrix instruction sits in a later piece
                                 static_assert(((long)(kk + 1) * NT * G) / NM > g, "operand prefetch needs a piece boundary");
-                                fetch_operands<T, kk + 1>(xaddr, raw);
-                                if constexpr (STRIP) fetch_operand<kk + 1>(xsaddr, raws);
+                                fetch_operands<T, kk + 1, KQ>(xaddr, raw);
+                                if constexpr (STRIP) fetch_operand<kk + 1, KQ>(xsaddr, raws);
                             }
                         });
                     }
@@ -1017,7 +1093,8 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
             });
             SMCMC_PROF_MARK(PROF_PIECES);
         });
-        if ((aw >> 2) >= (uint32_t)NB) {
+        // an accept word behind the blocks the proposal drew (never with FIXED_AW: its block is one of them)
+        if (!FIXED_AW && (aw >> 2) >= (uint32_t)NB) {
             smcmc_u32x4 blk = smcmc_draw_block(p.seed, gid, step, aw >> 2, SMCMC_STREAM_STEP);
             uword = smcmc_select_word(blk, aw & 3u);
         }
@@ -1060,7 +1137,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     }
     if (active) {
 #pragma unroll
-        for (int d = 0; d < DP; ++d) p.x[(size_t)d * NP + chain] = xcol[d * kXStride];
+        for (int d = 0; d < DP; ++d) p.x[(size_t)d * NP + chain] = xcol[XL::row(d)];
         lf[SMCMC_LANE_LOGL * NP] = logl;
         lf[SMCMC_LANE_SIGMA * NP] = sigma;
         lf[SMCMC_LANE_ACCEPTANCE * NP] = acc_rate;

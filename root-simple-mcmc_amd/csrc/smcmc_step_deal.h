@@ -1,8 +1,9 @@
-// smcmc_step_deal.h -- the compile-time geometry of the step kernel (tiles of the moment fold, LDS layout of the
-// decomposition, the pieces of a step) and the plan that deals the fold's matrix instructions over the pieces.
+// smcmc_step_deal.h -- the compile-time geometry of the step kernel (tiles of the moment fold, LDS layouts of the
+// accepted point and of the decomposition, the Philox block of the accept word, the pieces of a step) and the plan that
+// deals the fold's matrix instructions over the pieces.
 //
-// Plain C++17, no HIP: smcmc_kernels.hip.h includes it, and so does a host program (tests/cpp/step_deal_plan.C) that
-// prints the plan and lets a test check its invariants.
+// Plain C++17, no HIP: smcmc_kernels.hip.h includes it, and so do host programs (tests/cpp/step_deal_plan.C,
+// tests/cpp/step_rowpairs_layout.C) that print the plan and the layout and let tests check their invariants.
 #pragma once
 
 namespace smcmc {
@@ -22,6 +23,62 @@ struct Geo {
     static constexpr bool STRIP = ((DP + 1) % 16 != 0) && ((DP + 1) % 16 <= 4);
     static constexpr int T16 = STRIP ? T - 1 : T;  // tile rows folded with 16x16x4
     static constexpr int NT16 = T16 * (T16 + 1) / 2;
+};
+
+// The register-array sizes the step kernels are built for, smallest first: SMCMC_FOR_EACH_DP of smcmc_kernels.hip.h, which
+// holds a static_assert that the two lists agree.  Family DP serves the dimensions from the entry before it plus one up
+// to DP (pick_dp of smcmc_host.hpp: the smallest family that holds the dimension).
+constexpr int kDpFamilies[] = {7, 15, 31, 47, 50, 63};
+constexpr int kNumDpFamilies = sizeof(kDpFamilies) / sizeof(kDpFamilies[0]);
+
+// smcmc_accept_word of include/smcmc_detmath.h (a C header without constexpr), restated: the word of a step's stream
+// that makes the Metropolis draw.  tests/cpp/step_rowpairs_layout.C holds the two against each other.
+constexpr unsigned accept_word_of(unsigned dim) { return 2u * ((dim + 1u) / 2u); }
+
+// Where the accept word of family DP lies.  FIXED: every dimension the family serves has it in the same Philox block of
+// four words, BLOCK, and that block is one of the NB the proposal draws anyway -- a kernel may then take the word from
+// that block alone, by `accept word & 3`, instead of testing every block against a run-time block number.
+template <int DP>
+struct AcceptBlock {
+    static constexpr int lowest() {   // the smallest dimension the family serves
+        int prev = 0;
+        for (int f = 0; f < kNumDpFamilies; ++f) {
+            if (kDpFamilies[f] == DP) return prev + 1;
+            prev = kDpFamilies[f];
+        }
+        return 1;                     // not a family of the list: any dimension up to DP
+    }
+    static constexpr int LOWEST = lowest();
+    static constexpr int BLOCK = (int)(accept_word_of((unsigned)DP) >> 2);
+    static constexpr bool fixed() {
+        for (int d = LOWEST; d <= DP; ++d)
+            if ((int)(accept_word_of((unsigned)d) >> 2) != BLOCK) return false;
+        return BLOCK < Geo<DP>::NB;
+    }
+    static constexpr bool FIXED = fixed();
+};
+
+// LDS image of the accepted point, x[row][lane] (lane = chain), 8-byte slots.
+//   !PAIRS  row r, lane c at double r * kXStride + c: a stride of 2 (mod 32) doubles keeps both the lane = chain
+//           ds_read / ds_write_b64 and the matrix-operand ds_read_b64 conflict-free.
+//   PAIRS   rows 2p and 2p + 1 of a lane side by side: byte (r >> 1) * PAIR_STRIDE + 16 c + 8 (r & 1).  A lane reads or
+//           writes its column in 16-byte accesses on one base address (offsets p * PAIR_STRIDE, within the 16-bit field),
+//           each quarter-wave covering the 64 banks once.  The 32 bytes of padding per pair keep the fold's operand reads
+//           conflict-free (ds_read_b64 of row 16 t + (lane & 15), lane 4 kk + (lane >> 4)): for a half-wave the dword
+//           banks are 8 (r >> 1) + 4 c + 2 (r & 1) + {0, 1} (mod 64), all distinct.
+// ROWS rows are held (the dims, and with the moment fold the ones row DP); PAIRS rounds that up to whole pairs.
+constexpr int kXStride = 66;
+template <int DP, bool MOMENTS, bool PAIRS>
+struct XLayout {
+    static constexpr int ROWS = MOMENTS ? Geo<DP>::ROWS_MOMENTS : DP;
+    static constexpr int PAIR_STRIDE = 64 * 16 + 32;                   // bytes
+    static constexpr int HELD = PAIRS ? (ROWS + 1) / 2 * 2 : ROWS;     // rows the image has room for
+    static constexpr int LANE = PAIRS ? 2 : 1;                         // doubles from a lane to the next
+    static constexpr int DOUBLES = PAIRS ? HELD / 2 * (PAIR_STRIDE / 8) : ROWS * kXStride;
+    static constexpr int BYTES = DOUBLES * 8;
+    // double index of row r in lane 0's column; lane c is LANE * c doubles further
+    static constexpr int row(int r) { return PAIRS ? (r >> 1) * (PAIR_STRIDE / 8) + (r & 1) : r * kXStride; }
+    static constexpr int offset(int r, int c) { return 8 * (row(r) + LANE * c); }   // bytes
 };
 
 // LDS image of the decomposition: row i keeps columns j0(i)..DP-1 (j0 = i rounded

@@ -3,7 +3,9 @@
 
 For a kernel symbol (a substring of the mangled name is enough) this prints every `s_waitcnt lgkmcnt(n)` of the step
 loop that lies OUTSIDE the piece region: before the loop's first and behind its last matrix instruction, or, in a kernel
-without the moment fold, before its first and behind its last `ds_read_b128`.  Next to each wait stand the LDS
+without the moment fold, before its first and behind its last hand-placed `ds_read_b128` (inline assembly: the normals'
+tables and the pieces of the decomposition; the row-pair kernels also read the accepted point 16 bytes at a time, through
+the compiler, and those reads are the boundary's).  Next to each wait stand the LDS
 operations it completes (all in flight but the n youngest: they return in issue order) and the number of vector
 instructions between the oldest of them and the wait (and between the youngest and the wait) -- what a lone wavefront
 had to issue while that operation was on its way.  A wait with few vector instructions behind an operation it covers
@@ -23,7 +25,7 @@ import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from shadow_model import cls, kernel_lines, parse  # noqa: E402
+from shadow_model import HAND, cls, kernel_lines, parse  # noqa: E402
 
 
 def step_loop(items):
@@ -67,7 +69,7 @@ def plain_step(body):
 def piece_region(body):
     marks = [i for i, (n, _) in enumerate(body) if cls(n) == "matrix"]
     if not marks:
-        marks = [i for i, (n, _) in enumerate(body) if n == "ds_read_b128"]
+        marks = [i for i, (n, ops) in enumerate(body) if n == "ds_read_b128" and ops.endswith(HAND)]
     return marks[0], marks[-1]
 
 
@@ -106,7 +108,7 @@ def main():
     ap.add_argument("listing")
     ap.add_argument("symbol")
     a = ap.parse_args()
-    loop = step_loop(parse(kernel_lines(a.listing, a.symbol)))
+    loop = step_loop(parse(kernel_lines(a.listing, a.symbol), mark_hand=True))
     body, blocks = plain_step(loop)
     waits, first, last, size = boundary_waits(body)
     print("step loop: %d instructions, piece region %d .. %d; left out: %d block(s) that store to global memory, %d instructions" %

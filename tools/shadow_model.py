@@ -36,17 +36,24 @@ def kernel_lines(path, name):
     return out
 
 
-def parse(lines):
-    """[(mnemonic, operands)] with labels as ('label', name)."""
-    items = []
+HAND = " ;hand"   # parse(mark_hand=True): the end of the operands of an instruction of an inline-assembly block
+
+
+def parse(lines, mark_hand=False):
+    """[(mnemonic, operands)] with labels as ('label', name).  mark_hand: the operands of the instructions the source
+    placed by hand (between the compiler's ;;#ASMSTART and ;;#ASMEND) end in HAND."""
+    items, hand = [], False
     for line in lines:
         m = re.match(r"^(\.LBB\w+):", line)
         if m:
             items.append(("label", m.group(1)))
             continue
+        if line.lstrip().startswith(";;#ASM"):
+            hand = line.lstrip().startswith(";;#ASMSTART")
+            continue
         m = re.match(r"^\s+([a-z][a-z_0-9]*)\s*(.*)$", line)
         if m and not line.lstrip().startswith((";", "//", ".")):
-            items.append((m.group(1), m.group(2)))
+            items.append((m.group(1), m.group(2) + (HAND if mark_hand and hand else "")))
     return items
 
 
