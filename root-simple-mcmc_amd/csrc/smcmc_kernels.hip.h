@@ -501,6 +501,11 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     constexpr bool FIXED_AW = HEADLINE && MOMENTS && AcceptBlock<DP>::FIXED;
     typedef XLayout<DP, MOMENTS, PAIRS> XL;
     static_assert(!PAIRS || DP % 2 == 0, "a lane's 16-byte accesses cover whole row pairs of the point");
+    // ZROW: the fold's tile rows past the ones row read the image's zero row (XLayout::ZERO_ROW) instead of being clamped
+    // onto the ones row and zeroed by a select, two selects per k-quad and double (profiles/step_rms_blocks_notes.md).
+    // With the fold only: the other image has no such row.
+    constexpr bool ZROW = HEADLINE && MOMENTS;
+    static_assert(!ZROW || XL::ZERO_ROW == DP + 1, "the ones row's partner is the zero row");
     __shared__ alignas(PAIRS ? 16 : 8) double xs[XL::DOUBLES];   // accepted point, x[row][lane]
     __shared__ __attribute__((aligned(16))) double us[UL::SIZE];   // decomposition, every lane reads the same word
     __shared__ __attribute__((aligned(16))) double ntab[384];      // tables of the normal transform: log [64][2], angle over the half circle [128][2]
@@ -607,12 +612,13 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
             for (int t = 0; t < T; ++t) accs[t] = p.gacc[(((size_t)group * NT + NT16 + t) * 4) * kWave + lane];
             const int r = 16 * Geo<DP>::T16 + (lane & 3);
             c0s = (r < DP) ? p.c0[r] : 0.0;
-            xsrow = XL::row((r <= DP) ? r : DP) + XL::LANE * (lane >> 4);
+            xsrow = XL::row((r <= DP) ? r : (ZROW ? XL::ZERO_ROW : DP)) + XL::LANE * (lane >> 4);
         }
         // row DP carries the constant 1 (sum y and the point count come out of the
         // same contraction); tile rows above it are zero and are not stored
-        // The rows the image holds above it -- in row pairs the ones row's partner -- are +0: no lane reads them (the
-        // operand reads clamp to the ones row), but nothing in the image is left unwritten.  PAIRS: one 16-byte write.
+        // The rows the image holds above it -- in row pairs the ones row's partner -- are +0, in idle lanes too.  ZROW: the
+        // operand reads of the tile rows past the ones row go there; otherwise no lane reads them (the operand reads clamp
+        // to the ones row), but nothing in the image is left unwritten.  PAIRS: one 16-byte write.
         if constexpr (PAIRS) {
             static_assert(XL::HELD == DP + 2, "the ones row and its partner are one pair");
             f64x2 ones;
@@ -626,7 +632,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         for (int t = 0; t < T; ++t) {
             const int r = 16 * t + (lane & 15);
             c0r[t] = (r < DP) ? p.c0[r] : 0.0;
-            xrow[t] = XL::row((r <= DP) ? r : DP) + XL::LANE * (lane >> 4);
+            xrow[t] = XL::row((r <= DP) ? r : (ZROW ? XL::ZERO_ROW : DP)) + XL::LANE * (lane >> 4);
         }
     }
     __syncthreads();
@@ -708,6 +714,12 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         // is written between the reads and the sum (two independent sums, each in its own order) so that it could run
         // under the reads; the compiler merges the two `step_rms_window > 0` blocks and puts it behind the sum in that
         // path, so one LDS latency is still exposed (profiles/step_issue_notes.md).
+        // Taking the terms block by block inside the step instead (rows 4b .. 4b+3 of the proposal are final behind the
+        // last piece of block b; two hand-placed row-pair reads per block under the block's last piece, no wait of their
+        // own, no batch) was built and measured: the 17 waits of the batch go, but the ten registers the reads and the
+        // running sum hold through the pieces push finished rows of the proposal into accumulation registers (55 - 130
+        // more copies per step), and neither kernel gained beyond the runs' spread -- the one without the fold lost 1 %
+        // (profiles/step_rms_blocks_notes.md).  The batch stays.
         constexpr bool RMS_AHEAD = BOUNDARY;
         double xold[RMS_AHEAD ? DP : 1];
         if constexpr (RMS_AHEAD) {
@@ -1020,10 +1032,11 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
 #pragma unroll
                                 for (int t = 0; t < T; ++t) {
                                     ma[t] = raw[t] - c0r[t];
-                                    if (16 * t + 15 > DP) ma[t] = (16 * t + (lane & 15) <= DP) ? ma[t] : 0.0;   // rows past the ones row
+                                    // rows past the ones row (ZROW: they read the zero row and c0r is 0 there: +0 as it stands)
+                                    if (!ZROW && 16 * t + 15 > DP) ma[t] = (16 * t + (lane & 15) <= DP) ? ma[t] : 0.0;
                                 }
                                 ms = raws - c0s;
-                                ms = (16 * Geo<DP>::T16 + (lane & 3) <= DP) ? ms : 0.0;
+                                if constexpr (!ZROW) ms = (16 * Geo<DP>::T16 + (lane & 3) <= DP) ? ms : 0.0;
                                 __builtin_amdgcn_sched_barrier(0);
                             }
                             if constexpr (tile < NT16) {

@@ -3,7 +3,8 @@
 // deals the fold's matrix instructions over the pieces.
 //
 // Plain C++17, no HIP: smcmc_kernels.hip.h includes it, and so do host programs (tests/cpp/step_deal_plan.C,
-// tests/cpp/step_rowpairs_layout.C) that print the plan and the layout and let tests check their invariants.
+// tests/cpp/step_rowpairs_layout.C, tests/cpp/step_zero_row.C) that print the plan and the layout and let tests check
+// their invariants.
 #pragma once
 
 namespace smcmc {
@@ -79,6 +80,10 @@ struct XLayout {
     // double index of row r in lane 0's column; lane c is LANE * c doubles further
     static constexpr int row(int r) { return PAIRS ? (r >> 1) * (PAIR_STRIDE / 8) + (r & 1) : r * kXStride; }
     static constexpr int offset(int r, int c) { return 8 * (row(r) + LANE * c); }   // bytes
+    // The zero row: with the moment fold in row pairs the ones row DP has a partner, row DP + 1, that the prologue writes
+    // +0 in every lane (idle ones too) and nothing writes again.  The fold's operand reads of tile rows past the ones
+    // row go there: (+0) - (+0) = +0, the bits a select of 0.0 gave.  -1: the image holds no such row.
+    static constexpr int ZERO_ROW = (PAIRS && MOMENTS && HELD > ROWS) ? ROWS : -1;
 };
 
 // LDS image of the decomposition: row i keeps columns j0(i)..DP-1 (j0 = i rounded
