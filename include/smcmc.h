@@ -73,7 +73,8 @@ typedef enum {
                                (:1721-1831, the covariance loop of :1795-1820 included) and UpdateProposal when its own
                                --fNextUpdate < 1 on an accepted step (:1824-1826).  Every chain is bit for bit the
                                reference chain on its random stream.  dim <= 63 (up to smcmc_max_perchain_dim() with
-                               SMCMC_P_PERCHAIN_WORKGROUP = 1 set first), reference-order arithmetic, Gaussian
+                               SMCMC_P_PERCHAIN_WORKGROUP = 1, up to smcmc_max_perchain_stream_dim() with
+                               SMCMC_P_PERCHAIN_STREAM = 1, set first), reference-order arithmetic, Gaussian
                                proposals in every dimension; memory 12 dim (dim + 1) + 32 dim bytes per chain.
                                The shared getters (centre, covariance, decomposition, trials, trace) answer for
                                chain 0, the setters act on every chain; smcmc_read_chain_proposal reads any chain. */
@@ -132,7 +133,19 @@ typedef enum {
                                          * per-chain engine is SMCMC_ERR_UNSUPPORTED.  Every built-in likelihood; SMCMC_LIKE_USER
                                          * when the user header defines SMCMC_USER_LIKELIHOOD_ANY_DIM.  Reads back 1 exactly when
                                          * this kernel is what runs (SMCMC_P_PERCHAIN_WAVE then reads back 0). */
-    SMCMC_P_COUNT_
+    SMCMC_P_COUNT_ = 28,                /* the number of parameters.  It keeps its place in the text behind 26, where
+                                         * tests/test_perchain_workgroup_cpu.py looks for it; parameters added since follow
+                                         * it, and its value counts them. */
+    SMCMC_P_PERCHAIN_STREAM = 27        /* SMCMC_MODE_PER_CHAIN: 1 = one chain per workgroup of 512 threads with the chain's
+                                         * covariance and decomposition STREAMED from device memory, the kernel that serves
+                                         * 63 < dim <= smcmc_max_perchain_stream_dim(); set it before smcmc_set_mode to ask for
+                                         * the mode above smcmc_max_perchain_dim().  Opt-in like SMCMC_P_PERCHAIN_WORKGROUP, over
+                                         * which it wins where both serve: the mode's images are 12 dim^2 bytes per chain, held
+                                         * per started tile of 64 chains (at dim 512: 67 MB + 134 MB per tile, for one chain
+                                         * too), plus 8 dim (dim + 1) bytes of working copies per chain.  At dim <= 63 it changes
+                                         * nothing.  Same images, same bits.  Above smcmc_max_perchain_dim() setting 0 again on a
+                                         * per-chain engine is SMCMC_ERR_UNSUPPORTED.  Likelihoods as SMCMC_P_PERCHAIN_WORKGROUP.
+                                         * Reads back 1 exactly when this kernel is what runs (the two others then read 0). */
 } smcmc_param;
 
 /* Per-chain double fields (smcmc_read_lane_f64). */
@@ -184,7 +197,8 @@ const char* smcmc_status_string(int status);
 int smcmc_version(void);
 int smcmc_max_register_dim(void);   /* largest dim of the register-resident kernels (63) */
 int smcmc_max_dim(void);            /* largest dim any kernel covers (512) */
-int smcmc_max_perchain_dim(void);   /* largest dim of SMCMC_MODE_PER_CHAIN (SMCMC_P_PERCHAIN_WORKGROUP = 1) */
+int smcmc_max_perchain_dim(void);   /* largest dim of SMCMC_MODE_PER_CHAIN without SMCMC_P_PERCHAIN_STREAM (SMCMC_P_PERCHAIN_WORKGROUP = 1) */
+int smcmc_max_perchain_stream_dim(void);   /* largest dim of SMCMC_MODE_PER_CHAIN (SMCMC_P_PERCHAIN_STREAM = 1): smcmc_max_dim() */
 /* hipStream_t to launch on (NULL = default stream). */
 int smcmc_set_stream(smcmc_engine* h, void* hip_stream);
 
@@ -241,8 +255,8 @@ int smcmc_step(smcmc_engine* h, int nsteps, int metropolis);
  * [0, dim) fAccepted, [dim, 2 dim) fProposed, [2 dim, 3 dim) the diagonal of the chain's covariance (GetCovarianceTrace,
  * TSimpleMCMC.H:961-967, is its sum in index order: the reader adds it up; SMCMC_REC_COVARIANCE_TRACE itself is 0), then
  * the scalars of smcmc_record_field.  SMCMC_MODE_PER_CHAIN with the
- * one-chain-per-wavefront kernel (SMCMC_P_PERCHAIN_WAVE) or the one-chain-per-workgroup kernel
- * (SMCMC_P_PERCHAIN_WORKGROUP); SMCMC_ERR_UNSUPPORTED otherwise.  include/TSimpleMCMC_amd.H
+ * one-chain-per-wavefront kernel (SMCMC_P_PERCHAIN_WAVE) or a one-chain-per-workgroup kernel
+ * (SMCMC_P_PERCHAIN_WORKGROUP, SMCMC_P_PERCHAIN_STREAM); SMCMC_ERR_UNSUPPORTED otherwise.  include/TSimpleMCMC_amd.H
  * runs Step() ahead with it (TSimpleMCMC.H:370-496 one call at a time is one launch and three read-backs per step). */
 typedef enum {
     SMCMC_REC_LOGL = 0, SMCMC_REC_LOGL_PROPOSED, SMCMC_REC_STEP_RMS, SMCMC_REC_LAST_ACCEPT, SMCMC_REC_TRIALS,

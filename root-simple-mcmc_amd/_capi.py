@@ -21,7 +21,7 @@ PARAMS = ["COVARIANCE_WINDOW", "COVARIANCE_DEWEIGHT", "ACCEPTANCE_WINDOW", "ACCE
           "NEXT_UPDATE", "COVARIANCE_TRIALS", "CENTER_TRIALS", "COVARIANCE_TRACE", "TOTAL_STEPS",
           "SIGMA_TRACE", "UPDATE_COUNT", "LAST_UPDATE_PATH", "EXACT_ARITHMETIC", "MOMENT_STRIDE", "MOMENT_GROUP", "KEEP_PROPOSED",
           "DEVICE_UPDATE", "OVERLAP_UPDATE", "COVARIANCE_FROZEN", "DENSE_QUADFORM", "PERCHAIN_WAVE",
-          "PERCHAIN_WORKGROUP"]
+          "PERCHAIN_WORKGROUP", "PERCHAIN_STREAM"]
 P = {name: i for i, name in enumerate(PARAMS)}
 RECORD_FIELDS = ["logl", "logl_proposed", "step_rms", "last_accept", "trials", "successes", "next_update", "acceptance",
                  "acceptance_trials", "sigma", "center_trials", "covariance_trials", "covariance_trace", "total_steps",
@@ -75,6 +75,7 @@ SIGNATURES = {
     "smcmc_max_register_dim": (C.c_int, []),
     "smcmc_max_dim": (C.c_int, []),
     "smcmc_max_perchain_dim": (C.c_int, []),
+    "smcmc_max_perchain_stream_dim": (C.c_int, []),
     "smcmc_set_stream": (C.c_int, [_H, C.c_void_p]),
     "smcmc_set_likelihood_params": (C.c_int, [_H, _dp, C.c_int]),
     "smcmc_set_mode": (C.c_int, [_H, C.c_int]),

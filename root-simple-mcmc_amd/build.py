@@ -56,6 +56,8 @@ def _units(user_flag=None, name="user"):
             else ("smcmc_perchain_wave_inst.hip", [], "perchain_wave"))
     wg = (("smcmc_perchain_wg_inst.hip", [user_flag], "perchain_wg" + tag) if user_flag
           else ("smcmc_perchain_wg_inst.hip", [], "perchain_wg"))
+    stream = (("smcmc_perchain_stream_inst.hip", [user_flag], "perchain_stream" + tag) if user_flag
+              else ("smcmc_perchain_stream_inst.hip", [], "perchain_stream"))
     units = [engine, ("smcmc_selftest.hip", [], "selftest"), ("smcmc_autocorr.hip", [], "autocorr"),
              ("smcmc_autocorr_grid.hip", [], "autocorr_grid"),
              ("smcmc_marginals.hip", [], "marginals"), ("smcmc_trace_moments.hip", [], "trace_moments"),
@@ -63,7 +65,7 @@ def _units(user_flag=None, name="user"):
              hmc, ("smcmc_hmc_mfma_inst.hip", [], "hmc_mfma"),
              vaat, ("smcmc_vaat_large.hip", [], "vaat_large"),
              ("smcmc_pooled_update.hip", [], "pooled_update"), ("smcmc_perchain_inst.hip", [], "perchain"),
-             wave, wg,
+             wave, wg, stream,
              ("smcmc_panel_mfma_inst.hip", [], "panel_mfma"), ("smcmc_fold_inst.hip", [], "fold")]
     for dp in dp_list():
         for like in LIKELIHOODS:
@@ -161,7 +163,7 @@ def _compile(unit):
 # Translation units whose kernels hold a chain's state in registers for a whole launch: every kernel in them must use
 # no scratch (private segment), which the compiler's resource report (-Rpass-analysis=kernel-resource-usage) states
 # per kernel.  A unit that spills is refused, not built.
-NO_SCRATCH_SOURCES = ("smcmc_perchain_wg_inst.hip", "smcmc_marginals.hip", "smcmc_trace_moments.hip",
+NO_SCRATCH_SOURCES = ("smcmc_perchain_wg_inst.hip", "smcmc_perchain_stream_inst.hip", "smcmc_marginals.hip", "smcmc_trace_moments.hip",
                       "smcmc_convergence.hip", "smcmc_autocorr_grid.hip")
 
 

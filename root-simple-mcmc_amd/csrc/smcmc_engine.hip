@@ -25,6 +25,7 @@
 #include "smcmc_perchain_kernel.hip.h"
 #include "smcmc_perchain_wave.hip.h"
 #include "smcmc_perchain_wg.hip.h"
+#include "smcmc_perchain_stream.hip.h"
 #include "smcmc_proposal.hpp"
 
 using namespace smcmc;
@@ -129,6 +130,8 @@ struct smcmc_engine {
     bool pc_broken = false;        // a per-chain launch ended in an error with the chains part-way: Start / Restore again
     int pc_wave = -1;              // SMCMC_P_PERCHAIN_WAVE: -1 automatic, 0 / 1 one chain per lane / per wavefront
     bool pc_wg = false;            // SMCMC_P_PERCHAIN_WORKGROUP: one chain per workgroup (dim <= smcmc::kWgMaxDim)
+    bool pc_stream = false;        // SMCMC_P_PERCHAIN_STREAM: one chain per workgroup, matrices streamed (63 < dim <= smcmc::kStMaxDim)
+    DeviceBuffer<double> d_pc_wcov, d_pc_wu;   // its working copies, [nchains][dim (dim + 1) / 2] each; not part of a snapshot
     smcmc::PerChainRecord pc_rec = {nullptr, 0, 0};   // the per-step record of the launch in progress (smcmc_step_recorded)
     DeviceBuffer<double> d_pc_rec;    // its device buffer
     DeviceBuffer<double> d_pc_stage;  // the fallback ladder's staging records (pc_host_ladder), allocated at the first ladder
@@ -601,9 +604,17 @@ int fold_points(smcmc_engine* h, const double* const* pts, int n) {
 // ---- SMCMC_MODE_PER_CHAIN: every chain owns its adaptive state (smcmc_perchain_kernel.hip.h) --------------------
 bool per_chain(const smcmc_engine* h) { return h->mode == SMCMC_MODE_PER_CHAIN; }
 
+bool pc_use_stream(const smcmc_engine* h);
+
 // every chain's adaptive state, allocated at the first Start in this mode: all of it or none
 int pc_alloc(smcmc_engine* h) {
     if (h->d_pc_cov) return SMCMC_OK;
+    DeviceBuffer<double> wcov, wu;
+    if (pc_use_stream(h)) {   // the streamed kernel's working copies (written by every launch before it reads them)
+        const size_t each = (size_t)h->nchains * smcmc::st_packed(h->dim);
+        HIP_TRY(h, wcov.allocate(each));
+        HIP_TRY(h, wu.allocate(each));
+    }
     const size_t NP = (size_t)h->npad, D = (size_t)h->dim, npk = D * (D + 1) / 2;
     // the kernel reads both streams in whole chunks and primes its buffers unconditionally: padding behind the last tile
     const size_t pad = (size_t)smcmc::kPcPad * smcmc::kWave;
@@ -625,6 +636,7 @@ int pc_alloc(smcmc_engine* h) {
     h->d_pc_cov = std::move(cov); h->d_pc_ut = std::move(ut); h->d_pc_centre = std::move(centre);
     h->d_pc_last = std::move(last); h->d_pc_tmpl = std::move(tmpl); h->d_pc_flag = std::move(flag);
     if (proposed) h->d_proposed = std::move(proposed);
+    h->d_pc_wcov = std::move(wcov); h->d_pc_wu = std::move(wu);
     h->keep_proposed = true;
     return SMCMC_OK;
 }
@@ -815,13 +827,23 @@ bool pc_use_wave(const smcmc_engine* h) {
 // dim 63; at dim <= 63 it shares the images of the two others.
 bool pc_use_wg(const smcmc_engine* h) { return h->pc_wg && smcmc::perchain_wg_serves(h->likelihood); }
 
+// One chain per workgroup with its matrices streamed (smcmc_perchain_stream.hip.h) when SMCMC_P_PERCHAIN_STREAM asks for
+// it: the only kernel above smcmc::kWgMaxDim.  It wins over SMCMC_P_PERCHAIN_WORKGROUP where both serve; at dim <= 63,
+// which it does not serve, the default kernels run.
+bool pc_use_stream(const smcmc_engine* h) { return h->pc_stream && smcmc::perchain_stream_serves(h->likelihood, h->dim); }
+
 int pc_run(smcmc_engine* h, PerChainParams q) {
-    const bool wg = pc_use_wg(h);
-    const bool wave = !wg && pc_use_wave(h);
-    if (h->pc_rec.rec && !wave && !wg)
+    const bool stream = pc_use_stream(h);
+    const bool wg = !stream && pc_use_wg(h);
+    const bool wave = !stream && !wg && pc_use_wave(h);
+    if (stream && !h->d_pc_wcov)
+        return fail(h, SMCMC_ERR_LOGIC, "SMCMC_P_PERCHAIN_STREAM is set before the per-chain ensemble is started");
+    const smcmc::PerChainStreamWork work{h->d_pc_wcov, h->d_pc_wu};
+    if (h->pc_rec.rec && !wave && !wg && !stream)
         return fail(h, SMCMC_ERR_UNSUPPORTED, "a per-step record needs the one-chain-per-wavefront kernel (SMCMC_P_PERCHAIN_WAVE)");
     for (int round = 0; round < 1000; ++round) {
-        const hipError_t e = wg ? smcmc::launch_perchain_wg(q, h->pc_rec, h->likelihood, h->stream)
+        const hipError_t e = stream ? smcmc::launch_perchain_stream(q, h->pc_rec, work, h->likelihood, h->stream)
+                           : wg ? smcmc::launch_perchain_wg(q, h->pc_rec, h->likelihood, h->stream)
                            : wave ? smcmc::launch_perchain_wave(q, h->pc_rec, h->likelihood, h->stream)
                                   : launch_perchain(q, h->likelihood, h->stream);
         if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("per-chain kernel launch: ") + hipGetErrorString(e));
@@ -838,19 +860,21 @@ int pc_run(smcmc_engine* h, PerChainParams q) {
     return fail(h, SMCMC_ERR_RUNTIME, "per-chain update: the fallback ladder does not converge");
 }
 
-// the dimensions SMCMC_MODE_PER_CHAIN serves: <= 63, or up to smcmc::kWgMaxDim on the one-chain-per-workgroup kernel
+// the dimensions SMCMC_MODE_PER_CHAIN serves: <= 63, up to smcmc::kWgMaxDim on the one-chain-per-workgroup kernel, or
+// 63 < dim <= smcmc::kStMaxDim on the streamed one
 bool pc_dim_served(const smcmc_engine* h) {
     if (!h->panel_w && h->dim <= kPcMaxDim) return true;
-    return pc_use_wg(h) && h->dim <= smcmc::kWgMaxDim;
+    return (pc_use_wg(h) && h->dim <= smcmc::kWgMaxDim) || pc_use_stream(h);
 }
 
 int pc_check_supported(smcmc_engine* h) {
     if (!pc_dim_served(h))
         return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN serves dim <= 63 (up to smcmc_max_perchain_dim() with "
-                                              "SMCMC_P_PERCHAIN_WORKGROUP = 1)");
+                                              "SMCMC_P_PERCHAIN_WORKGROUP = 1, up to smcmc_max_perchain_stream_dim() with "
+                                              "SMCMC_P_PERCHAIN_STREAM = 1)");
     if (!h->exact)
         return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN runs in reference-order arithmetic (SMCMC_P_EXACT_ARITHMETIC = 1)");
-    if (h->likelihood == SMCMC_LIKE_USER && !smcmc::perchain_wave_serves(SMCMC_LIKE_USER) && !pc_use_wg(h))   // (not the per-lane kernel)
+    if (h->likelihood == SMCMC_LIKE_USER && !smcmc::perchain_wave_serves(SMCMC_LIKE_USER) && !pc_use_wg(h) && !pc_use_stream(h))   // (not the per-lane kernel)
         return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN serves the built-in likelihoods");
     for (int d = 0; d < h->dim; ++d)
         if (h->prop->ptype[d] != 0)
@@ -1085,6 +1109,7 @@ extern "C" {
 int smcmc_version(void) { return 100; }
 int smcmc_max_register_dim(void) { return kDPList[kNumDP - 1]; }
 int smcmc_max_perchain_dim(void) { return smcmc::kWgMaxDim; }
+int smcmc_max_perchain_stream_dim(void) { return smcmc::kStMaxDim; }
 int smcmc_max_dim(void) { return 8 * kPanelCW; }
 
 const char* smcmc_status_string(int status) {
@@ -1218,7 +1243,8 @@ int smcmc_set_mode(smcmc_engine* h, int mode) {
         return fail(h, SMCMC_ERR_LOGIC, "SMCMC_MODE_PER_CHAIN is chosen before Start");
     if (mode == SMCMC_MODE_PER_CHAIN && !pc_dim_served(h))
         return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN serves dim <= 63 (up to smcmc_max_perchain_dim() with "
-                                              "SMCMC_P_PERCHAIN_WORKGROUP = 1)");
+                                              "SMCMC_P_PERCHAIN_WORKGROUP = 1, up to smcmc_max_perchain_stream_dim() with "
+                                              "SMCMC_P_PERCHAIN_STREAM = 1)");
     h->mode = mode;
     h->prop->covFrozen = (mode == SMCMC_MODE_FROZEN);
     return SMCMC_OK;
@@ -1326,9 +1352,16 @@ int smcmc_set_param(smcmc_engine* h, int which, double v) {
         case SMCMC_P_COVARIANCE_FROZEN: h->pc_frozen = (v != 0.0); return SMCMC_OK;
         case SMCMC_P_PERCHAIN_WAVE: h->pc_wave = (v < 0.0) ? -1 : (v != 0.0 ? 1 : 0); return SMCMC_OK;
         case SMCMC_P_PERCHAIN_WORKGROUP:
-            if (v == 0.0 && per_chain(h) && (h->panel_w || h->dim > kPcMaxDim))
+            if (v == 0.0 && per_chain(h) && (h->panel_w || h->dim > kPcMaxDim) && !pc_use_stream(h))
                 return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN above dim 63 runs on the one-chain-per-workgroup kernel");
             h->pc_wg = (v != 0.0);
+            return SMCMC_OK;
+        case SMCMC_P_PERCHAIN_STREAM:
+            if (v == 0.0 && per_chain(h) && (h->dim > smcmc::kWgMaxDim || ((h->panel_w || h->dim > kPcMaxDim) && !pc_use_wg(h))))
+                return fail(h, SMCMC_ERR_UNSUPPORTED, "SMCMC_MODE_PER_CHAIN above smcmc_max_perchain_dim() runs on the streamed kernel");
+            if (v != 0.0 && per_chain(h) && h->d_pc_cov && !h->d_pc_wcov)
+                return fail(h, SMCMC_ERR_LOGIC, "SMCMC_P_PERCHAIN_STREAM is set before the per-chain ensemble is started");
+            h->pc_stream = (v != 0.0);
             return SMCMC_OK;
         case SMCMC_P_DENSE_QUADFORM:
             h->dense_quadform = (v != 0.0);
@@ -1444,7 +1477,8 @@ int smcmc_get_param(smcmc_engine* h, int which, double* out) {
         case SMCMC_P_COVARIANCE_FROZEN: *out = (h->pc_frozen || h->mode == SMCMC_MODE_FROZEN) ? 1.0 : 0.0; break;
         case SMCMC_P_DENSE_QUADFORM: *out = (h->dense_quadform || h->d_like_rowptr == nullptr) ? 1.0 : 0.0; break;
         case SMCMC_P_PERCHAIN_WAVE: *out = (per_chain(h) && h->dim <= kPcMaxDim && !pc_use_wg(h) && pc_use_wave(h)) ? 1.0 : 0.0; break;
-        case SMCMC_P_PERCHAIN_WORKGROUP: *out = (per_chain(h) && pc_use_wg(h)) ? 1.0 : 0.0; break;
+        case SMCMC_P_PERCHAIN_WORKGROUP: *out = (per_chain(h) && pc_use_wg(h) && !pc_use_stream(h)) ? 1.0 : 0.0; break;
+        case SMCMC_P_PERCHAIN_STREAM: *out = (per_chain(h) && pc_use_stream(h)) ? 1.0 : 0.0; break;
         default: return fail(h, SMCMC_ERR_INVALID, "unknown parameter");
     }
     return SMCMC_OK;

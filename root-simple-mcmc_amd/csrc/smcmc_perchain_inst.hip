@@ -1,7 +1,7 @@
 // smcmc_perchain_inst.hip -- instantiations of the per-chain adaptive step (smcmc_perchain_kernel.hip.h): one kernel
 // per likelihood, the dimension is a run-time value.
 #include "smcmc_perchain_kernel.hip.h"
-#include "smcmc_perchain_limits.h"   // kWgMaxDim: the largest dimension of the mode
+#include "smcmc_perchain_stream_index.h"   // kStMaxDim: the largest dimension of the mode
 
 namespace smcmc {
 
@@ -129,13 +129,13 @@ __global__ void __launch_bounds__(256) perchain_stage_kernel(PerChainStage g, in
 }
 
 hipError_t launch_perchain_stage(const PerChainStage& g, int nflagged, bool scatter, hipStream_t s) {
-    if (nflagged < 1 || g.dim < 1 || g.dim > kWgMaxDim || !g.chains || !g.stage) return hipErrorInvalidValue;
+    if (nflagged < 1 || g.dim < 1 || g.dim > kStMaxDim || !g.chains || !g.stage) return hipErrorInvalidValue;
     hipLaunchKernelGGL(perchain_stage_kernel, dim3(nflagged), dim3(256), 0, s, g, scatter ? 1 : 0);
     return hipGetLastError();
 }
 
 hipError_t launch_perchain_broadcast(const PerChainBroadcast& p, hipStream_t s) {
-    if (p.dim < 1 || p.dim > kWgMaxDim || p.nchains < 1 || p.nchains > p.npad) return hipErrorInvalidValue;
+    if (p.dim < 1 || p.dim > kStMaxDim || p.nchains < 1 || p.nchains > p.npad) return hipErrorInvalidValue;
     hipLaunchKernelGGL(perchain_broadcast_kernel, dim3((p.nchains + 255) / 256), dim3(256), 0, s, p);
     return hipGetLastError();
 }

@@ -21,10 +21,13 @@ class Engine(TraceReducers):
     """N chains of dimension D advancing in lock step on one GPU."""
 
     def __init__(self, dim, nchains=1, likelihood=LIKE_ISO_GAUSS, likelihood_params=None, seed=20240607,
-                 chain_offset=0, device=0, mode=MODE_POOLED, exact=True, stream=None, library=None, perchain_workgroup=False):
+                 chain_offset=0, device=0, mode=MODE_POOLED, exact=True, stream=None, library=None, perchain_workgroup=False,
+                 perchain_stream=False):
         # library: path of a build that carries a user likelihood (LIKE_USER), see build.py --user-likelihood
         # perchain_workgroup: MODE_PER_CHAIN on the one-chain-per-workgroup kernel (SMCMC_P_PERCHAIN_WORKGROUP), the one
         # that serves dim > 63 (up to smcmc_max_perchain_dim())
+        # perchain_stream: MODE_PER_CHAIN on the one-chain-per-workgroup kernel that streams the chain's matrices from
+        # device memory (SMCMC_P_PERCHAIN_STREAM), 63 < dim <= smcmc_max_perchain_stream_dim()
         self._lib = _capi.load(library)
         self.dim, self.nchains = int(dim), int(nchains)
         h = C.c_void_p()
@@ -38,6 +41,8 @@ class Engine(TraceReducers):
             raise SmcmcError(st, msg)
         if perchain_workgroup:
             self.set_param("PERCHAIN_WORKGROUP", 1.0)
+        if perchain_stream:
+            self.set_param("PERCHAIN_STREAM", 1.0)
         self._check(self._lib.smcmc_set_mode(self._h, mode))
         self.mode = mode
         self.set_param("EXACT_ARITHMETIC", 1.0 if exact else 0.0)
