@@ -59,8 +59,69 @@ typedef enum {
      * For dim > 63 all three run in reference-order arithmetic only. */
     SMCMC_LIKE_ASYM = 4,
     SMCMC_LIKE_HORRIFIC = 5,
-    SMCMC_LIKE_CONSTRAINED = 6
+    SMCMC_LIKE_CONSTRAINED = 6,
+    /* example/FakeLikelihood.H: a binned Poisson likelihood over a simulated event sample, re-weighted and corrected by
+     * nine systematic parameters (the definition follows below, "event sample").  dim = 9, Metropolis engine, frozen /
+     * pooled / SMCMC_MODE_PER_CHAIN on the one-chain-per-wavefront kernel, reference-order arithmetic only. */
+    SMCMC_LIKE_EVENT_SAMPLE = 7
 } smcmc_likelihood;
+
+/* ---- SMCMC_LIKE_EVENT_SAMPLE: the definition ------------------------------------------------------------------
+ * The point is p[9], in the order of example/SystematicCorrection.H:11-22: SignalWeight, BackgroundWeight, MassScale,
+ * MassWidth, MassSkew, SignalSeparationScale, BackgroundSeparationScale, FakeMuDkProb, MuDkEfficiency.
+ *
+ * smcmc_set_likelihood_params takes one flat array of 8 + 3 nbins + 6 nevents doubles:
+ *   { nevents, nbins, xmin, xmax, exposureRatio, separationCut (100), trueFakes (0.05), trueEfficiency (0.5),
+ *     data[3][nbins]      Close, Separated, DecayTag (FakeLikelihood.H:53-78 sums them in this order),
+ *     events[nevents][6]  Mass, Type, Separation, MuDk, TrueMass, TrueMassSigma (Simulated.H:7-14);
+ *                         Type 0 is signal, Type > 0 background; MuDk > 0 is a decay tag }
+ * SMCMC_ERR_INVALID unless the count is exact, 1 <= nbins <= SMCMC_EVENT_SAMPLE_MAX_BINS, nevents >= 1, every field
+ * finite, Mass, TrueMass and TrueMassSigma > 0, Type >= 0 (a data event, Type < 0, has no place in the simulated sample),
+ * xmin < xmax, and trueFakes and trueEfficiency inside (0, 1).
+ *
+ * exp, log, erf, atan below are smcmc_exp, smcmc_log, smcmc_erf, smcmc_atan of smcmc_detmath.h; every other operation
+ * is one IEEE operation, un-fused, in the order written.  The two tangents tan(pi (trueFakes - 0.5)) and
+ * tan(pi (trueEfficiency - 0.5)) are constants of the sample: the host takes them from libm when it packs the parameters.
+ *
+ * Once per evaluation (SystematicCorrection.H):
+ *   scale = p[2] / 10                                  :64      width = exp(p[3] / 10)                  :65
+ *   skew  = 0.3 erf(p[4] / 10)                         :68
+ *   sepS  = exp(p[5] / 10),  sepB = exp(p[6] / 10)     :40-43
+ *   cf = atan(tanFakes + p[7]) / M_PI + 0.5            :94-96   ce = atan(tanEfficiency + p[8]) / M_PI + 0.5   :106-108
+ *   weight of a signal event      (exp(p[0] / 10) * (MuDk > 0 ? cf / trueFakes : (1 - cf) / (1 - trueFakes))) * exposureRatio
+ *   weight of a background event  (exp(p[1] / 10) * (MuDk > 0 ? ce / trueEfficiency : (1 - ce) / (1 - trueEfficiency))) * exposureRatio
+ *                                                      :83-116
+ * Per event, in the order of the array (CorrectEvent, :35-128):
+ *   nominalLogMass = log(TrueMass);  nominalLogSigma = log(TrueMass + TrueMassSigma) - nominalLogMass       :57-59
+ *   logMass = log(Mass);  logSigma = (logMass - nominalLogMass) / nominalLogSigma                           :61-62
+ *       (none of the four depends on the point: the engine computes them once, on the host, with smcmc_log)
+ *   logMass = nominalLogMass + (logMass - nominalLogMass) * exp(logSigma * skew)                            :69, 72
+ *   logMass = nominalLogMass + (logMass - nominalLogMass) * width                                           :73
+ *   logMass = logMass + scale;  mass = exp(logMass)                                                         :74, 76
+ *   separation = Separation * (Type > 0 ? sepB : sepS)                                                      :47
+ * The cuts and the split (FakeLikelihood.H:203-214): the event is dropped if mass > 500.0, if mass < 0.0 or if
+ * separation < 0.0 (the reference's literals); it goes to DecayTag if MuDk > 0, else to Close if separation <
+ * separationCut, else to Separated -- a separation equal to the cut is Separated.
+ *   1. A bin's content is the sum of its events' weights in event order, one un-fused addition per event, from +0:
+ *      the reference's Fill loop.  This is what makes a chain reproducible.
+ *   2. The bin rule: for xmin <= mass < xmax, bin = int(nbins * (mass - xmin) / (xmax - xmin)) -- the product first,
+ *      then one IEEE division, then truncation -- and a quotient that rounds up to nbins counts as nbins - 1.  Anything
+ *      else is dropped, mass == xmax and a non-finite mass included.  TH1::Fill finds its bin through TAxis::FindBin;
+ *      ROOT is absent where this was written and the rule is not pinned against it (as for smcmc_marginal_histograms).
+ *   3. The bin sum (FakeLikelihood.H:53-78), over Close, then Separated, then DecayTag, bins ascending, from +0:
+ *        mc = content;  if (mc < 0.001) mc = 0.001;
+ *   4.   v = data - mc;  if (data > 0) v += data * log(mc / data);  logL += v
+ *      with smcmc_log and one IEEE division.
+ * Device and host (smcmc_event_sample_evaluate) compile this from one header, include/smcmc_event_sample.h. */
+#define SMCMC_EVENT_SAMPLE_MAX_BINS 97   /* the largest nbins whose 3 nbins + 1 rows of 64 doubles fit one workgroup's LDS
+                                          * (160 KiB) beside the step kernel's own (smcmc_kernels.hip.h derives and asserts it) */
+/* The likelihood on the host, for what the reference does outside Step(): Init()'s exposure ratio (FakeLikelihood.H:
+ * 107-143: evaluate at the origin with exposureRatio = 1, take data / mc from the histograms) and WriteSimulation()
+ * (:173-179).  params / count as above, point[9]; *logl the log-likelihood, hist (may be NULL) the three simulated
+ * histograms [3][nbins] at that point.  The same bits as the device.  It never steps a chain.  SMCMC_ERR_INVALID with
+ * the parameter rules above (smcmc_event_sample_last_error has the text of the latest failure of the calling thread). */
+int smcmc_event_sample_evaluate(const double* params, int count, const double* point, double* logl, double* hist);
+const char* smcmc_event_sample_last_error(void);
 
 /* How the proposal covariance adapts over the ensemble. */
 typedef enum {
@@ -595,7 +656,9 @@ int smcmc_vaat_rollback(smcmc_vaat* h);
 /* Runs every function of include/smcmc_detmath.h on the device for n inputs so
  * tests can compare device and host bit for bit.  kind: 0 log, 1 exp,
  * 2 sin(2 pi x), 3 cos(2 pi x), 4 pow_small(x, y), 5 sqrt, 6 x / y, 7 / 8 the two normals of
- * the Box-Muller pair made from the 32-bit words x, y, 9 sqrt_mid. */
+ * the Box-Muller pair made from the 32-bit words x, y, 9 sqrt_mid, 10 erf, 11 atan.
+ * device = -1 evaluates kinds 0, 1, 10 and 11 on the host instead (no GPU needed; other kinds SMCMC_ERR_INVALID):
+ * the host side of the comparison, and what tests/event_sample_ref.py builds its deterministic restatement on. */
 int smcmc_selftest_detmath(int device, int kind, int n, const double* x, const double* y, double* out);
 /* One v_mfma_f64_16x16x4_f64 chain: c[16][16] = sum_k a[16][k] b[k][16] over K
  * (multiple of 4), the accumulation order the pooled moments rely on. */

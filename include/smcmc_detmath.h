@@ -233,6 +233,91 @@ SMCMC_HD double smcmc_exp_mid(double x) {
     return y * smcmc_u2d((uint64_t)(0x3ff + k) << 52);
 }
 
+/* ---- erf(x), every x (SMCMC_LIKE_EVENT_SAMPLE: the mass skew, example/SystematicCorrection.H:68) ----------------
+ * Per-evaluation scalars: written for accuracy and for the same bits on host and device, not for speed.
+ *   |x| < 7/8    erf x = x + x r,  r = (2/sqrt(pi) - 1) + z Q(z), z = x^2, Q the Maclaurin series
+ *                2/sqrt(pi) sum_{n >= 1} (-1)^n z^(n-1) / (n! (2n + 1)) to n = 18 (next term < 1e-21); |r| < 0.13, so the
+ *                series' rounding reaches the result at an eighth of its size.  Subnormal x: z = 0, one fused rounding.
+ *   7/8 .. 6     erf x = 1 - erfc x,  erfc x = exp(-x^2) / (sqrt(pi) t_0),  t_(k-1) = x + (k/2) / t_k, t_N = x: the
+ *                continued fraction x + (1/2)/(x + 1/(x + (3/2)/(x + ...))) evaluated from its tail, every term
+ *                positive; N = int(300 / x^2) + 20 terms leave < 4e-16 of erfc, < 1e-16 of erf.  exp(-x^2) from the
+ *                split x = hi + lo (hi: the upper 32 bits, hi^2 exact), as fdlibm's s_erf.c takes it.
+ *   >= 6         +-1 (erfc 6 = 2.2e-17 is below half an ulp of 1); +-inf included.  NaN is returned as it is. */
+SMCMC_HD double smcmc_erf(double x) {
+    const double efx = 0x1.06eba8214db69p-3;          /* 2/sqrt(pi) - 1 */
+    const double isqrtpi = 0x1.20dd750429b6dp-1;      /* 1/sqrt(pi) */
+    const double q[18] = {-0x1.812746b0379e7p-2, 0x1.ce2f21a042be2p-4, -0x1.b82ce31288b51p-6, 0x1.565bcd0e6a53fp-8,
+                          -0x1.c02db40040b86p-11, 0x1.f9a326f9b89b7p-14, -0x1.f4d25c3e0c2ebp-17, 0x1.b9e6c9dc651a3p-20,
+                          -0x1.5f742ec43e71ap-23, 0x1.fcc5720624c1cp-27, -0x1.51d7181c5d36dp-30, 0x1.9e6ad5e55a730p-34,
+                          -0x1.d8453cb0c46eap-38, 0x1.f683ae4a97007p-42, -0x1.f56f071a885cfp-46, 0x1.d70b3537f4765p-50,
+                          -0x1.a2007af3447f6p-54, 0x1.5f7919bc67b8cp-58};
+    if (x != x) return x;
+    const double ax = smcmc_u2d(smcmc_d2u(x) & 0x7fffffffffffffffull);
+    if (ax < 0.875) {
+        const double z = x * x;
+        double s = q[17];
+        SMCMC_UNROLL
+        for (int n = 16; n >= 0; --n) s = SMCMC_FMA(z, s, q[n]);
+        const double r = SMCMC_FMA(z, s, efx);
+        return SMCMC_FMA(x, r, x);
+    }
+    double v = 1.0;
+    if (ax < 6.0) {
+        const double hi = smcmc_u2d(smcmc_d2u(ax) & 0xffffffff00000000ull);
+        const double e = smcmc_exp(-hi * hi) * smcmc_exp((hi - ax) * (hi + ax));
+        const int N = (int)(300.0 / (ax * ax)) + 20;
+        double t = ax;
+        for (int k = N; k >= 1; --k) t = ax + (0.5 * (double)k) / t;
+        v = 1.0 - (e * isqrtpi) / t;
+    }
+    return ((int64_t)smcmc_d2u(x) < 0) ? -v : v;
+}
+
+/* ---- atan(x), every x (SystematicCorrection.H:96, 108) -- fdlibm s_atan.c: the argument reduced onto |t| < 7/16 about
+ * 0, atan(1/2), atan(1), atan(3/2) or infinity, an odd polynomial of degree 23 there, the reduction constants as hi + lo.
+ * < 1 ulp.  |x| < 2^-29 (subnormals, +-0) returns x; |x| >= 2^66 and +-inf return +-pi/2; NaN is returned as it is. */
+SMCMC_HD double smcmc_atan(double x) {
+    const double atanhi[4] = {4.63647609000806093515e-01, 7.85398163397448278999e-01, 9.82793723247329054082e-01,
+                              1.57079632679489655800e+00};
+    const double atanlo[4] = {2.26987774529616870924e-17, 3.06161699786838301793e-17, 1.39033110312309984516e-17,
+                              6.12323399573676603587e-17};
+    const double aT[11] = {3.33333333333329318027e-01, -1.99999999998764832476e-01, 1.42857142725034663711e-01,
+                           -1.11111104054623557880e-01, 9.09088713343650656196e-02, -7.69187620504482999495e-02,
+                           6.66107313738753120669e-02, -5.83357013379057348645e-02, 4.97687799461593236017e-02,
+                           -3.65315727442169155270e-02, 1.62858201153657823623e-02};
+    if (x != x) return x;
+    const int neg = (int64_t)smcmc_d2u(x) < 0;
+    double t = smcmc_u2d(smcmc_d2u(x) & 0x7fffffffffffffffull);
+    int id;
+    if (t >= 73786976294838206464.0) {                /* 2^66 */
+        const double r = atanhi[3] + atanlo[3];
+        return neg ? -r : r;
+    }
+    if (t < 0.4375) {
+        if (t < 1.86264514923095703125e-09) return x; /* 2^-29 */
+        id = -1;
+    } else if (t < 1.1875) {
+        if (t < 0.6875) { id = 0; t = (2.0 * t - 1.0) / (2.0 + t); }
+        else { id = 1; t = (t - 1.0) / (t + 1.0); }
+    } else {
+        if (t < 2.4375) { id = 2; t = (t - 1.5) / (1.0 + 1.5 * t); }
+        else { id = 3; t = -1.0 / t; }
+    }
+    const double z = t * t;
+    const double w = z * z;
+    const double s1 = z * (aT[0] + w * (aT[2] + w * (aT[4] + w * (aT[6] + w * (aT[8] + w * aT[10])))));
+    const double s2 = w * (aT[1] + w * (aT[3] + w * (aT[5] + w * (aT[7] + w * aT[9]))));
+    double r;
+    if (id < 0) r = t - t * (s1 + s2);
+    else {
+        /* (selects, not an indexed table: on the device an indexed local array is scratch memory) */
+        const double hi = (id == 0) ? atanhi[0] : (id == 1) ? atanhi[1] : (id == 2) ? atanhi[2] : atanhi[3];
+        const double lo = (id == 0) ? atanlo[0] : (id == 1) ? atanlo[1] : (id == 2) ? atanlo[2] : atanlo[3];
+        r = hi - ((t * (s1 + s2) - lo) - t);
+    }
+    return neg ? -r : r;
+}
+
 /* pow(x, y) for finite normal x > 0 and small |y| (the sigma update uses
  * y <= 1/500, TSimpleMCMC.H:1772-1775).  exp(y*log x): with |y log x| << 1 the
  * result is within ~1 ulp of the true power. */

@@ -1,0 +1,85 @@
+/* smcmc_event_sample.h -- the arithmetic of SMCMC_LIKE_EVENT_SAMPLE (include/smcmc.h states the definition), one
+ * copy for the device kernels and for the host entry point smcmc_event_sample_evaluate: example/SystematicCorrection.H
+ * and example/FakeLikelihood.H of the reference restated on include/smcmc_detmath.h, so that host and gfx950 give the
+ * same bits.  Compile with -ffp-contract=off.
+ *
+ * The engine's own layout of the sample ("packed", made once on the host by smcmc::es_pack, smcmc_event_sample_host.hpp):
+ *   [0, 16)               header, SMCMC_ES_H_*
+ *   [16, 16 + 3 nbins)    data: Close, Separated, DecayTag
+ *   then nevents x 6      per event {log TrueMass, log Mass - log TrueMass, logSigma, Separation, class, 0}
+ * Everything of an event that does not depend on the point is in there already: nominalLogMass, the difference
+ * logMass - nominalLogMass and its quotient by nominalLogSigma (SystematicCorrection.H:57-62).  class = 2 (Type > 0) +
+ * 1 (MuDk > 0) picks one of four weights, which depend on the point alone.
+ */
+#ifndef SMCMC_EVENT_SAMPLE_H_SEEN
+#define SMCMC_EVENT_SAMPLE_H_SEEN
+
+#include "smcmc_detmath.h"
+
+enum {
+    SMCMC_ES_H_NEVENTS = 0, SMCMC_ES_H_NBINS, SMCMC_ES_H_XMIN, SMCMC_ES_H_XMAX, SMCMC_ES_H_EXPOSURE, SMCMC_ES_H_CUT,
+    SMCMC_ES_H_TRUE_FAKES, SMCMC_ES_H_TRUE_EFF, SMCMC_ES_H_TAN_FAKES, SMCMC_ES_H_TAN_EFF, SMCMC_ES_H_RANGE,
+    SMCMC_ES_HEADER = 16,       /* doubles in front of the data */
+    SMCMC_ES_EVENT = 6,         /* doubles per packed event */
+    SMCMC_ES_PARAM_HEADER = 8,  /* doubles in front of the data in the caller's array (smcmc.h) */
+    SMCMC_ES_DIM = 9
+};
+
+/* what an evaluation takes from the point before it walks the events */
+typedef struct {
+    double scale, width, skew, sep[2];  /* mass shift, mass width, 0.3 erf(p4/10), separation scale by Type */
+    double weight[4];                   /* by class */
+} smcmc_es_scalars;
+
+/* p: the point; the other arguments: the header's values of those names */
+SMCMC_HD void smcmc_es_point_scalars(const double* p, double exposure, double true_fakes, double true_eff,
+                                     double tan_fakes, double tan_eff, smcmc_es_scalars* s) {
+    const double pi = 3.14159265358979323846;                       /* M_PI */
+    s->scale = p[2] / 10.0;                                          /* SystematicCorrection.H:64 */
+    s->width = smcmc_exp(p[3] / 10.0);                               /* :65 */
+    s->skew = 0.3 * smcmc_erf(p[4] / 10.0);                          /* :68 */
+    s->sep[0] = smcmc_exp(p[5] / 10.0);                              /* :40, 43 */
+    s->sep[1] = smcmc_exp(p[6] / 10.0);                              /* :41, 43 */
+    const double ws = smcmc_exp(p[0] / 10.0);                        /* :87 */
+    const double wb = smcmc_exp(p[1] / 10.0);                        /* :88 */
+    double cf = tan_fakes;                                           /* :94 */
+    cf += p[7];                                                      /* :95 */
+    cf = smcmc_atan(cf) / pi + 0.5;                                  /* :96 */
+    double ce = tan_eff;                                             /* :106 */
+    ce += p[8];                                                      /* :107 */
+    ce = smcmc_atan(ce) / pi + 0.5;                                  /* :108 */
+    s->weight[0] = (ws * ((1.0 - cf) / (1.0 - true_fakes))) * exposure;   /* :100, 115 */
+    s->weight[1] = (ws * (cf / true_fakes)) * exposure;                   /* :99, 115 */
+    s->weight[2] = (wb * ((1.0 - ce) / (1.0 - true_eff))) * exposure;     /* :112, 115 */
+    s->weight[3] = (wb * (ce / true_eff)) * exposure;                     /* :111, 115 */
+}
+
+/* One event: its bin over the three histograms laid end to end (Close 0 .. nbins - 1, Separated, DecayTag), or -1 when a
+ * cut or the axis drops it.  nlm, dlm, lsg, sepn: the packed event; background = class >= 2, tagged = class & 1. */
+SMCMC_HD int smcmc_es_event_bin(double nlm, double dlm, double lsg, double sepn, int background, int tagged,
+                                const smcmc_es_scalars* s, int nbins, double xmin, double xmax, double range, double cut) {
+    const double skew = smcmc_exp(lsg * s->skew);                    /* SystematicCorrection.H:69 */
+    double lm = nlm + dlm * skew;                                    /* :72 */
+    lm = nlm + (lm - nlm) * s->width;                                /* :73 */
+    lm = lm + s->scale;                                              /* :74 */
+    const double mass = smcmc_exp(lm);                               /* :76 */
+    const double sep = sepn * (background ? s->sep[1] : s->sep[0]);  /* :47 */
+    if (mass > 500.0) return -1;                                     /* FakeLikelihood.H:203 */
+    if (mass < 0.0) return -1;                                       /* :204 */
+    if (sep < 0.0) return -1;                                        /* :205 */
+    const int hist = tagged ? 2 : (sep < cut) ? 0 : 1;               /* :206-214 */
+    if (!(mass >= xmin) || !(mass < xmax)) return -1;                /* under- and overflow, NaN */
+    int b = (int)(((double)nbins * (mass - xmin)) / range);
+    if (b > nbins - 1) b = nbins - 1;                                /* (the quotient rounded up to nbins) */
+    return hist * nbins + b;
+}
+
+/* one bin's term of the sum (FakeLikelihood.H:54-59) */
+SMCMC_HD double smcmc_es_bin_term(double data, double mc) {
+    if (mc < 0.001) mc = 0.001;
+    double v = data - mc;
+    if (data > 0.0) v += data * smcmc_log(mc / data);
+    return v;
+}
+
+#endif

@@ -29,6 +29,8 @@ FLAGS = ["-std=c++17", "-O3", "-fPIC", "-ffp-contract=off", f"--offload-arch={AR
 LIKELIHOODS = (0, 1, 2)
 STRESS_LIKELIHOODS = (4, 5, 6)   # SMCMC_LIKE_ASYM / HORRIFIC / CONSTRAINED: built for two families only (launch_step)
 STRESS_DP = (31, 63)
+EVENT_SAMPLE_LIKELIHOOD = 7       # SMCMC_LIKE_EVENT_SAMPLE: dim = 9, so the one family pick_dp(9) gives (kEsDP of smcmc_kernels.hip.h)
+EVENT_SAMPLE_DP = (15,)
 
 
 def dp_list():
@@ -66,13 +68,17 @@ def _units(user_flag=None, name="user"):
              vaat, ("smcmc_vaat_large.hip", [], "vaat_large"),
              ("smcmc_pooled_update.hip", [], "pooled_update"), ("smcmc_perchain_inst.hip", [], "perchain"),
              wave, wg, stream,
-             ("smcmc_panel_mfma_inst.hip", [], "panel_mfma"), ("smcmc_fold_inst.hip", [], "fold")]
+             ("smcmc_panel_mfma_inst.hip", [], "panel_mfma"), ("smcmc_fold_inst.hip", [], "fold"),
+             ("smcmc_event_sample.hip", [], "event_sample")]
     for dp in dp_list():
         for like in LIKELIHOODS:
             units.append(("smcmc_inst.hip", [f"-DSMCMC_DP={dp}", f"-DSMCMC_LIKE={like}"], f"inst_dp{dp}_l{like}"))
     for dp in STRESS_DP:
         for like in STRESS_LIKELIHOODS:
             units.append(("smcmc_inst.hip", [f"-DSMCMC_DP={dp}", f"-DSMCMC_LIKE={like}"], f"inst_dp{dp}_l{like}"))
+    for dp in EVENT_SAMPLE_DP:
+        units.append(("smcmc_inst.hip", [f"-DSMCMC_DP={dp}", f"-DSMCMC_LIKE={EVENT_SAMPLE_LIKELIHOOD}"],
+                      f"inst_dp{dp}_l{EVENT_SAMPLE_LIKELIHOOD}"))
     for w in (4, 8):
         units.append(("smcmc_panel_inst.hip", [f"-DSMCMC_PANEL_W={w}"], f"panel_w{w}"))
         if user_flag:   # a user likelihood as an HMC target (finite-difference / covariant gradient)

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "smcmc.h"
+#include "smcmc_event_sample_host.hpp"
 #include "smcmc_kernels.hip.h"   // SMCMC_FOR_EACH_DP
 
 namespace smcmc {
@@ -124,8 +125,8 @@ hipError_t fill(T* dst, size_t n, T v, hipStream_t stream) {
 
 // The format of the built-in likelihoods' parameters (h->like_params for h->dim dimensions), the same in every engine.
 // On success `prm` holds what the device reads for ROSENBROCK, ASYM and CONSTRAINED, defaults filled in, and a user
-// likelihood's parameters as given; it stays empty for the others.  QUADFORM's Error matrix is only checked: every
-// engine packs it in its own layout.  user_max / user_rule: the engine's own limit for SMCMC_LIKE_USER and its message.
+// likelihood's parameters as given; it stays empty for the others.  QUADFORM's Error matrix and EVENT_SAMPLE's sample
+// are only checked: every engine packs the matrix in its own layout, the Metropolis engine the sample.  user_max / user_rule: the engine's own limit for SMCMC_LIKE_USER and its message.
 template <typename H>
 int check_like_params(H* h, int like, size_t user_max, const char* user_rule, std::vector<double>& prm) {
     const std::vector<double>& p = h->like_params;
@@ -149,6 +150,12 @@ int check_like_params(H* h, int like, size_t user_max, const char* user_rule, st
                             "CONSTRAINED needs {SummedValues, SummedConstraint, ExpectedValues[dim], PriorConstraints[dim]}");
             prm = p;
             break;
+        case SMCMC_LIKE_EVENT_SAMPLE: {
+            // only checked, like QUADFORM's matrix: the engine packs the sample in a layout of its own (es_pack)
+            const char* why = es_check(p.data(), p.size());
+            if (why) return fail(h, SMCMC_ERR_INVALID, why);
+            break;
+        }
         case SMCMC_LIKE_USER:
             if (p.size() > user_max) return fail(h, SMCMC_ERR_INVALID, user_rule);
             prm = p;

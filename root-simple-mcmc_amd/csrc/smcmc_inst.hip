@@ -12,6 +12,16 @@ namespace smcmc {
 
 template <int DP, int LIKE, bool EXACT, bool FULLU, bool MOM, bool SPECIAL>
 static hipError_t go(const StepParams& p, hipStream_t s) {
+    if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE) {
+        // the lanes' histograms in dynamic LDS (event_sample_loglike): more than the default limit
+        auto kernel = step_kernel<DP, LIKE, EXACT, FULLU, MOM, SPECIAL>;
+        if (p.like_lds_bytes <= 0 || p.like_lds_bytes > event_sample_lds_bytes(SMCMC_EVENT_SAMPLE_MAX_BINS)) return hipErrorInvalidValue;
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 event_sample_lds_bytes(SMCMC_EVENT_SAMPLE_MAX_BINS));
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(p.npad / kWave), dim3(kWave), (size_t)p.like_lds_bytes, s, p);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(HIP_KERNEL_NAME(step_kernel<DP, LIKE, EXACT, FULLU, MOM, SPECIAL>), dim3(p.npad / kWave),
                        dim3(kWave), 0, s, p);
     return hipGetLastError();
@@ -21,6 +31,15 @@ template <>
 hipError_t launch_step_like<SMCMC_DP, SMCMC_LIKE>(const StepParams& p, bool exact, bool fullu, bool mom, bool special,
                                                   hipStream_t s) {
     constexpr int DP = SMCMC_DP, LIKE = SMCMC_LIKE;
+#if SMCMC_LIKE == 7   // SMCMC_LIKE_EVENT_SAMPLE: reference-order arithmetic only (the engine refuses the fused order)
+    if (!exact) return hipErrorNotSupported;
+    if (special) {
+        if (fullu) return mom ? go<DP, LIKE, true, true, true, true>(p, s) : go<DP, LIKE, true, true, false, true>(p, s);
+        return mom ? go<DP, LIKE, true, false, true, true>(p, s) : go<DP, LIKE, true, false, false, true>(p, s);
+    }
+    if (fullu) return mom ? go<DP, LIKE, true, true, true, false>(p, s) : go<DP, LIKE, true, true, false, false>(p, s);
+    return mom ? go<DP, LIKE, true, false, true, false>(p, s) : go<DP, LIKE, true, false, false, false>(p, s);
+#else
     if (special) {
         // uniform dimensions / scan: reference-order arithmetic only
         if (!exact) return hipErrorNotSupported;
@@ -30,9 +49,11 @@ hipError_t launch_step_like<SMCMC_DP, SMCMC_LIKE>(const StepParams& p, bool exac
     if (fullu) return mom ? go<DP, LIKE, true, true, true, false>(p, s) : go<DP, LIKE, true, true, false, false>(p, s);
     if (exact) return mom ? go<DP, LIKE, true, false, true, false>(p, s) : go<DP, LIKE, true, false, false, false>(p, s);
     return mom ? go<DP, LIKE, false, false, true, false>(p, s) : go<DP, LIKE, false, false, false, false>(p, s);
+#endif
 }
 
-#if SMCMC_LIKE != 3 || defined(SMCMC_USER_LIKELIHOOD)   // 3 = SMCMC_LIKE_USER (an enumerator, invisible to the preprocessor)
+#if (SMCMC_LIKE != 3 || defined(SMCMC_USER_LIKELIHOOD)) && SMCMC_LIKE != 7   // 3 = SMCMC_LIKE_USER, 7 = SMCMC_LIKE_EVENT_SAMPLE, which the
+// variable-at-a-time engine refuses (enumerators, invisible to the preprocessor)
 // the variable-at-a-time chains on the same likelihood code (smcmc_vaat_kernel.hip.h)
 template <>
 hipError_t launch_vaat_like<SMCMC_DP, SMCMC_LIKE>(const VaatParams& p, bool exact, hipStream_t s) {

@@ -30,6 +30,7 @@
 
 #include "smcmc.h"
 #include "smcmc_detmath.h"
+#include "smcmc_event_sample.h"
 #include "smcmc_step_deal.h"
 
 namespace smcmc {
@@ -225,6 +226,7 @@ struct StepParams {
     int zero;                  // always 0; makes table addresses depend on the step so that the
                                // compiler does not hoist (and then spill) whole tables out of the loop
     unsigned long long* prof;  // section profile (SMCMC_STEP_PROFILE builds only): [group][kProfSlots][64] cycle sums, added to
+    int like_lds_bytes;        // SMCMC_LIKE_EVENT_SAMPLE: dynamic LDS of the launch, the lanes' histograms (event_sample_lds_bytes)
 };
 
 // ---- Section profile of the step loop: -DSMCMC_STEP_PROFILE=1 (sections) or 2 (sections and every piece) ----
@@ -404,6 +406,72 @@ __device__ __forceinline__ double loglike(const double (&p)[DP], cptr_f64 prm, i
     return logl;
 }
 
+// ---- SMCMC_LIKE_EVENT_SAMPLE (smcmc.h; the arithmetic is include/smcmc_event_sample.h) ----
+// One chain per lane.  Every lane walks all events in order; the packed sample is wave-uniform and comes through the
+// constant address space (a few scalar loads per event for the whole wavefront).  A lane's three histograms sit in
+// dynamic LDS as hist[bin][lane], bins laid end to end (Close, Separated, DecayTag) and one more row behind them that
+// takes the events a cut or the axis drops: a lane only ever touches its own banks, whatever bin it hits, and the
+// update needs no predicate.  The family the likelihood is built for (dim = 9: pick_dp gives 15):
+constexpr int kEsDP = 15;
+constexpr int kEsLdsLimit = 160 * 1024;       // LDS of a gfx950 compute unit, all of which one workgroup may have
+// static LDS of step_kernel<kEsDP, ...> at its largest (moment fold, full decomposition): point, decomposition, tables
+constexpr int kEsStaticLds = 8 * (XLayout<kEsDP, true, false>::DOUBLES + ULayout<kEsDP, true>::SIZE + 384) + 64;
+constexpr int event_sample_lds_bytes(int nbins) { return (3 * nbins + 1) * kWave * 8; }
+static_assert(kEsStaticLds + event_sample_lds_bytes(SMCMC_EVENT_SAMPLE_MAX_BINS) <= kEsLdsLimit &&
+              kEsStaticLds + event_sample_lds_bytes(SMCMC_EVENT_SAMPLE_MAX_BINS + 1) > kEsLdsLimit,
+              "SMCMC_EVENT_SAMPLE_MAX_BINS (smcmc.h) is the largest nbins whose histograms fit one workgroup beside the kernel's static LDS");
+// The read-modify-write of a bin is a dependent LDS chain (address, read, add, write).  kEsBatch events are corrected
+// first -- (bin, weight) in registers --, then their bins are read together, added to in event order and written back
+// in event order: the reads' latency is paid once per batch.  Two events of a batch that hit the same bin: the later
+// one adds to the earlier one's sum (taken from its register, not from the read), so the order of additions into a bin
+// is the event order.
+constexpr int kEsBatch = 4;
+template <int DP>
+__device__ __forceinline__ double event_sample_loglike(const double (&p)[DP], cptr_f64 prm, double* hist, int lane) {
+    static_assert(DP >= SMCMC_ES_DIM, "the nine systematic parameters");
+    const int nev = (int)prm[SMCMC_ES_H_NEVENTS], nbins = (int)prm[SMCMC_ES_H_NBINS];
+    const double xmin = prm[SMCMC_ES_H_XMIN], xmax = prm[SMCMC_ES_H_XMAX], range = prm[SMCMC_ES_H_RANGE];
+    const double cut = prm[SMCMC_ES_H_CUT];
+    double pt[SMCMC_ES_DIM];
+#pragma unroll
+    for (int i = 0; i < SMCMC_ES_DIM; ++i) pt[i] = p[i];
+    smcmc_es_scalars s;
+    smcmc_es_point_scalars(pt, prm[SMCMC_ES_H_EXPOSURE], prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF],
+                           prm[SMCMC_ES_H_TAN_FAKES], prm[SMCMC_ES_H_TAN_EFF], &s);
+    const int rows = 3 * nbins;                 // row `rows`: the dropped events'
+    double* const col = hist + lane;
+    for (int r = 0; r <= rows; ++r) col[r * kWave] = 0.0;
+    const cptr_f64 ev = prm + SMCMC_ES_HEADER + rows;
+    for (int e0 = 0; e0 < nev; e0 += kEsBatch) {
+        int idx[kEsBatch];
+        double w[kEsBatch], v[kEsBatch];
+#pragma unroll
+        for (int u = 0; u < kEsBatch; ++u) {
+            const bool in = e0 + u < nev;                                   // (wave-uniform)
+            const cptr_f64 q = ev + (size_t)(in ? e0 + u : nev - 1) * SMCMC_ES_EVENT;
+            const int cls = (int)q[4];
+            const int b = smcmc_es_event_bin(q[0], q[1], q[2], q[3], cls >> 1, cls & 1, &s, nbins, xmin, xmax, range, cut);
+            idx[u] = (in && b >= 0) ? b : rows;
+            w[u] = (cls == 0) ? s.weight[0] : (cls == 1) ? s.weight[1] : (cls == 2) ? s.weight[2] : s.weight[3];
+        }
+#pragma unroll
+        for (int u = 0; u < kEsBatch; ++u) v[u] = col[idx[u] * kWave];
+#pragma unroll
+        for (int u = 0; u < kEsBatch; ++u) {
+#pragma unroll
+            for (int j = 0; j < u; ++j) v[u] = (idx[j] == idx[u]) ? v[j] : v[u];
+            v[u] = v[u] + w[u];
+        }
+#pragma unroll
+        for (int u = 0; u < kEsBatch; ++u) col[idx[u] * kWave] = v[u];
+    }
+    // FakeLikelihood.H:53-78: the bins of Close, Separated, DecayTag, in that order
+    const cptr_f64 data = prm + SMCMC_ES_HEADER;
+    double logl = 0.0;
+    for (int r = 0; r < rows; ++r) logl += smcmc_es_bin_term(data[r], col[r * kWave]);
+    return logl;
+}
+
 // SPECIAL = the variant that also knows uniform per-dimension proposals, the scan of one dimension
 // (TSimpleMCMC.H:685-716) and the read-back of the proposed point (:514); kept out of the common kernels, whose
 // register allocation it disturbs.
@@ -509,6 +577,14 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     __shared__ alignas(PAIRS ? 16 : 8) double xs[XL::DOUBLES];   // accepted point, x[row][lane]
     __shared__ __attribute__((aligned(16))) double us[UL::SIZE];   // decomposition, every lane reads the same word
     __shared__ __attribute__((aligned(16))) double ntab[384];      // tables of the normal transform: log [64][2], angle over the half circle [128][2]
+
+    // SMCMC_LIKE_EVENT_SAMPLE: the lanes' histograms, hist[bin][lane] (event_sample_loglike), in dynamic LDS
+    double* es_hist = nullptr;
+    if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE) {
+        extern __shared__ __attribute__((aligned(16))) double es_dynamic[];
+        es_hist = es_dynamic;
+    }
+    (void)es_hist;
 
     const int lane = threadIdx.x;
     const int group = blockIdx.x;
@@ -762,6 +838,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
             }
             if (dense) logl_prop = loglike_quadform_lds<DP, EXACT, XL>(xcol, likep + p.zero * (s + 1));
         }
+        else if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE) logl_prop = event_sample_loglike<DP>(xp, likep + p.zero * (s + 1), es_hist, lane);
         else if constexpr (!RMS_AHEAD) logl_prop = loglike<DP, LIKE, EXACT>(xp, likep + p.zero * (s + 1), D);
         if constexpr (!RMS_AHEAD) SMCMC_PROF_MARK(PROF_LIKE);
         bool take;
@@ -1261,6 +1338,10 @@ inline hipError_t launch_step(const StepParams& p, int like, bool exact, bool fu
             else return hipErrorInvalidValue;
         case SMCMC_LIKE_CONSTRAINED:
             if constexpr (DP == 31 || DP == 63) return launch_step_like<DP, SMCMC_LIKE_CONSTRAINED>(p, exact, fullu, moments, special, stream);
+            else return hipErrorInvalidValue;
+        // the event sample is built for the family of its nine dimensions only (kEsDP)
+        case SMCMC_LIKE_EVENT_SAMPLE:
+            if constexpr (DP == kEsDP) return launch_step_like<DP, SMCMC_LIKE_EVENT_SAMPLE>(p, exact, fullu, moments, special, stream);
             else return hipErrorInvalidValue;
 #ifdef SMCMC_USER_LIKELIHOOD
         case SMCMC_LIKE_USER: return launch_step_like<DP, SMCMC_LIKE_USER>(p, exact, fullu, moments, special, stream);

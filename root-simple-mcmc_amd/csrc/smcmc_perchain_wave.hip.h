@@ -106,6 +106,96 @@ __device__ __forceinline__ double pw_ordered_sum(double t, int n, double* scratc
     return pw_sum_lds<DMAX>(scratch, n, s0);
 }
 
+// SMCMC_LIKE_EVENT_SAMPLE (smcmc.h; the arithmetic is include/smcmc_event_sample.h) for ONE chain on 64 lanes.  Every
+// lane evaluating the same point over all events would be the time of one evaluation, milliseconds.  Instead:
+//   * the EVENTS are dealt to the lanes in batches of 64: lane l corrects event 64 b + l (its packed row by a vector
+//     load) and posts (bin, weight) to LDS, bin = -1 for an event a cut or the axis drops and for the slots past the
+//     last event;
+//   * the BINS are dealt to the lanes: lane j owns bins j, j + 64, j + 128, ... of the three histograms laid end to end
+//     (kEsOwn registers).  It scans the batch's 64 posts in event order and adds those that hit one of its bins -- a
+//     select, so a post for somebody else's bin leaves the sum's bits alone.  A bin's content is then the sum of its
+//     events' weights in event order, the reference's Fill loop bit for bit;
+//   * the bin terms (the clamp, data - mc, data log(mc / data)) are formed by the owners and added up in bin order by
+//     every lane alike, as pw_sum_lds does for the likelihoods of one term per dimension.
+// p: the point in LDS (ps).  Static LDS: 64 posts and the bin terms, 3.3 KB.
+constexpr int kEsOwn = (3 * SMCMC_EVENT_SAMPLE_MAX_BINS + kWave - 1) / kWave;
+static_assert(kEsOwn * kWave >= 3 * SMCMC_EVENT_SAMPLE_MAX_BINS + kPwBatch, "the last batch of the bin sum reads inside `term`");
+// the scan of one batch's posts by a lane that owns N bins (N compile-time: with the count as a run-time bound of the
+// inner loop every post cost five scalar branches, 2.7 ms per step at 30 000 events instead of 1.3)
+template <int N>
+__device__ __forceinline__ void pw_event_sample_scan(const int* post_bin, const double* post_w, int lane, double (&own)[kEsOwn]) {
+#pragma unroll 8
+    for (int k = 0; k < kWave; ++k) {
+        const int d = post_bin[k] - lane;               // (every lane reads the same word)
+        const double wk = post_w[k];
+#pragma unroll
+        for (int r = 0; r < N; ++r) own[r] = (d == kWave * r) ? own[r] + wk : own[r];
+    }
+}
+__device__ __forceinline__ double pw_event_sample(const double* p, const double* __restrict__ like) {
+    __shared__ int post_bin[kWave];
+    __shared__ __attribute__((aligned(16))) double post_w[kWave];
+    __shared__ __attribute__((aligned(16))) double term[kEsOwn * kWave];
+    const int lane = threadIdx.x;
+    const cptr_f64 prm = as_const(like);
+    const int nev = (int)prm[SMCMC_ES_H_NEVENTS], nbins = (int)prm[SMCMC_ES_H_NBINS];
+    const double xmin = prm[SMCMC_ES_H_XMIN], xmax = prm[SMCMC_ES_H_XMAX], range = prm[SMCMC_ES_H_RANGE];
+    const double cut = prm[SMCMC_ES_H_CUT];
+    double pt[SMCMC_ES_DIM];
+#pragma unroll
+    for (int i = 0; i < SMCMC_ES_DIM; ++i) pt[i] = p[i];
+    smcmc_es_scalars s;
+    smcmc_es_point_scalars(pt, prm[SMCMC_ES_H_EXPOSURE], prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF],
+                           prm[SMCMC_ES_H_TAN_FAKES], prm[SMCMC_ES_H_TAN_EFF], &s);
+    const int rows = 3 * nbins;
+    const int nown = (rows + kWave - 1) / kWave;        // registers of `own` in use (wave-uniform)
+    double own[kEsOwn];
+#pragma unroll
+    for (int r = 0; r < kEsOwn; ++r) own[r] = 0.0;
+    const double* const ev = like + SMCMC_ES_HEADER + rows;
+    for (int e0 = 0; e0 < nev; e0 += kWave) {
+        const int e = e0 + lane;
+        int b = -1;
+        double w = 0.0;
+        if (e < nev) {
+            const double* q = ev + (size_t)e * SMCMC_ES_EVENT;
+            const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+            const int cls = (int)q[4];
+            b = smcmc_es_event_bin(q0, q1, q2, q3, cls >> 1, cls & 1, &s, nbins, xmin, xmax, range, cut);
+            w = (cls == 0) ? s.weight[0] : (cls == 1) ? s.weight[1] : (cls == 2) ? s.weight[2] : s.weight[3];
+        }
+        __syncthreads();                                // the scan of the batch before is over
+        post_bin[lane] = b;
+        post_w[lane] = w;
+        __syncthreads();
+        switch (nown) {
+            case 1: pw_event_sample_scan<1>(post_bin, post_w, lane, own); break;
+            case 2: pw_event_sample_scan<2>(post_bin, post_w, lane, own); break;
+            case 3: pw_event_sample_scan<3>(post_bin, post_w, lane, own); break;     // (50 bins: 150 rows)
+            case 4: pw_event_sample_scan<(kEsOwn < 4 ? kEsOwn : 4)>(post_bin, post_w, lane, own); break;
+            default: pw_event_sample_scan<kEsOwn>(post_bin, post_w, lane, own); break;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < kEsOwn; ++r) {
+        const int k = lane + kWave * r;
+        term[k] = (k < rows) ? smcmc_es_bin_term(like[SMCMC_ES_HEADER + k], own[r]) : 0.0;
+    }
+    __syncthreads();
+    // FakeLikelihood.H:53-78: the bins of Close, Separated, DecayTag, in that order
+    double logl = 0.0;
+    for (int k0 = 0; k0 < rows; k0 += kPwBatch) {
+        double t[kPwBatch];
+#pragma unroll
+        for (int u = 0; u < kPwBatch; ++u) t[u] = term[k0 + u];     // (rows <= kEsOwn * 64 - 3: the entries past rows are +0 and in range)
+#pragma unroll
+        for (int u = 0; u < kPwBatch; ++u)
+            if (k0 + u < rows) logl += t[u];
+    }
+    return logl;
+}
+
 // log L of the point in LDS (p[0 .. D)), in the reference's summation order: the arithmetic of serial_loglike<LIKE, true>
 // (pi: this lane's coordinate of the same point)
 template <int LIKE, int DMAX>
@@ -151,6 +241,8 @@ __device__ __forceinline__ double pw_loglike(const double* p, double pi, int D, 
         lsum /= __builtin_sqrt(D * 4.0 / 12.0);
         lsum = -0.5 * lsum * lsum / sigma / sigma;
         lsum = outside ? -1E+30 : lsum;
+    } else if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE) {
+        lsum = pw_event_sample(p, like);
     } else if constexpr (LIKE == SMCMC_LIKE_CONSTRAINED) {
         // example4/TConstrainedLikelihood.H:26-46; like = {SummedValues, SummedConstraint, Expected[D], Prior[D]}
         double sum = pw_ordered_sum<DMAX>(pi, D, scratch);
@@ -526,7 +618,7 @@ __global__ void __launch_bounds__(kWave) perchain_wave_kernel(const PerChainPara
                 step_rms = __builtin_sqrt(ms);
             }
             PW_MARK(6)
-            if constexpr (LIKE == SMCMC_LIKE_QUADFORM || LIKE == SMCMC_LIKE_USER) {
+            if constexpr (LIKE == SMCMC_LIKE_QUADFORM || LIKE == SMCMC_LIKE_USER || LIKE == SMCMC_LIKE_EVENT_SAMPLE) {
                 __syncthreads();
                 ps[lane] = mine ? xpi : 0.0;
                 __syncthreads();
@@ -634,7 +726,8 @@ inline bool perchain_wave_serves(int like) {
     if (like == SMCMC_LIKE_USER) return true;      // (a library built with a user likelihood: build.py --user-likelihood)
 #endif
     return like == SMCMC_LIKE_ISO_GAUSS || like == SMCMC_LIKE_QUADFORM || like == SMCMC_LIKE_ROSENBROCK ||
-           like == SMCMC_LIKE_ASYM || like == SMCMC_LIKE_HORRIFIC || like == SMCMC_LIKE_CONSTRAINED;
+           like == SMCMC_LIKE_ASYM || like == SMCMC_LIKE_HORRIFIC || like == SMCMC_LIKE_CONSTRAINED ||
+           like == SMCMC_LIKE_EVENT_SAMPLE;
 }
 
 hipError_t launch_perchain_wave(const PerChainParams& p, const PerChainRecord& rec, int like, hipStream_t stream);

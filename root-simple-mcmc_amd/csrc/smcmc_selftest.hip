@@ -36,6 +36,8 @@ __global__ void detmath_kernel(int kind, int n, const double* __restrict__ x, co
         case 7: smcmc_normal_pair((uint32_t)a, (uint32_t)b, &c, &s); r = c; break;   // words held as doubles
         case 8: smcmc_normal_pair((uint32_t)a, (uint32_t)b, &c, &s); r = s; break;
         case 9: r = smcmc_sqrt_mid(a); break;
+        case 10: r = smcmc_erf(a); break;
+        case 11: r = smcmc_atan(a); break;
         default: break;
     }
     out[i] = r;
@@ -75,7 +77,20 @@ __global__ void __launch_bounds__(64) mfma_strip_kernel(int K, const double* __r
 using smcmc::DeviceBuffer;
 
 extern "C" int smcmc_selftest_detmath(int device, int kind, int n, const double* x, const double* y, double* out) {
-    if (n <= 0 || !x || !out || kind < 0 || kind > 9) return SMCMC_ERR_INVALID;
+    if (n <= 0 || !x || !out || kind < 0 || kind > 11) return SMCMC_ERR_INVALID;
+    if (device == -1) {
+        // the host's evaluation of the same header (no device is touched)
+        for (int i = 0; i < n; ++i) {
+            switch (kind) {
+                case 0: out[i] = smcmc_log(x[i]); break;
+                case 1: out[i] = smcmc_exp(x[i]); break;
+                case 10: out[i] = smcmc_erf(x[i]); break;
+                case 11: out[i] = smcmc_atan(x[i]); break;
+                default: return SMCMC_ERR_INVALID;
+            }
+        }
+        return SMCMC_OK;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return SMCMC_ERR_NO_DEVICE;
     smcmc::DeviceGuard guard(device);

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (LIKE_ASYM, LIKE_CONSTRAINED, LIKE_HORRIFIC, LIKE_ISO_GAUSS, LIKE_QUADFORM, LIKE_ROSENBROCK, LIKE_USER, MODE_FROZEN, MODE_PER_CHAIN, MODE_POOLED, P,  # noqa: F401
+from ._capi import (LIKE_ASYM, LIKE_CONSTRAINED, LIKE_EVENT_SAMPLE, LIKE_HORRIFIC, LIKE_ISO_GAUSS, LIKE_QUADFORM, LIKE_ROSENBROCK, LIKE_USER, MODE_FROZEN, MODE_PER_CHAIN, MODE_POOLED, P,  # noqa: F401
                     SmcmcError)
 # the reducers over a saved trace live in trace.py; their names stay importable from here
 from .trace import (Autocorrelation, AutocorrelationGrid, AutocorrelationPlan, Convergence, MacroAutocorrelation, Marginals,  # noqa: F401
@@ -46,9 +46,12 @@ class Engine(TraceReducers):
         self._check(self._lib.smcmc_set_mode(self._h, mode))
         self.mode = mode
         self.set_param("EXACT_ARITHMETIC", 1.0 if exact else 0.0)
+        self.likelihood = int(likelihood)
+        self._likelihood_params = None
         if likelihood_params is not None:
             prm = _f64(likelihood_params).ravel()
             self._check(self._lib.smcmc_set_likelihood_params(self._h, _ptr(prm), prm.size))
+            self._likelihood_params = prm.copy()
         if stream is not None:
             self.set_stream(stream)
 
@@ -68,6 +71,15 @@ class Engine(TraceReducers):
             self.close()
         except Exception:
             pass
+
+    def EventSampleHistograms(self, point):
+        """LIKE_EVENT_SAMPLE: the three simulated histograms [3][nbins] (Close, Separated, DecayTag) at `point`, as
+        FakeLikelihood::WriteSimulation (example/FakeLikelihood.H:173-179) fills them, and the log-likelihood there:
+        (hist, logl).  Evaluated on the host by smcmc_event_sample_evaluate, bit for bit what the device sums."""
+        if self.likelihood != LIKE_EVENT_SAMPLE or self._likelihood_params is None:
+            raise SmcmcError(_capi.ERR_LOGIC, "EventSampleHistograms needs LIKE_EVENT_SAMPLE and its parameters")
+        logl, hist = event_sample_evaluate(self._likelihood_params, point, histograms=True)
+        return hist, logl
 
     def set_stream(self, stream):
         """stream: a raw hipStream_t value (e.g. torch.cuda.current_stream().cuda_stream)."""
@@ -403,6 +415,49 @@ class PosteriorMoments:
     def covariance(self):
         mu = self.mean
         return self.s2 / self.n - np.outer(mu, mu)
+
+
+def event_sample_evaluate(params, point, histograms=False):
+    """smcmc_event_sample_evaluate: LIKE_EVENT_SAMPLE at `point` (9 values) on the host, for the exposure ratio and the
+    simulated histograms -- never to step a chain.  Returns logL, or (logL, hist[3][nbins]) with histograms=True."""
+    lib = _capi.load()
+    prm = _f64(params).ravel()
+    pt = _f64(point).ravel()
+    if pt.size != 9:
+        raise SmcmcError(_capi.ERR_INVALID, "the event sample has nine parameters")
+    nbins = int(prm[1]) if prm.size > 1 and np.isfinite(prm[1]) and 1 <= prm[1] <= _capi.EVENT_SAMPLE_MAX_BINS else 1
+    hist = np.zeros((3, nbins))
+    logl = C.c_double(0.0)
+    st = lib.smcmc_event_sample_evaluate(_ptr(prm), prm.size, _ptr(pt), C.byref(logl), _ptr(hist) if histograms else None)
+    if st != _capi.OK:
+        raise SmcmcError(st, lib.smcmc_event_sample_last_error().decode() or lib.smcmc_status_string(st).decode())
+    return (logl.value, hist) if histograms else logl.value
+
+
+def event_sample_params(events, data, nbins, xmin, xmax, exposure_ratio=None, separation_cut=100.0, true_fakes=0.05,
+                        true_efficiency=0.5):
+    """The flat parameter array of LIKE_EVENT_SAMPLE (include/smcmc.h).  events: [nevents][6] (Mass, Type, Separation,
+    MuDk, TrueMass, TrueMassSigma); data: [3][nbins] (Close, Separated, DecayTag).  exposure_ratio=None takes it as
+    FakeLikelihood::Init does (example/FakeLikelihood.H:107-138): the simulated histograms at the origin with a ratio of
+    1, then sum(data) / sum(mc), the histograms added up as TH1::Integral does it (bins ascending, Close + Separated +
+    DecayTag)."""
+    events = _f64(events).reshape(-1, 6)
+    data = _f64(data).reshape(3, int(nbins))
+    head = [events.shape[0], int(nbins), xmin, xmax, 1.0 if exposure_ratio is None else exposure_ratio, separation_cut,
+            true_fakes, true_efficiency]
+    prm = np.concatenate([np.asarray(head, dtype=np.float64), data.ravel(), events.ravel()])
+    if exposure_ratio is None:
+        _, hist = event_sample_evaluate(prm, np.zeros(9), histograms=True)
+
+        def integral(h):
+            s = 0.0
+            for v in h:
+                s += float(v)
+            return s
+        d = integral(data[0]) + integral(data[1]) + integral(data[2])
+        m = integral(hist[0]) + integral(hist[1]) + integral(hist[2])
+        prm[4] = d / m
+    return prm
 
 
 def selftest_detmath(kind, x, y=None, device=0):
