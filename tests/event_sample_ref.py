@@ -183,6 +183,17 @@ def make_sample(oracle, nsignal, nbackground, nbins, key, xmin=0.0, xmax=500.0):
     return np.concatenate([np.array(head, dtype=np.float64), data.ravel(), ev.ravel()])
 
 
+def truncate(params, nevents):
+    """The first nevents events of a sample, nevents rewritten: the samples below make_sample's two signal and three
+    background events."""
+    params = np.asarray(params, dtype=np.float64)
+    nbins = int(params[1])
+    assert 1 <= nevents <= int(params[0])
+    out = params[:8 + 3 * nbins + 6 * nevents].copy()
+    out[0] = nevents
+    return out
+
+
 def points(oracle, n, key, spread=3.0):
     """n points of nine coordinates: the origin, then uniform in (-spread, spread), the last with a mass skew beyond the
     switch of smcmc_erf's two forms (p[4] / 10 > 7/8)."""
