@@ -68,16 +68,7 @@ __global__ void perchain_broadcast_kernel(const PerChainBroadcast p) {
     // UpdateProposal(true) :1493: the trace is the one fSigmaTrace was just set to, so sigma keeps its value
     const double scale = __builtin_sqrt(p.sigma_trace / p.sigma_trace);
     sigma = sigma * scale;
-    if (p.cov_w >= 0.0) {
-        cov_trials = dmax(1.0, p.cov_w * cov_trials);
-        cov_trials = dmin(cov_trials, p.cov_wW);
-        centre_trials = dmax(1.0, p.cov_w * centre_trials);
-        centre_trials = dmin(centre_trials, p.cov_wW);
-    }
-    if (p.acc_w >= 0.0) {
-        acc_trials = dmax(1.0, p.acc_w * acc_trials);
-        acc_trials = dmin(acc_trials, p.acc_wW);
-    }
+    deweight_trials(cov_trials, centre_trials, acc_trials, p.cov_w, p.cov_wW, p.acc_w, p.acc_wW);
     lf[SMCMC_LANE_SIGMA * NP] = sigma;
     lf[SMCMC_LANE_SIGMA_TRACE * NP] = p.sigma_trace;
     lf[SMCMC_LANE_ACCEPTANCE_TRIALS * NP] = acc_trials;

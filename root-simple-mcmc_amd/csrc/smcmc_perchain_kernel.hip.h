@@ -21,6 +21,10 @@
 // chains are independent and every draw is keyed on (chain, step), so a chain that runs a few steps late runs the
 // same steps.
 //
+// The chain's scalar columns, its scalar step and the stop / resume protocol are the one statement of
+// smcmc_perchain_scalars.hip.h, shared with the workgroup kernel (smcmc_perchain_wg.hip.h; the wave and the streamed
+// kernel restate it): the host side does not know which of the mode's kernels ran.
+//
 // Reference-order arithmetic only (compile with -ffp-contract=off).
 #pragma once
 
@@ -32,6 +36,7 @@
 #include "smcmc_detmath.h"
 #include "smcmc_kernels.hip.h"
 #include "smcmc_panel_kernel.hip.h"   // serial_loglike
+#include "smcmc_perchain_scalars.hip.h"
 
 namespace smcmc {
 
@@ -44,9 +49,6 @@ constexpr int kPcPad = kPcDepth * kPcChunk + kPcChunk * (kPcChunk + 1) / 2;
 constexpr int kPcBatch = 8;           // loads issued together in the O(D) loops over the [dim][chain] images
 constexpr int kPcMaxDim = 63;         // one lane per column in the wavefront's Cholesky
 constexpr int kPcRPitch = 65;         // row pitch of the LDS matrix of the Cholesky
-
-// SMCMC_LANE_UPDATE_STATUS
-enum { kPcOk = 0, kPcNeedsLadder = 1, kPcResume = 2, kPcInvalidTrace = 3 };
 
 struct PerChainParams {
     int nchains, npad, dim;
@@ -142,61 +144,18 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
 
     double* lf = p.lane_f64 + chain;
     int32_t* li = p.lane_i32 + chain;
-    double logl = lf[SMCMC_LANE_LOGL * NP];
-    double sigma = lf[SMCMC_LANE_SIGMA * NP];
-    double acc_rate = lf[SMCMC_LANE_ACCEPTANCE * NP];
-    double acc_trials = lf[SMCMC_LANE_ACCEPTANCE_TRIALS * NP];
-    double rigid = lf[SMCMC_LANE_RIGIDITY * NP];
-    double last_value = lf[SMCMC_LANE_LAST_VALUE * NP];
-    double last_x0 = lf[SMCMC_LANE_LAST_X0 * NP];
-    double step_rms = lf[SMCMC_LANE_STEP_RMS * NP];
-    double logl_prop = lf[SMCMC_LANE_LOGL_PROPOSED * NP];
-    double centre_trials = lf[SMCMC_LANE_CENTER_TRIALS * NP];
-    double cov_trials = lf[SMCMC_LANE_COVARIANCE_TRIALS * NP];
-    double sigma_trace = lf[SMCMC_LANE_SIGMA_TRACE * NP];
-    int trials = li[SMCMC_LANE_TRIALS * NP];
-    int succ = li[SMCMC_LANE_SUCCESSES * NP];
-    int next_update = li[SMCMC_LANE_NEXT_UPDATE * NP];
-    int naccept = li[SMCMC_LANE_NACCEPT * NP];
-    int rms_trials = li[SMCMC_LANE_STEP_RMS_TRIALS * NP];
-    int last_accept = li[SMCMC_LANE_LAST_ACCEPT * NP];
-    int status = li[SMCMC_LANE_UPDATE_STATUS * NP];
-    int ufull = li[SMCMC_LANE_DECOMP_FULL * NP];
-    uint32_t tstep = (uint32_t)li[SMCMC_LANE_CHAIN_STEPS * NP];
-    int update_count = li[SMCMC_LANE_UPDATE_COUNT * NP];
-    int last_path = li[SMCMC_LANE_LAST_UPDATE_PATH * NP];
+    PerChainScalars cs;
+    cs.load(lf, li, NP);
 
-    bool resume = active && status == kPcResume;   // the host finished this chain's UpdateProposal: the step goes on behind it
-    if (resume) status = kPcOk;
+    bool resume = active && cs.status == kPcResume;   // the host finished this chain's UpdateProposal: the step goes on behind it
+    if (resume) cs.status = kPcOk;
     const uint32_t aw = smcmc_accept_word((uint32_t)D);
     const int NB = (D + 3) / 4;
 
     // UpdateProposal (TSimpleMCMC.H:1009-1106) for the lanes of `want`; `trace` is the lane's covariance trace.
     // Returns with status / ufull / last_path of those lanes set; a lane whose decomposition failed has stopped.
     auto update_proposal = [&](bool want, double trace) {
-        if (want) {
-            ++update_count;
-            if (!(trace > 0)) {                                        // :1025-1028 (the reference throws)
-                status = kPcInvalidTrace;
-                want = false;
-            } else {
-                const double scale = __builtin_sqrt(sigma_trace / trace);
-                sigma = sigma * scale;                                 // :1042
-                sigma_trace = trace;                                   // :1043
-                const double up = 0.5 * succ;                          // :1051
-                next_update = (int)(p.acc_window + p.max_up - p.max_up / (up + 1.0));   // :1052
-                if (p.cov_w >= 0.0) {                                  // :1056-1067
-                    cov_trials = dmax(1.0, p.cov_w * cov_trials);
-                    cov_trials = dmin(cov_trials, p.cov_wW);
-                    centre_trials = dmax(1.0, p.cov_w * centre_trials);
-                    centre_trials = dmin(centre_trials, p.cov_wW);
-                }
-                if (p.acc_w >= 0.0) {                                  // :1081-1086
-                    acc_trials = dmax(1.0, p.acc_w * acc_trials);
-                    acc_trials = dmin(acc_trials, p.acc_wW);
-                }
-            }
-        }
+        if (want) want = cs.update_proposal(trace, p.acc_window, p.max_up, p.cov_w, p.cov_wW, p.acc_w, p.acc_wW);
         // the decomposition, one chain at a time, the whole wavefront on it (lane = column)
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");             // every lane's covariance stores are visible
         uint64_t todo = __ballot(want);
@@ -238,10 +197,7 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
                     gut[(size_t)kk * kWave + L] = lds[i * kPcRPitch + j];
                 }
             }
-            if (lane == L) {
-                if (ok) { ufull = 0; last_path = 0; }
-                else status = kPcNeedsLadder;                          // the host's ladder takes over (:1134-1389)
-            }
+            if (lane == L) cs.decomposed(ok);
         }
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");             // the owners read what the other lanes wrote
@@ -259,39 +215,18 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
     } else {
         // a resumed chain still owes the rest of the step its UpdateProposal interrupted -- also when that step was the
         // last one of its launch (tstep already stands at the target then; the loop's end test stops it afterwards)
-        bool live = active && status == kPcOk && (resume || tstep < p.target_step);
+        bool live = active && cs.status == kPcOk && (resume || cs.tstep < p.target_step);
         while (__any(live)) {
-            if (live && !resume) ++tstep;                               // ++fTotalSteps, :376
-            const uint64_t step = (uint64_t)tstep;
-            const bool forced_now = p.has_forced && tstep == p.step0 + 1u;
+            if (live && !resume) ++cs.tstep;                               // ++fTotalSteps, :376
+            const uint64_t step = (uint64_t)cs.tstep;
+            const bool forced_now = p.has_forced && cs.tstep == p.step0 + 1u;
             const bool upd = live && !resume && !forced_now;            // UpdateState runs (:706)
             bool moved = false;
             double x0 = p.x[chain];
 
             if (__any(upd)) {
                 // ---- UpdateState, scalar half (TSimpleMCMC.H:1723-1776) ----
-                if (upd) {
-                    ++trials;
-                    moved = (logl != last_value) || (x0 != last_x0);
-                    if (moved) ++succ;
-                    acc_rate *= acc_trials;
-                    if (moved) acc_rate = acc_rate + 1.0;
-                    acc_rate /= acc_trials + 1.0;
-                    acc_trials = dmin(p.acc_window, acc_trials + 1.0);
-                    if (rigid < 500.0 && rigid > 0.0) {
-                        if (__builtin_fabs(acc_rate - p.target) < p.asig) {
-                            rigid += 0.5 * rigid / p.acc_window;
-                            rigid = dmin(200.0, rigid);
-                        }
-                        if (__builtin_fabs(acc_rate - p.target) > 4.0 * p.asig) {
-                            rigid -= 1.618 * 0.5 * rigid / p.acc_window;
-                            rigid = dmax(2.0, rigid);
-                        }
-                    }
-                    if (rigid > 0 && rigid < 100.0) {
-                        sigma *= smcmc_pow_small(acc_rate / p.target, dmin(1.0 / 500.0, 1.0 / (rigid * p.acc_window)));
-                    }
-                }
+                if (upd) moved = cs.update_state(x0, p.acc_window, p.target, p.asig);
                 // ---- running centre (:1780-1788); the diffs x - c stay in LDS for the covariance ----
                 __syncthreads();
                 for (int i0 = 0; i0 < D; i0 += kPcBatch) {
@@ -306,15 +241,15 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
                     for (int q = 0; q < kPcBatch; ++q) {
                         if (i0 + q < D) {
                             double c = cv[q];
-                            c *= centre_trials;
+                            c *= cs.centre_trials;
                             c += xv[q];
-                            c /= centre_trials + 1;
+                            c /= cs.centre_trials + 1;
                             if (upd) p.centre[(size_t)(i0 + q) * NP + chain] = c;
                             vec[(i0 + q) * kWave] = xv[q] - c;
                         }
                     }
                 }
-                if (upd) centre_trials = dmin(p.cov_window, centre_trials + 1.0);
+                if (upd) cs.centre_trials = dmin(p.cov_window, cs.centre_trials + 1.0);
                 // ---- running covariance (:1795-1820): the stream ----
                 double trace = 0.0;
                 if (!p.cov_frozen) {
@@ -325,7 +260,7 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
                     // (row, column) of every element is wavefront-uniform bookkeeping.
                     constexpr int CH = kPcChunk;
                     double buf[kPcDepth][CH];
-                    const double tv = cov_trials, tv1 = cov_trials + 1.0;
+                    const double tv = cs.cov_trials, tv1 = cs.cov_trials + 1.0;
                     const int nch = (npk + CH - 1) / CH;
                     auto fetch = [&](double (&b)[CH], int c) {
                         const double* src = ccov + (size_t)c * (CH * kWave);
@@ -384,20 +319,20 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
                             }
                         }
                     }
-                    if (upd) cov_trials = dmin(p.cov_window, cov_trials + 1.0);
+                    if (upd) cs.cov_trials = dmin(p.cov_window, cs.cov_trials + 1.0);
                 }
                 // ---- UpdateProposal when the chain's own schedule says so (:1824-1826) ----
                 bool trigger = false;
-                if (upd && moved) trigger = (--next_update) < 1;
+                if (upd && moved) trigger = (--cs.next_update) < 1;
                 if (__any(trigger)) {
                     if (p.cov_frozen) trace = load_trace();
                     update_proposal(trigger, trace);
-                    if (status != kPcOk) live = false;                 // this chain waits for the host
+                    if (cs.status != kPcOk) live = false;                 // this chain waits for the host
                 }
             }
             if (live && !forced_now) {                                 // :1829-1830
-                last_value = logl;
-                last_x0 = x0;
+                cs.last_value = cs.logl;
+                cs.last_x0 = x0;
                 for (int i0 = 0; i0 < D; i0 += kPcBatch) {
                     double xv[kPcBatch];
 #pragma unroll
@@ -414,7 +349,7 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
             // the trial step's square sum (:391-396) and -- ISO_GAUSS -- the likelihood are taken at the column ends of
             // the proposal stream, in the reference's index order, instead of in passes over the images: only when
             // no lane of the wavefront has a full decomposition or a forced step
-            const bool fused = !__any(ufull != 0) && !__any(forced_now);
+            const bool fused = !__any(cs.ufull != 0) && !__any(forced_now);
             double sqr = 0.0, lsum = 0.0;
             if (forced_now) {
                 for (int i = 0; i < D; ++i)
@@ -429,10 +364,10 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
                     double n0, n1, n2, n3;
                     smcmc_normal_pair(blk.v[0], blk.v[1], &n0, &n1);
                     smcmc_normal_pair(blk.v[2], blk.v[3], &n2, &n3);
-                    vec[(4 * b) * kWave] = sigma * n0;
-                    if (4 * b + 1 < D) vec[(4 * b + 1) * kWave] = sigma * n1;
-                    if (4 * b + 2 < D) vec[(4 * b + 2) * kWave] = sigma * n2;
-                    if (4 * b + 3 < D) vec[(4 * b + 3) * kWave] = sigma * n3;
+                    vec[(4 * b) * kWave] = cs.sigma * n0;
+                    if (4 * b + 1 < D) vec[(4 * b + 1) * kWave] = cs.sigma * n1;
+                    if (4 * b + 2 < D) vec[(4 * b + 2) * kWave] = cs.sigma * n2;
+                    if (4 * b + 3 < D) vec[(4 * b + 3) * kWave] = cs.sigma * n3;
                 }
                 if ((aw >> 2) >= (uint32_t)NB) {
                     const smcmc_u32x4 blk = smcmc_draw_block(p.seed, gid, step, aw >> 2, SMCMC_STREAM_STEP);
@@ -547,7 +482,7 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
                         }
                     }
                 }
-                if (__any(ufull != 0)) {
+                if (__any(cs.ufull != 0)) {
                     // a full decomposition (the eigen rung of the ladder): the rows below the diagonal, which every
                     // x'[j] sees after its upper part (i ascending)
                     for (int i2 = 1; i2 < D; ++i2) {
@@ -556,7 +491,7 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
                             const double u = cut[(size_t)(npk + i2 * (i2 - 1) / 2 + j2) * kWave];
                             double v = p.proposed[(size_t)j2 * NP + chain];
                             v += sr * u;
-                            if (live && ufull) p.proposed[(size_t)j2 * NP + chain] = v;
+                            if (live && cs.ufull) p.proposed[(size_t)j2 * NP + chain] = v;
                         }
                     }
                 }
@@ -583,14 +518,7 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
                         }
                     }
                 }
-                if (live) {
-                    double ms = step_rms * step_rms;
-                    ms *= rms_trials;
-                    ms += sqr;
-                    ms /= rms_trials + 1.0;
-                    rms_trials = (p.step_rms_window < rms_trials + 1) ? p.step_rms_window : rms_trials + 1;
-                    step_rms = __builtin_sqrt(ms);
-                }
+                if (live) cs.fold_step_rms(sqr, p.step_rms_window);
             }
             double lp;
             if (LIKE == SMCMC_LIKE_ISO_GAUSS && fused) {
@@ -616,27 +544,7 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
                 lp = serial_loglike<LIKE, true>(p.proposed, chain, NP, D, p.like);
             }
             if (live) {
-                logl_prop = lp;
-                bool take;
-                if (p.metropolis == 2) {
-                    take = true;
-                } else if (!__builtin_isfinite(logl_prop) || logl_prop < -0.999999E+30) {
-                    take = false;
-                } else {
-                    const double delta = logl_prop - logl;
-                    take = true;
-                    if (delta < 0.0) {
-                        if (p.metropolis == 1) take = false;
-                        else {
-                            const double trial = smcmc_log_pos(smcmc_u01(uword));
-                            if (delta < trial) take = false;
-                        }
-                    }
-                }
-                last_accept = take ? 1 : 0;
-                if (take) {
-                    logl = logl_prop;
-                    ++naccept;
+                if (cs.metropolis_take(p.metropolis, lp, uword)) {
                     for (int i0 = 0; i0 < D; i0 += kPcBatch) {
                         double pv[kPcBatch];
 #pragma unroll
@@ -646,42 +554,20 @@ __global__ void __launch_bounds__(kWave, 1) perchain_step_kernel(const PerChainP
                             if (i0 + q < D) p.x[(size_t)(i0 + q) * NP + chain] = pv[q];
                     }
                 }
-                if (p.save_x != nullptr && ((tstep - p.step0) % (uint32_t)p.save_stride) == 0) {
-                    const size_t slot = (size_t)((tstep - p.step0) / (uint32_t)p.save_stride - 1u);
+                if (p.save_x != nullptr && ((cs.tstep - p.step0) % (uint32_t)p.save_stride) == 0) {
+                    const size_t slot = (size_t)((cs.tstep - p.step0) / (uint32_t)p.save_stride - 1u);
                     for (int i = 0; i < D; ++i)
                         p.save_x[(slot * (size_t)D + (size_t)i) * NP + chain] = p.x[(size_t)i * NP + chain];
-                    p.save_logl[slot * NP + chain] = logl;
+                    p.save_logl[slot * NP + chain] = cs.logl;
                 }
             }
-            live = live && tstep < p.target_step;
+            live = live && cs.tstep < p.target_step;
         }
     }
 
     if (active) {
-        if (status == kPcNeedsLadder || status == kPcInvalidTrace) atomicAdd(p.flag_count, 1);
-        lf[SMCMC_LANE_LOGL * NP] = logl;
-        lf[SMCMC_LANE_SIGMA * NP] = sigma;
-        lf[SMCMC_LANE_ACCEPTANCE * NP] = acc_rate;
-        lf[SMCMC_LANE_ACCEPTANCE_TRIALS * NP] = acc_trials;
-        lf[SMCMC_LANE_RIGIDITY * NP] = rigid;
-        lf[SMCMC_LANE_LAST_VALUE * NP] = last_value;
-        lf[SMCMC_LANE_LAST_X0 * NP] = last_x0;
-        lf[SMCMC_LANE_STEP_RMS * NP] = step_rms;
-        lf[SMCMC_LANE_LOGL_PROPOSED * NP] = logl_prop;
-        lf[SMCMC_LANE_CENTER_TRIALS * NP] = centre_trials;
-        lf[SMCMC_LANE_COVARIANCE_TRIALS * NP] = cov_trials;
-        lf[SMCMC_LANE_SIGMA_TRACE * NP] = sigma_trace;
-        li[SMCMC_LANE_TRIALS * NP] = trials;
-        li[SMCMC_LANE_SUCCESSES * NP] = succ;
-        li[SMCMC_LANE_NEXT_UPDATE * NP] = next_update;
-        li[SMCMC_LANE_NACCEPT * NP] = naccept;
-        li[SMCMC_LANE_STEP_RMS_TRIALS * NP] = rms_trials;
-        li[SMCMC_LANE_LAST_ACCEPT * NP] = last_accept;
-        li[SMCMC_LANE_UPDATE_STATUS * NP] = status;
-        li[SMCMC_LANE_DECOMP_FULL * NP] = ufull;
-        li[SMCMC_LANE_CHAIN_STEPS * NP] = (int32_t)tstep;
-        li[SMCMC_LANE_UPDATE_COUNT * NP] = update_count;
-        li[SMCMC_LANE_LAST_UPDATE_PATH * NP] = last_path;
+        if (cs.status == kPcNeedsLadder || cs.status == kPcInvalidTrace) atomicAdd(p.flag_count, 1);
+        cs.store(lf, li, NP);
     }
 }
 

@@ -20,6 +20,8 @@
 //     from the working copy), then the pivot's root and the division.  A failed pivot stops the chain for the host's
 //     ladder; its working decomposition is spoiled then, and the next launch reads the ladder's from the image.
 // A workgroup's stores to the working copies are read by other threads of the same workgroup only, behind a barrier.
+// The chain's scalar step is stated once for the lane and the register kernel in smcmc_perchain_scalars.hip.h; THIS
+// kernel keeps its own copy of that text: called from there it lost 0.3 - 1.7 % (profiles/perchain_scalars_notes.md).
 //
 // Reference-order arithmetic only (compile with -ffp-contract=off).
 #pragma once
@@ -38,24 +40,6 @@ struct PerChainStreamWork {
     double* wcov;
     double* wu;
 };
-
-// log L of the proposal: wg_loglike on vectors of kStVec
-template <int LIKE>
-__device__ __forceinline__ double st_loglike(const double* p, double pi, int D, const double* __restrict__ like, const QuadCsr& csr,
-                                             double* scratch) {
-    if constexpr (LIKE == SMCMC_LIKE_ROSENBROCK) {
-        // THardLogLikelihood.H:57-67: term i from p[i] and p[i + 1], the terms subtracted in order
-        const int t = threadIdx.x;
-        const double rb = like[0];
-        const double nx = p[(t + 1 < kStVec) ? t + 1 : t];
-        const double a = (1.0 - pi);
-        const double b = nx - pi * pi;
-        const double term = a * a + rb * b * b;
-        return wg_ordered_sum(-term, D - 1, scratch);
-    } else {
-        return wg_loglike<LIKE>(p, pi, D, like, csr, scratch);
-    }
-}
 
 // grid = nchains workgroups of 512 threads
 template <int LIKE>
@@ -380,7 +364,7 @@ __global__ void __launch_bounds__(kWgThreads, 1) perchain_stream_kernel(const Pe
             __syncthreads();
             const double xp0 = ps[0];
             const QuadCsr csr{p.like_csr.rowptr, p.like_csr.cols, p.like_csr.vals, p.like_csr.rows};
-            logl_prop = st_loglike<LIKE>(ps, xpi, D, p.like, csr, sv);
+            logl_prop = wg_loglike<LIKE, kStVec>(ps, xpi, D, p.like, csr, sv);
             bool take;
             if (p.metropolis == 2) {
                 take = true;

@@ -22,10 +22,10 @@
 // The HBM images, the per-chain scalar columns and the stop / resume protocol are those of perchain_step_kernel (a
 // launch reads the chain's state at its start and writes it back at its end), so the host side -- ladder, broadcast,
 // restore, getters -- does not know which kernel ran, and every chain is bit for bit oracle.Chain either way.
+// The chain's scalar step is stated once for the lane and the workgroup kernel in smcmc_perchain_scalars.hip.h; THIS
+// kernel keeps its own copy of that text: called from there it lost 4.8 % at D = 20 (profiles/perchain_scalars_notes.md).
 //
-// A launch can leave a per-step record of one chain (PerChainRecord): what TSimpleMCMC::Step() shows its caller after
-// every step (fAccepted, fProposed, the two likelihoods, StepRMS, the accept flag, the Adaptive* scalars SaveStep
-// fills).  include/TSimpleMCMC_amd.H runs Step() ahead in launches of many steps and serves the calls from it.
+// A launch can leave a per-step record of one chain (PerChainRecord, smcmc_perchain_scalars.hip.h).
 //
 // Reference-order arithmetic only (compile with -ffp-contract=off).
 #pragma once
@@ -33,22 +33,6 @@
 #include "smcmc_perchain_kernel.hip.h"
 
 namespace smcmc {
-
-// Per-step record of one chain: rec[(step - step0 - 1) * stride + ...]: [0, D) fAccepted, [D, 2 D) fProposed, [2 D, 3 D) the
-// diagonal of the covariance (GetCovarianceTrace is its sum in index order: the reader adds it up when somebody asks),
-// then the scalars below.
-enum {
-    kPcRecLogl = 0, kPcRecLoglProposed, kPcRecStepRms, kPcRecLastAccept, kPcRecTrials, kPcRecSuccesses, kPcRecNextUpdate,
-    kPcRecAcceptance, kPcRecAcceptanceTrials, kPcRecSigma, kPcRecCenterTrials, kPcRecCovarianceTrials, kPcRecTrace,
-    kPcRecTotalSteps, kPcRecStatus, kPcRecScalars
-};
-static_assert(kPcRecScalars == SMCMC_REC_COUNT_ && kPcRecTrace == SMCMC_REC_COVARIANCE_TRACE && kPcRecStatus == SMCMC_REC_UPDATE_STATUS,
-              "the record of smcmc_step_recorded (smcmc.h)");
-struct PerChainRecord {
-    double* rec;     // nullptr: no record
-    int chain;
-    int stride;      // doubles per step: >= 3 dim + kPcRecScalars
-};
 
 constexpr int kPwBatch = 8;          // LDS values read ahead of the additions of an ordered sum
 

@@ -17,9 +17,9 @@
 //   * UpdateProposal's scalar half replicated in every thread (the same numbers everywhere); the Cholesky right-looking
 //     over the workgroup: every element takes row c's subtraction as soon as row c is finished -- the subtractions of
 //     SharedProposal::cholesky in its order, the same bits.  A failed pivot stops the chain for the host's ladder.
-// The HBM images, the per-chain scalar columns and the stop / resume protocol are those of the other two kernels (a
-// launch reads the chain's state at its start and writes it back at its end), so the host side -- ladder, broadcast,
-// restore, getters -- does not know which kernel ran.
+// The HBM images are those of the other two kernels (a launch reads the chain's state at its start and writes it back
+// at its end); the per-chain scalar columns, the chain's scalar step and the stop / resume protocol are the one
+// statement of smcmc_perchain_scalars.hip.h, so the host side does not know which kernel ran.
 //
 // Reference-order arithmetic only (compile with -ffp-contract=off).
 #pragma once
@@ -101,8 +101,9 @@ struct WgLdsPoint {
     __device__ __forceinline__ double operator[](int i) const { return v[i]; }
 };
 
-// log L of the proposal: p[0 .. D) in LDS, pi this thread's coordinate of it; the arithmetic of pw_loglike
-template <int LIKE>
+// log L of the proposal: p[0 .. D) of an LDS vector of VEC doubles, pi this thread's coordinate of it; the arithmetic of
+// pw_loglike
+template <int LIKE, int VEC>
 __device__ __forceinline__ double wg_loglike(const double* p, double pi, int D, const double* __restrict__ like, const QuadCsr& csr,
                                              double* scratch) {
     const int t = threadIdx.x;
@@ -159,7 +160,7 @@ __device__ __forceinline__ double wg_loglike(const double* p, double pi, int D, 
         static_assert(LIKE == SMCMC_LIKE_ROSENBROCK, "the likelihoods the workgroup kernel serves");
         // THardLogLikelihood.H:57-67: term i from p[i] and p[i + 1], the terms subtracted in order
         const double rb = like[0];
-        const double nx = p[(t + 1 < kWgVec) ? t + 1 : t];
+        const double nx = p[(t + 1 < VEC) ? t + 1 : t];
         const double a = (1.0 - pi);
         const double b = nx - pi * pi;
         const double term = a * a + rb * b * b;
@@ -208,42 +209,12 @@ __global__ void __launch_bounds__(kWgThreads, 1) perchain_wg_kernel(const PerCha
     const bool mine = t < D;             // this thread owns a coordinate
     const size_t own = (size_t)(mine ? t : D - 1) * NP + chain;
 
-    if (t < 128) ntab[t] = smcmc_log_table_dev[t];
-    if (t < kWave) {
-        // entry 64 + k is entry k turned by pi / 2: (-sin, cos) (SMCMC_NORMAL_PAIR_BODY_HALFCIRCLE)
-        const double c = smcmc_angle_table_dev[2 * t], sn = smcmc_angle_table_dev[2 * t + 1];
-        ntab[128 + 2 * t] = c;
-        ntab[128 + 2 * t + 1] = sn;
-        ntab[128 + 128 + 2 * t] = -sn;
-        ntab[128 + 128 + 2 * t + 1] = c;
-    }
-    const uint32_t ltab = (uint32_t)(uintptr_t)(lds_cptr_f64)ntab, atab = ltab + 128u * 8u;   // LDS byte addresses
+    const PerChainNormalTables tabs = fill_normal_tables(ntab, kWgThreads);
 
     double* lf = kp->lane_f64 + chain;
     int32_t* li = kp->lane_i32 + chain;
-    double logl = lf[SMCMC_LANE_LOGL * NP];
-    double sigma = lf[SMCMC_LANE_SIGMA * NP];
-    double acc_rate = lf[SMCMC_LANE_ACCEPTANCE * NP];
-    double acc_trials = lf[SMCMC_LANE_ACCEPTANCE_TRIALS * NP];
-    double rigid = lf[SMCMC_LANE_RIGIDITY * NP];
-    double last_value = lf[SMCMC_LANE_LAST_VALUE * NP];
-    double last_x0 = lf[SMCMC_LANE_LAST_X0 * NP];
-    double step_rms = lf[SMCMC_LANE_STEP_RMS * NP];
-    double logl_prop = lf[SMCMC_LANE_LOGL_PROPOSED * NP];
-    double centre_trials = lf[SMCMC_LANE_CENTER_TRIALS * NP];
-    double cov_trials = lf[SMCMC_LANE_COVARIANCE_TRIALS * NP];
-    double sigma_trace = lf[SMCMC_LANE_SIGMA_TRACE * NP];
-    int trials = li[SMCMC_LANE_TRIALS * NP];
-    int succ = li[SMCMC_LANE_SUCCESSES * NP];
-    int next_update = li[SMCMC_LANE_NEXT_UPDATE * NP];
-    int naccept = li[SMCMC_LANE_NACCEPT * NP];
-    int rms_trials = li[SMCMC_LANE_STEP_RMS_TRIALS * NP];
-    int last_accept = li[SMCMC_LANE_LAST_ACCEPT * NP];
-    int status = li[SMCMC_LANE_UPDATE_STATUS * NP];
-    int ufull = li[SMCMC_LANE_DECOMP_FULL * NP];
-    uint32_t tstep = (uint32_t)li[SMCMC_LANE_CHAIN_STEPS * NP];
-    int update_count = li[SMCMC_LANE_UPDATE_COUNT * NP];
-    int last_path = li[SMCMC_LANE_LAST_UPDATE_PATH * NP];
+    PerChainScalars cs;
+    cs.load(lf, li, NP);
 
     // the chain's state on chip
     double xi = kp->x[own], ci = kp->centre[own], lasti = kp->last_point[own], xpi = kp->proposed[own];
@@ -267,8 +238,8 @@ __global__ void __launch_bounds__(kWgThreads, 1) perchain_wg_kernel(const PerCha
     // does any thread's slot r lie in [m0, m1) (wave-uniform)
     auto slot_meets = [&](int r, int m0, int m1) __attribute__((always_inline)) { return kWgThreads * r < m1 && kWgThreads * (r + 1) > m0; };
 
-    bool resume = status == kPcResume;   // the host finished this chain's UpdateProposal: the step goes on behind it
-    if (resume) status = kPcOk;
+    bool resume = cs.status == kPcResume;   // the host finished this chain's UpdateProposal: the step goes on behind it
+    if (resume) cs.status = kPcOk;
     const uint32_t aw = smcmc_accept_word((uint32_t)D);
 
     // trace of the covariance, summed in index order (GetCovarianceTrace :961-967)
@@ -287,26 +258,7 @@ __global__ void __launch_bounds__(kWgThreads, 1) perchain_wg_kernel(const PerCha
     // UpdateProposal (TSimpleMCMC.H:1009-1106); `trace` is the covariance trace.  A failed pivot leaves
     // status = kPcNeedsLadder (the host's ladder takes over, :1134-1389) and the U registers spoiled: the chain stops.
     auto update_proposal = [&](double trace) __attribute__((always_inline)) {
-        ++update_count;
-        if (!(trace > 0)) {                                            // :1025-1028 (the reference throws)
-            status = kPcInvalidTrace;
-            return;
-        }
-        const double scale = __builtin_sqrt(sigma_trace / trace);
-        sigma = sigma * scale;                                         // :1042
-        sigma_trace = trace;                                           // :1043
-        const double up = 0.5 * succ;                                  // :1051
-        next_update = (int)(kp->acc_window + kp->max_up - kp->max_up / (up + 1.0));   // :1052
-        if (kp->cov_w >= 0.0) {                                          // :1056-1067
-            cov_trials = dmax(1.0, kp->cov_w * cov_trials);
-            cov_trials = dmin(cov_trials, kp->cov_wW);
-            centre_trials = dmax(1.0, kp->cov_w * centre_trials);
-            centre_trials = dmin(centre_trials, kp->cov_wW);
-        }
-        if (kp->acc_w >= 0.0) {                                          // :1081-1086
-            acc_trials = dmax(1.0, kp->acc_w * acc_trials);
-            acc_trials = dmin(acc_trials, kp->acc_wW);
-        }
+        if (!cs.update_proposal(trace, kp->acc_window, kp->max_up, kp->cov_w, kp->cov_wW, kp->acc_w, kp->acc_wW)) return;
         // SharedProposal::cholesky (smcmc_proposal.hpp), right-looking: W(a, b) = A(a, b) - sum_{c < a} U(c, a) U(c, b),
         // the subtraction of row c as soon as row c is finished (c ascending: the host's order of roundings)
 #pragma unroll
@@ -358,62 +310,39 @@ __global__ void __launch_bounds__(kWgThreads, 1) perchain_wg_kernel(const PerCha
                 if ((r & 7) == 7) wg_fence();
             }
         }
-        // (as selects: stores in the two branches would be merged into one store through a selected address, and the
-        // three variables would then live in scratch)
-        ufull = ok ? 0 : ufull;
-        last_path = ok ? 0 : last_path;
-        status = ok ? status : (int)kPcNeedsLadder;
+        cs.decomposed(ok);
         __syncthreads();
     };
 
     if (kp->update_only) {
         update_proposal(trace_now());
     } else {
-        bool live = status == kPcOk && (resume || tstep < kp->target_step);
+        bool live = cs.status == kPcOk && (resume || cs.tstep < kp->target_step);
         while (live) {
             kp = wg_launder(kbase);
-            if (!resume) ++tstep;                                       // ++fTotalSteps, :376
-            const uint64_t step = (uint64_t)tstep;
-            const bool forced_now = kp->has_forced && tstep == kp->step0 + 1u;
+            if (!resume) ++cs.tstep;                                       // ++fTotalSteps, :376
+            const uint64_t step = (uint64_t)cs.tstep;
+            const bool forced_now = kp->has_forced && cs.tstep == kp->step0 + 1u;
             const bool upd = !resume && !forced_now;                    // UpdateState runs (:706)
             bool moved = false;
             if (upd) {
                 // ---- UpdateState, scalar half (TSimpleMCMC.H:1723-1776) ----
-                ++trials;
-                moved = (logl != last_value) || (x0 != last_x0);
-                if (moved) ++succ;
-                acc_rate *= acc_trials;
-                if (moved) acc_rate = acc_rate + 1.0;
-                acc_rate /= acc_trials + 1.0;
-                acc_trials = dmin(kp->acc_window, acc_trials + 1.0);
-                if (rigid < 500.0 && rigid > 0.0) {
-                    if (__builtin_fabs(acc_rate - kp->target) < kp->asig) {
-                        rigid += 0.5 * rigid / kp->acc_window;
-                        rigid = dmin(200.0, rigid);
-                    }
-                    if (__builtin_fabs(acc_rate - kp->target) > 4.0 * kp->asig) {
-                        rigid -= 1.618 * 0.5 * rigid / kp->acc_window;
-                        rigid = dmax(2.0, rigid);
-                    }
-                }
-                if (rigid > 0 && rigid < 100.0) {
-                    sigma *= smcmc_pow_small(acc_rate / kp->target, dmin(1.0 / 500.0, 1.0 / (rigid * kp->acc_window)));
-                }
+                moved = cs.update_state(x0, kp->acc_window, kp->target, kp->asig);
                 // ---- running centre (:1780-1788) ----
                 __syncthreads();
                 if (mine) {
                     double c = ci;
-                    c *= centre_trials;
+                    c *= cs.centre_trials;
                     c += xi;
-                    c /= centre_trials + 1;
+                    c /= cs.centre_trials + 1;
                     ci = c;
                     dv[t] = xi - c;
                 }
-                centre_trials = dmin(kp->cov_window, centre_trials + 1.0);
+                cs.centre_trials = dmin(kp->cov_window, cs.centre_trials + 1.0);
                 // ---- running covariance about the updated centre (:1795-1820) ----
                 if (!kp->cov_frozen) {
                     __syncthreads();
-                    const double tv = cov_trials, tv1 = cov_trials + 1.0;
+                    const double tv = cs.cov_trials, tv1 = cs.cov_trials + 1.0;
 #pragma unroll
                     for (int r = 0; r < NE; ++r) {
                         const double da = dv[col_of(r)], db = dv[row_of(r)];   // element (b, a): row b, column a
@@ -425,19 +354,19 @@ __global__ void __launch_bounds__(kWgThreads, 1) perchain_wg_kernel(const PerCha
                         cov[r] = v;
                         if ((r & 7) == 7) wg_fence();
                     }
-                    cov_trials = dmin(kp->cov_window, cov_trials + 1.0);
+                    cs.cov_trials = dmin(kp->cov_window, cs.cov_trials + 1.0);
                 }
                 // ---- UpdateProposal when the chain's own schedule says so (:1824-1826) ----
                 bool trigger = false;
-                if (moved) trigger = (--next_update) < 1;
+                if (moved) trigger = (--cs.next_update) < 1;
                 if (trigger) {
                     update_proposal(trace_now());
-                    if (status != kPcOk) live = false;                  // this chain waits for the host
+                    if (cs.status != kPcOk) live = false;                  // this chain waits for the host
                 }
             }
             if (live && !forced_now) {                                  // :1829-1830
-                last_value = logl;
-                last_x0 = x0;
+                cs.last_value = cs.logl;
+                cs.last_x0 = x0;
                 lasti = xi;
             }
             resume = false;
@@ -457,10 +386,10 @@ __global__ void __launch_bounds__(kWgThreads, 1) perchain_wg_kernel(const PerCha
                 if (mine) {
                     const smcmc_u32x4 blk = smcmc_draw_block(kp->seed, gid, step, (uint32_t)(t >> 2), SMCMC_STREAM_STEP);
                     const uint32_t w0 = (t & 2) ? blk.v[2] : blk.v[0], w1 = (t & 2) ? blk.v[3] : blk.v[1];
-                    const NormalTables nt = normal_tables_fetch<false>(w0, w1, ltab, atab);
+                    const NormalTables nt = normal_tables_fetch<false>(w0, w1, tabs.ltab, tabs.atab);
                     double n0, n1;
                     normal_pair_lds(w0, w1, nt, &n0, &n1);
-                    z = sigma * ((t & 1) ? n1 : n0);
+                    z = cs.sigma * ((t & 1) ? n1 : n0);
                 }
                 __syncthreads();
                 if (t < kWgVec) zv[t] = z;
@@ -500,7 +429,7 @@ __global__ void __launch_bounds__(kWgThreads, 1) perchain_wg_kernel(const PerCha
                         }
                     }
                 }
-                if (ufull) {
+                if (cs.ufull) {
                     // a full decomposition (the eigen rung of the ladder): the rows below the diagonal, which every
                     // x'[j] sees after its upper part (i ascending), from the image
                     for (int i2 = 1; i2 < D; ++i2) {
@@ -517,50 +446,25 @@ __global__ void __launch_bounds__(kWgThreads, 1) perchain_wg_kernel(const PerCha
             // ---- StepRMS window (:391-406), likelihood (:410), Metropolis test (:432-463), accept copy (:484-491) ----
             if (kp->step_rms_window > 0) {
                 const double ts = xpi - xi;
-                const double sqr = wg_ordered_sum(ts * ts, D, sv);
-                double ms = step_rms * step_rms;
-                ms *= rms_trials;
-                ms += sqr;
-                ms /= rms_trials + 1.0;
-                rms_trials = (kp->step_rms_window < rms_trials + 1) ? kp->step_rms_window : rms_trials + 1;
-                step_rms = __builtin_sqrt(ms);
+                cs.fold_step_rms(wg_ordered_sum(ts * ts, D, sv), kp->step_rms_window);
             }
             __syncthreads();
             if (mine) ps[t] = xpi;
             __syncthreads();
             const double xp0 = ps[0];
             const QuadCsr csr{kp->like_csr.rowptr, kp->like_csr.cols, kp->like_csr.vals, kp->like_csr.rows};
-            logl_prop = wg_loglike<LIKE>(ps, xpi, D, kp->like, csr, sv);
-            bool take;
-            if (kp->metropolis == 2) {
-                take = true;
-            } else if (!__builtin_isfinite(logl_prop) || logl_prop < -0.999999E+30) {
-                take = false;
-            } else {
-                const double delta = logl_prop - logl;
-                take = true;
-                if (delta < 0.0) {
-                    if (kp->metropolis == 1) take = false;
-                    else {
-                        const double trial = smcmc_log_pos(smcmc_u01(uword));
-                        if (delta < trial) take = false;
-                    }
-                }
-            }
-            last_accept = take ? 1 : 0;
-            if (take) {
-                logl = logl_prop;
-                ++naccept;
+            const double lp = wg_loglike<LIKE, kWgVec>(ps, xpi, D, kp->like, csr, sv);
+            if (cs.metropolis_take(kp->metropolis, lp, uword)) {
                 xi = xpi;
                 x0 = xp0;
             }
-            if (kp->save_x != nullptr && ((tstep - kp->step0) % (uint32_t)kp->save_stride) == 0) {
-                const size_t slot = (size_t)((tstep - kp->step0) / (uint32_t)kp->save_stride - 1u);
+            if (kp->save_x != nullptr && ((cs.tstep - kp->step0) % (uint32_t)kp->save_stride) == 0) {
+                const size_t slot = (size_t)((cs.tstep - kp->step0) / (uint32_t)kp->save_stride - 1u);
                 if (mine) kp->save_x[(slot * (size_t)D + (size_t)t) * NP + chain] = xi;
-                if (t == 0) kp->save_logl[slot * NP + chain] = logl;
+                if (t == 0) kp->save_logl[slot * NP + chain] = cs.logl;
             }
             if (rec.rec != nullptr && chain == rec.chain) {          // (one chain per workgroup: the same for all threads)
-                double* rr = rec.rec + (size_t)(tstep - kp->step0 - 1u) * rec.stride;
+                double* rr = rec.rec + (size_t)(cs.tstep - kp->step0 - 1u) * rec.stride;
                 double* recl = panel;
                 __syncthreads();
                 if (mine) {
@@ -573,20 +477,12 @@ __global__ void __launch_bounds__(kWgThreads, 1) perchain_wg_kernel(const PerCha
                     if (a == col_of(r) && a < D) recl[2 * D + a] = cov[r];
                     if ((r & 7) == 7) wg_fence();
                 }
-                if (t == 0) {
-                    double* s = recl + 3 * D;
-                    s[kPcRecLogl] = logl; s[kPcRecLoglProposed] = logl_prop; s[kPcRecStepRms] = step_rms;
-                    s[kPcRecLastAccept] = last_accept; s[kPcRecTrials] = trials; s[kPcRecSuccesses] = succ;
-                    s[kPcRecNextUpdate] = next_update; s[kPcRecAcceptance] = acc_rate; s[kPcRecAcceptanceTrials] = acc_trials;
-                    s[kPcRecSigma] = sigma; s[kPcRecCenterTrials] = centre_trials; s[kPcRecCovarianceTrials] = cov_trials;
-                    s[kPcRecTrace] = 0.0;     // (the reader sums the diagonal)
-                    s[kPcRecTotalSteps] = (double)tstep; s[kPcRecStatus] = status;
-                }
+                if (t == 0) cs.write_record_scalars(recl + 3 * D);
                 __syncthreads();
                 for (int k = t; k < 3 * D + kPcRecScalars; k += kWgThreads) rr[k] = recl[k];
                 __syncthreads();
             }
-            live = tstep < kp->target_step;
+            live = cs.tstep < kp->target_step;
         }
     }
 
@@ -605,30 +501,8 @@ __global__ void __launch_bounds__(kWgThreads, 1) perchain_wg_kernel(const PerCha
         if ((r & 7) == 7) wg_fence();
     }
     if (t == 0) {
-        if (status == kPcNeedsLadder || status == kPcInvalidTrace) atomicAdd(kp->flag_count, 1);
-        lf[SMCMC_LANE_LOGL * NP] = logl;
-        lf[SMCMC_LANE_SIGMA * NP] = sigma;
-        lf[SMCMC_LANE_ACCEPTANCE * NP] = acc_rate;
-        lf[SMCMC_LANE_ACCEPTANCE_TRIALS * NP] = acc_trials;
-        lf[SMCMC_LANE_RIGIDITY * NP] = rigid;
-        lf[SMCMC_LANE_LAST_VALUE * NP] = last_value;
-        lf[SMCMC_LANE_LAST_X0 * NP] = last_x0;
-        lf[SMCMC_LANE_STEP_RMS * NP] = step_rms;
-        lf[SMCMC_LANE_LOGL_PROPOSED * NP] = logl_prop;
-        lf[SMCMC_LANE_CENTER_TRIALS * NP] = centre_trials;
-        lf[SMCMC_LANE_COVARIANCE_TRIALS * NP] = cov_trials;
-        lf[SMCMC_LANE_SIGMA_TRACE * NP] = sigma_trace;
-        li[SMCMC_LANE_TRIALS * NP] = trials;
-        li[SMCMC_LANE_SUCCESSES * NP] = succ;
-        li[SMCMC_LANE_NEXT_UPDATE * NP] = next_update;
-        li[SMCMC_LANE_NACCEPT * NP] = naccept;
-        li[SMCMC_LANE_STEP_RMS_TRIALS * NP] = rms_trials;
-        li[SMCMC_LANE_LAST_ACCEPT * NP] = last_accept;
-        li[SMCMC_LANE_UPDATE_STATUS * NP] = status;
-        li[SMCMC_LANE_DECOMP_FULL * NP] = ufull;
-        li[SMCMC_LANE_CHAIN_STEPS * NP] = (int32_t)tstep;
-        li[SMCMC_LANE_UPDATE_COUNT * NP] = update_count;
-        li[SMCMC_LANE_LAST_UPDATE_PATH * NP] = last_path;
+        if (cs.status == kPcNeedsLadder || cs.status == kPcInvalidTrace) atomicAdd(kp->flag_count, 1);
+        cs.store(lf, li, NP);
     }
 }
 

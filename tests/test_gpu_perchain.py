@@ -212,6 +212,22 @@ def test_frozen_covariance_and_metropolis_modes(gpu, oracle):
     _same(e, chains, "forced step")
 
 
+def test_update_proposal_of_a_covariance_without_a_trace(gpu, oracle):
+    """A covariance whose trace is not positive (TSimpleMCMC.H:1025-1028, where the reference throws): UpdateProposal
+    counts the call, leaves everything else of the chain alone and reports it."""
+    dim = 5
+    e, chains = _make(gpu, oracle, dim, 3)
+    _step(e, chains, 20)
+    _both(e, chains, "SetCovariance", "set_covariance", np.zeros((dim, dim)))
+    with pytest.raises(gpu.SmcmcError, match="Invalid trace"):
+        e.UpdateProposal()
+    for ch in chains.values():
+        ch.update_proposal()
+        assert ch.scalars["failed"] == 1
+    _same(e, chains, "UpdateProposal without a trace")
+    assert np.all(e.lane("update_status")[:3] == 3)
+
+
 def test_the_fallback_ladder_inside_a_launch(gpu, oracle):
     """A covariance whose Cholesky pivot fails when the chain's own schedule fires: the chain stops inside the launch,
     the host runs the ladder of TSimpleMCMC.H:1134-1389 for it (here: conditioning, rung 1) and the chain catches up;

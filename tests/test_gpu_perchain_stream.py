@@ -185,6 +185,22 @@ def test_state_round_trips(gpu, oracle):
     _same(e2, chains2, "forced step")
 
 
+def test_update_proposal_of_a_covariance_without_a_trace(gpu, oracle):
+    """A covariance whose trace is not positive (TSimpleMCMC.H:1025-1028, where the reference throws): UpdateProposal
+    counts the call, leaves everything else of the chain alone and reports it."""
+    dim = 64
+    e, chains = _make(gpu, oracle, dim, 2)
+    _step(e, chains, 20)
+    _both(e, chains, "SetCovariance", "set_covariance", np.zeros((dim, dim)))
+    with pytest.raises(gpu.SmcmcError, match="Invalid trace"):
+        e.UpdateProposal()
+    for ch in chains.values():
+        ch.update_proposal()
+        assert ch.scalars["failed"] == 1
+    _same(e, chains, "UpdateProposal without a trace")
+    assert np.all(e.lane("update_status")[:2] == 3)
+
+
 def test_snapshot_and_rollback(gpu, oracle):
     """20 steps, snapshot, 30 steps, rollback, 30 steps: the same bits as 50 straight (the working copies are not part of
     a snapshot: every launch reads the images)."""
