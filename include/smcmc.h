@@ -63,7 +63,12 @@ typedef enum {
     /* example/FakeLikelihood.H: a binned Poisson likelihood over a simulated event sample, re-weighted and corrected by
      * nine systematic parameters (the definition follows below, "event sample").  dim = 9, Metropolis engine, frozen /
      * pooled / SMCMC_MODE_PER_CHAIN on the one-chain-per-wavefront kernel, reference-order arithmetic only. */
-    SMCMC_LIKE_EVENT_SAMPLE = 7
+    SMCMC_LIKE_EVENT_SAMPLE = 7,
+    /* example2/FakeLikelihood.H: the same analysis as a template fit -- the fitted parameters 0 and 1 are the signal and
+     * background event counts, each class of the simulated sample is normalised by its own integral at every evaluation,
+     * and penalty terms keep the corner cases in check (the definition follows below, "event template").  dim = 9; served
+     * and refused exactly where SMCMC_LIKE_EVENT_SAMPLE is. */
+    SMCMC_LIKE_EVENT_TEMPLATE = 8
 } smcmc_likelihood;
 
 /* ---- SMCMC_LIKE_EVENT_SAMPLE: the definition ------------------------------------------------------------------
@@ -122,6 +127,46 @@ typedef enum {
  * the parameter rules above (smcmc_event_sample_last_error has the text of the latest failure of the calling thread). */
 int smcmc_event_sample_evaluate(const double* params, int count, const double* point, double* logl, double* hist);
 const char* smcmc_event_sample_last_error(void);
+
+/* ---- SMCMC_LIKE_EVENT_TEMPLATE: the definition ----------------------------------------------------------------
+ * The point is p[9], in the order of example2/SystematicCorrection.H:11-22 (the names above); p[0] and p[1] are the
+ * fitted numbers of signal and background events.
+ *
+ * The parameter array is SMCMC_LIKE_EVENT_SAMPLE's, field for field and rule for rule, and three rules more:
+ * exposureRatio (slot 4) is exactly 1.0 (example2 has none), at least one event has Type 0 and at least one Type > 0.
+ * Anything else is SMCMC_ERR_INVALID with a message.
+ *
+ * Once per evaluation: scale, width, skew, sepS, sepB, cf, ce as above (example2's mass and separation corrections are
+ * example's line for line).  The event weights (example2/SystematicCorrection.H:76-115, WEIGHT_SIGNAL_ANYWAY undefined)
+ * have no exp(p[0] / 10) factor and no exposure factor; 1.0 * w is w:
+ *   signal, untagged      (1 - cf) / (1 - trueFakes)            signal, tagged      cf / trueFakes
+ *   background, untagged  (1 - ce) / (1 - trueEfficiency)       background, tagged  ce / trueEfficiency
+ * Per event: the corrected mass, the scaled separation, the cuts, the split into Close / Separated / DecayTag and the
+ * bin rule are those above.
+ *   1. Six histograms, S[3][nbins] from the Type 0 events and B[3][nbins] from the Type > 0 events; a bin's content is
+ *      the sum of its events' weights in event order, un-fused, from +0 (example2/FakeLikelihood.H:232-264).
+ *   2. IS = (sum DecayTagS + sum CloseS) + sum SeparatedS (:266-268): each of the three sums over the bins ascending, from
+ *      +0, the three added in that order.  Under- and overflow -- the dropped events -- are not in it.  ws = p[0] / IS, one
+ *      IEEE division (:269-270).  IB and wb = p[1] / IB likewise (:273-277).
+ *   3. mc[h][b] = (0.0 + ws * S[h][b]) + wb * B[h][b] (:280-288): two products and an addition, un-fused.
+ *   4. The bin sum: steps 3 and 4 above over Close, Separated, DecayTag with this mc (:64-89).
+ *   5. The penalties, in this order (:91-115):
+ *        if (p[0] < 0) logL -= 10.0 + fabs(logL);   then the same for p[1], on the logL just updated;
+ *        v = p[6] / 5.0;  logL -= (0.5 * v) * v;    v = p[7] / 1.0;  logL -= (0.5 * v) * v;    v = p[8] / 1.0;  likewise.
+ *   6. Nothing is special-cased: a class none of whose events survives at a point has IS == 0, ws is +-inf or NaN, mc is
+ *      NaN and logL is NaN, on the host and on the device alike; the step's test rejects it as non-finite.
+ * Steps 2 and 3 restate TH1::Integral and TH1::Add and are not pinned against ROOT (absent where this was written), as
+ * the bin rule says of itself.
+ * No histogram takes events of both types, so a stable partition of the events by Type, signal first, leaves every
+ * sum's order of additions as it was: the engine packs the sample that way, and an interleaved array gives the bits of
+ * the same events sorted.
+ *
+ * On the host: params / count as above, point[9]; *logl the log-likelihood, hist (may be NULL) mc[3][nbins] before the
+ * clamp, parts (may be NULL) 6 nbins + 4 doubles: S[3][nbins], B[3][nbins], then IS, IB, ws, wb -- what
+ * WriteSimulation and the tests of the intermediate stages need.  The same bits as the device; it never steps a chain.
+ * smcmc_event_sample_last_error serves this entry point too. */
+int smcmc_event_template_evaluate(const double* params, int count, const double* point, double* logl, double* hist,
+                                  double* parts);
 
 /* How the proposal covariance adapts over the ensemble. */
 typedef enum {

@@ -10,6 +10,12 @@
  * Everything of an event that does not depend on the point is in there already: nominalLogMass, the difference
  * logMass - nominalLogMass and its quotient by nominalLogSigma (SystematicCorrection.H:57-62).  class = 2 (Type > 0) +
  * 1 (MuDk > 0) picks one of four weights, which depend on the point alone.
+ *
+ * SMCMC_LIKE_EVENT_TEMPLATE (example2/ of the reference; smcmc.h states the definition) shares the layout, the per-event
+ * part and the bin term; its own arithmetic -- the four weights, the class integral, the normalisation, the expectation
+ * of a bin and the penalties -- is the smcmc_et_* functions below.  For it es_pack partitions the events by class, signal
+ * first and otherwise in the caller's order, and writes the number of signal events to the header (SMCMC_ES_H_NSIGNAL): no
+ * histogram takes events of both classes, so no sum's order of additions changes.
  */
 #ifndef SMCMC_EVENT_SAMPLE_H_SEEN
 #define SMCMC_EVENT_SAMPLE_H_SEEN
@@ -19,6 +25,7 @@
 enum {
     SMCMC_ES_H_NEVENTS = 0, SMCMC_ES_H_NBINS, SMCMC_ES_H_XMIN, SMCMC_ES_H_XMAX, SMCMC_ES_H_EXPOSURE, SMCMC_ES_H_CUT,
     SMCMC_ES_H_TRUE_FAKES, SMCMC_ES_H_TRUE_EFF, SMCMC_ES_H_TAN_FAKES, SMCMC_ES_H_TAN_EFF, SMCMC_ES_H_RANGE,
+    SMCMC_ES_H_NSIGNAL,         /* EVENT_TEMPLATE: events [0, nsignal) are the signal's, the rest the background's */
     SMCMC_ES_HEADER = 16,       /* doubles in front of the data */
     SMCMC_ES_EVENT = 6,         /* doubles per packed event */
     SMCMC_ES_PARAM_HEADER = 8,  /* doubles in front of the data in the caller's array (smcmc.h) */
@@ -31,23 +38,36 @@ typedef struct {
     double weight[4];                   /* by class */
 } smcmc_es_scalars;
 
-/* p: the point; the other arguments: the header's values of those names */
-SMCMC_HD void smcmc_es_point_scalars(const double* p, double exposure, double true_fakes, double true_eff,
-                                     double tan_fakes, double tan_eff, smcmc_es_scalars* s) {
-    const double pi = 3.14159265358979323846;                       /* M_PI */
+/* the part of the scalars that corrects an event's mass and separation (SystematicCorrection.H:40-43, 64-68) */
+SMCMC_HD void smcmc_es_mass_scalars(const double* p, smcmc_es_scalars* s) {
     s->scale = p[2] / 10.0;                                          /* SystematicCorrection.H:64 */
     s->width = smcmc_exp(p[3] / 10.0);                               /* :65 */
     s->skew = 0.3 * smcmc_erf(p[4] / 10.0);                          /* :68 */
     s->sep[0] = smcmc_exp(p[5] / 10.0);                              /* :40, 43 */
     s->sep[1] = smcmc_exp(p[6] / 10.0);                              /* :41, 43 */
-    const double ws = smcmc_exp(p[0] / 10.0);                        /* :87 */
-    const double wb = smcmc_exp(p[1] / 10.0);                        /* :88 */
+}
+
+/* the corrected fake probability and decay-tag efficiency (:94-96, 106-108) */
+SMCMC_HD void smcmc_es_tag_fractions(const double* p, double tan_fakes, double tan_eff, double* fakes, double* eff) {
+    const double pi = 3.14159265358979323846;                       /* M_PI */
     double cf = tan_fakes;                                           /* :94 */
     cf += p[7];                                                      /* :95 */
     cf = smcmc_atan(cf) / pi + 0.5;                                  /* :96 */
     double ce = tan_eff;                                             /* :106 */
     ce += p[8];                                                      /* :107 */
     ce = smcmc_atan(ce) / pi + 0.5;                                  /* :108 */
+    *fakes = cf;
+    *eff = ce;
+}
+
+/* p: the point; the other arguments: the header's values of those names */
+SMCMC_HD void smcmc_es_point_scalars(const double* p, double exposure, double true_fakes, double true_eff,
+                                     double tan_fakes, double tan_eff, smcmc_es_scalars* s) {
+    smcmc_es_mass_scalars(p, s);
+    const double ws = smcmc_exp(p[0] / 10.0);                        /* :87 */
+    const double wb = smcmc_exp(p[1] / 10.0);                        /* :88 */
+    double cf, ce;
+    smcmc_es_tag_fractions(p, tan_fakes, tan_eff, &cf, &ce);
     s->weight[0] = (ws * ((1.0 - cf) / (1.0 - true_fakes))) * exposure;   /* :100, 115 */
     s->weight[1] = (ws * (cf / true_fakes)) * exposure;                   /* :99, 115 */
     s->weight[2] = (wb * ((1.0 - ce) / (1.0 - true_eff))) * exposure;     /* :112, 115 */
@@ -80,6 +100,53 @@ SMCMC_HD double smcmc_es_bin_term(double data, double mc) {
     double v = data - mc;
     if (data > 0.0) v += data * smcmc_log(mc / data);
     return v;
+}
+
+/* ---- SMCMC_LIKE_EVENT_TEMPLATE (example2/) ---- */
+
+/* The scalars of example2/SystematicCorrection.H: the mass and separation corrections are example's line for line; the
+ * weights (:76-115, WEIGHT_SIGNAL_ANYWAY undefined) carry neither exp(p[0] / 10) nor an exposure ratio. */
+SMCMC_HD void smcmc_et_point_scalars(const double* p, double true_fakes, double true_eff, double tan_fakes, double tan_eff,
+                                     smcmc_es_scalars* s) {
+    smcmc_es_mass_scalars(p, s);
+    double cf, ce;
+    smcmc_es_tag_fractions(p, tan_fakes, tan_eff, &cf, &ce);
+    s->weight[0] = (1.0 - cf) / (1.0 - true_fakes);                  /* example2/SystematicCorrection.H:99 */
+    s->weight[1] = cf / true_fakes;                                  /* :98 */
+    s->weight[2] = (1.0 - ce) / (1.0 - true_eff);                    /* :111 */
+    s->weight[3] = ce / true_eff;                                    /* :110 */
+}
+
+/* A class's integral from the sums of its three histograms over their bins (each ascending, from +0), added in the
+ * order of example2/FakeLikelihood.H:266-268: DecayTag, then Close, then Separated.  TH1::Integral restated: under- and
+ * overflow -- the dropped events -- are in none of the three. */
+SMCMC_HD double smcmc_et_integral(double close, double separated, double decay_tag) {
+    double v = decay_tag;
+    v += close;
+    v += separated;
+    return v;
+}
+
+/* the factor that makes a class's histograms integrate to the fitted count (:269-270, 276-277): one IEEE division; an
+ * empty class gives +-inf or NaN and nothing here looks at it */
+SMCMC_HD double smcmc_et_norm(double count, double integral) { return count / integral; }
+
+/* the signal's share of a bin's expectation (:280 ..: TH1::Add into a histogram that was reset) */
+SMCMC_HD double smcmc_et_mc_signal(double ws, double s) { return 0.0 + ws * s; }
+/* ... and the bin's expectation, the background's share added to it */
+SMCMC_HD double smcmc_et_mc(double signal_share, double wb, double b) { return signal_share + wb * b; }
+
+/* the penalty terms on the bin sum (:91-115), p the point */
+SMCMC_HD double smcmc_et_penalties(double logl, const double* p) {
+    if (p[0] < 0.0) logl -= 10.0 + __builtin_fabs(logl);             /* :96 */
+    if (p[1] < 0.0) logl -= 10.0 + __builtin_fabs(logl);             /* :100 */
+    double v = p[6] / 5.0;                                           /* :104 */
+    logl -= (0.5 * v) * v;
+    v = p[7] / 1.0;                                                  /* :109 */
+    logl -= (0.5 * v) * v;
+    v = p[8] / 1.0;                                                  /* :114 */
+    logl -= (0.5 * v) * v;
+    return logl;
 }
 
 #endif

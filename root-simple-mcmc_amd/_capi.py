@@ -15,6 +15,7 @@ OK, ERR_INVALID, ERR_LOGIC, ERR_RUNTIME, ERR_BAD_START, ERR_UNSUPPORTED, ERR_HIP
 LIKE_ISO_GAUSS, LIKE_QUADFORM, LIKE_ROSENBROCK, LIKE_USER = 0, 1, 2, 3
 LIKE_ASYM, LIKE_HORRIFIC, LIKE_CONSTRAINED = 4, 5, 6   # the reference's stress targets (smcmc.h)
 LIKE_EVENT_SAMPLE = 7   # example/FakeLikelihood.H: binned Poisson likelihood over a simulated event sample, dim = 9
+LIKE_EVENT_TEMPLATE = 8   # example2/FakeLikelihood.H: the same sample as a template fit of the two event counts, dim = 9
 EVENT_SAMPLE_MAX_BINS = 97   # SMCMC_EVENT_SAMPLE_MAX_BINS of include/smcmc.h
 MODE_FROZEN, MODE_POOLED, MODE_PER_CHAIN = 0, 1, 2
 
@@ -200,6 +201,7 @@ SIGNATURES = {
     "smcmc_vaat_rollback": (C.c_int, [_H]),
     "smcmc_event_sample_evaluate": (C.c_int, [_dp, C.c_int, _dp, _dp, _dp]),
     "smcmc_event_sample_last_error": (C.c_char_p, []),
+    "smcmc_event_template_evaluate": (C.c_int, [_dp, C.c_int, _dp, _dp, _dp, _dp]),
     "smcmc_selftest_detmath": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]),
     "smcmc_selftest_mfma": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp]),
     "smcmc_selftest_mfma_strip": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp]),

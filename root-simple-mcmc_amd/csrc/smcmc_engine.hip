@@ -84,7 +84,8 @@ struct smcmc_engine {
     DeviceBuffer<double> d_U;
     DeviceBuffer<double> d_Uop;    // large dimensions, fused order: U^T in matrix-operand order (smcmc_panel_mfma_kernel.hip.h)
     DeviceBuffer<double> d_like;
-    int like_lds_bytes = 0;   // SMCMC_LIKE_EVENT_SAMPLE: dynamic LDS of a step launch (the lanes' histograms)
+    int like_lds_bytes = 0;   // SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE: dynamic LDS of a step launch (the lanes' histograms)
+    DeviceBuffer<double> d_like_park;   // SMCMC_LIKE_EVENT_TEMPLATE: the park image [3 nbins][npad] (event_template_loglike); no chain state
     // QUADFORM with a sparse Error matrix: the non-zero entries of Error^T, row by row (quadform_csr); empty = dense only
     DeviceBuffer<int32_t> d_like_rowptr;
     DeviceBuffer<int32_t> d_like_cols;
@@ -362,16 +363,24 @@ int upload_like(smcmc_engine* h) {
             for (int j = 0; j < D; ++j) et[(size_t)i * D + j] = h->like_params[(size_t)j * D + i];
         return upload_padded(h, et.data(), h->d_like);
     }
-    if (h->likelihood == SMCMC_LIKE_EVENT_SAMPLE) {
+    if (event_likelihood(h->likelihood)) {
         // the sample in the engine's own layout (include/smcmc_event_sample.h): what does not depend on the point -- the
         // three logarithms of an event and their quotient, the two tangents -- is computed here, once
         if (!h->exact)
             return fail(h, SMCMC_ERR_UNSUPPORTED, "the event-sample likelihood runs in reference-order arithmetic only (SMCMC_P_EXACT_ARITHMETIC = 1)");
         std::vector<double> packed;
-        smcmc::es_pack(h->like_params.data(), packed);
-        if (h->d_like.size() < packed.size()) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));          // nothing in flight reads the old image
-            HIP_TRY(h, h->d_like.allocate(packed.size()));
+        const bool tmpl = h->likelihood == SMCMC_LIKE_EVENT_TEMPLATE;
+        smcmc::es_pack(h->like_params.data(), packed, tmpl);       // (the template's events partitioned by class)
+        // the template's park image, [3 nbins][npad], comes with the parameters; all or nothing: a second allocation that
+        // fails leaves the engine with the images and sizes it had
+        const size_t park = tmpl ? (size_t)3 * (size_t)packed[SMCMC_ES_H_NBINS] * (size_t)h->npad : 0;
+        if (h->d_like.size() < packed.size() || h->d_like_park.size() < park) {
+            HIP_TRY(h, hipStreamSynchronize(h->stream));          // nothing in flight reads the old images
+            DeviceBuffer<double> like, image;
+            if (h->d_like.size() < packed.size()) HIP_TRY(h, like.allocate(packed.size()));
+            if (h->d_like_park.size() < park) HIP_TRY(h, image.allocate(park));
+            if (like) h->d_like = std::move(like);
+            if (image) h->d_like_park = std::move(image);
         }
         HIP_TRY(h, hipMemcpyAsync(h->d_like, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -836,7 +845,7 @@ PerChainParams pc_params(smcmc_engine* h, const StepParams& p) {
 bool pc_use_wave(const smcmc_engine* h) {
     if (!smcmc::perchain_wave_serves(h->likelihood)) return false;
     if (h->likelihood == SMCMC_LIKE_USER) return true;     // (the one-chain-per-lane kernel has no user instantiation)
-    if (h->likelihood == SMCMC_LIKE_EVENT_SAMPLE) return true;   // (nor an event-sample one: smcmc_set_param refuses the request)
+    if (event_likelihood(h->likelihood)) return true;   // (nor an event-sample one: smcmc_set_param refuses the request)
     if (h->pc_wave >= 0) return h->pc_wave != 0;
     return true;     // measured faster at every ensemble size, 1 to 65 536 chains (profiles/r04_notes.md)
 }
@@ -931,6 +940,7 @@ StepParams make_params(smcmc_engine* h, int nsteps, int metropolis) {
     p.proposed = h->keep_proposed ? h->d_proposed.get() : nullptr;
     p.prof = static_cast<unsigned long long*>(h->d_step_prof);
     p.like_lds_bytes = h->like_lds_bytes;
+    p.like_park = h->d_like_park;
     p.uniform = h->d_uniform;
     for (int d = 0; d < h->dim && d < 64; ++d)   // the register kernels (dim <= 63); larger dimensions carry theirs in d_uniform
         if (P.ptype[d] == 1) p.uniform_mask |= (uint64_t)1 << d;
@@ -1114,7 +1124,7 @@ int launch(smcmc_engine* h, int nsteps, int metropolis, int stride, double* save
     if ((p.scan_dim >= 0 || p.uniform_mask != 0) && !exact)
         return fail(h, SMCMC_ERR_UNSUPPORTED,
                     "uniform proposals and the scan of a dimension run in reference-order arithmetic only");
-    if (h->likelihood == SMCMC_LIKE_EVENT_SAMPLE && !exact)
+    if (event_likelihood(h->likelihood) && !exact)
         return fail(h, SMCMC_ERR_UNSUPPORTED, "the event-sample likelihood runs in reference-order arithmetic only (SMCMC_P_EXACT_ARITHMETIC = 1)");
     hipError_t e = dispatch_step(h->dp, p, h->likelihood, exact, fullu, moments, h->stream);
     if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("step kernel launch: ") + hipGetErrorString(e));
@@ -1154,12 +1164,12 @@ int smcmc_create(int dim, int nchains, int likelihood, uint64_t seed, uint32_t c
     if (!out) return SMCMC_ERR_INVALID;
     *out = nullptr;
     if (dim < 1 || nchains < 1) return SMCMC_ERR_INVALID;
-    if (likelihood < SMCMC_LIKE_ISO_GAUSS || likelihood > SMCMC_LIKE_EVENT_SAMPLE) return SMCMC_ERR_INVALID;
+    if (likelihood < SMCMC_LIKE_ISO_GAUSS || likelihood > SMCMC_LIKE_EVENT_TEMPLATE) return SMCMC_ERR_INVALID;
 #ifndef SMCMC_USER_LIKELIHOOD
     if (likelihood == SMCMC_LIKE_USER) return SMCMC_ERR_UNSUPPORTED;   // this build carries no user likelihood
 #endif
     // the event sample has the nine systematic parameters of SystematicCorrection.H:11-22 and no other dimension
-    if (likelihood == SMCMC_LIKE_EVENT_SAMPLE && dim != SMCMC_ES_DIM) return SMCMC_ERR_UNSUPPORTED;
+    if (event_likelihood(likelihood) && dim != SMCMC_ES_DIM) return SMCMC_ERR_UNSUPPORTED;
     if (likelihood == SMCMC_LIKE_ROSENBROCK && dim < 2) return SMCMC_ERR_INVALID;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return SMCMC_ERR_NO_DEVICE;
@@ -1255,8 +1265,8 @@ int smcmc_set_stream(smcmc_engine* h, void* hip_stream) {
 int smcmc_set_likelihood_params(smcmc_engine* h, const double* params, int count) {
     if (!h || count < 0 || (count > 0 && !params)) return SMCMC_ERR_INVALID;
     ON_DEVICE(h);
-    if (h->likelihood == SMCMC_LIKE_EVENT_SAMPLE) {            // (checked before it replaces what a started engine runs on)
-        const char* why = smcmc::es_check(params, (size_t)count);
+    if (event_likelihood(h->likelihood)) {            // (checked before it replaces what a started engine runs on)
+        const char* why = smcmc::es_check_like(h->likelihood, params, (size_t)count);
         if (why) return fail(h, SMCMC_ERR_INVALID, why);
     }
     h->like_params.assign(params, params + count);
@@ -1378,7 +1388,7 @@ int smcmc_set_param(smcmc_engine* h, int which, double v) {
             return (per_chain(h) && h->started) ? broadcast_lane_f64(h, SMCMC_LANE_CENTER_TRIALS, v) : SMCMC_OK;
         case SMCMC_P_COVARIANCE_FROZEN: h->pc_frozen = (v != 0.0); return SMCMC_OK;
         case SMCMC_P_PERCHAIN_WAVE:
-            if (v == 0.0 && h->likelihood == SMCMC_LIKE_EVENT_SAMPLE)
+            if (v == 0.0 && event_likelihood(h->likelihood))
                 return fail(h, SMCMC_ERR_UNSUPPORTED, "the event-sample likelihood adapts per chain on the one-chain-per-wavefront "
                                                       "kernel only (64 lanes share the events of one chain)");
             h->pc_wave = (v < 0.0) ? -1 : (v != 0.0 ? 1 : 0);
@@ -1399,7 +1409,7 @@ int smcmc_set_param(smcmc_engine* h, int which, double v) {
             h->dense_quadform = (v != 0.0);
             return (h->started && h->likelihood == SMCMC_LIKE_QUADFORM) ? upload_like_csr(h) : SMCMC_OK;
         case SMCMC_P_EXACT_ARITHMETIC:
-            if (v == 0.0 && h->likelihood == SMCMC_LIKE_EVENT_SAMPLE)
+            if (v == 0.0 && event_likelihood(h->likelihood))
                 return fail(h, SMCMC_ERR_UNSUPPORTED, "the event-sample likelihood runs in reference-order arithmetic only (SMCMC_P_EXACT_ARITHMETIC = 1)");
             h->exact = (v != 0.0);
             if (h->started) {                                  // the fused order keeps its own operand images
@@ -1548,7 +1558,7 @@ static int place_chains(smcmc_engine* h, const double* x0, int broadcast, std::v
         q.has_forced = 0;
         hipError_t e = launch_panel_mfma(q, h->likelihood, h->stream);
         if (e != hipSuccess) return fail(h, SMCMC_ERR_HIP, std::string("start kernel launch: ") + hipGetErrorString(e));
-    } else if (h->panel_w || (h->mode == SMCMC_MODE_PER_CHAIN && h->likelihood != SMCMC_LIKE_EVENT_SAMPLE)) {
+    } else if (h->panel_w || (h->mode == SMCMC_MODE_PER_CHAIN && !event_likelihood(h->likelihood))) {
         // (the event sample's start of a per-chain ensemble takes the branch below: the forced step of the
         // one-chain-per-lane kernel family, which shares the [dim_padded][chain] image of the point)
         hipError_t e;

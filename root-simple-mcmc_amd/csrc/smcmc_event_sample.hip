@@ -1,5 +1,5 @@
-// smcmc_event_sample.hip -- smcmc_event_sample_evaluate (include/smcmc.h): SMCMC_LIKE_EVENT_SAMPLE evaluated on the
-// host from the header the device kernels compile (include/smcmc_event_sample.h), for what the reference does outside
+// smcmc_event_sample.hip -- smcmc_event_sample_evaluate and smcmc_event_template_evaluate (include/smcmc.h):
+// SMCMC_LIKE_EVENT_SAMPLE and SMCMC_LIKE_EVENT_TEMPLATE evaluated on the host from the header the device kernels compile (include/smcmc_event_sample.h), for what the reference does outside
 // Step(): Init()'s exposure ratio and WriteSimulation() (example/FakeLikelihood.H:107-143, 173-179).  No chain is
 // stepped here.  Compile with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -27,6 +27,24 @@ extern "C" int smcmc_event_sample_evaluate(const double* params, int count, cons
     std::vector<double> packed;
     smcmc::es_pack(params, packed);
     *logl = smcmc::es_evaluate_packed(packed.data(), point, hist);
+    es_error.clear();
+    return SMCMC_OK;
+}
+
+extern "C" int smcmc_event_template_evaluate(const double* params, int count, const double* point, double* logl, double* hist,
+                                             double* parts) {
+    if (!point || !logl || count < 0) {
+        es_error = "smcmc_event_template_evaluate: point and logl must be given";
+        return SMCMC_ERR_INVALID;
+    }
+    const char* why = smcmc::et_check(params, (size_t)count);
+    if (why) {
+        es_error = why;
+        return SMCMC_ERR_INVALID;
+    }
+    std::vector<double> packed;
+    smcmc::es_pack(params, packed, true);
+    *logl = smcmc::et_evaluate_packed(packed.data(), point, hist, parts);
     es_error.clear();
     return SMCMC_OK;
 }

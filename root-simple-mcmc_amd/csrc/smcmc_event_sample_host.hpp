@@ -1,4 +1,4 @@
-// smcmc_event_sample_host.hpp -- host side of SMCMC_LIKE_EVENT_SAMPLE: the rules of the caller's parameter array
+// smcmc_event_sample_host.hpp -- host side of SMCMC_LIKE_EVENT_SAMPLE and SMCMC_LIKE_EVENT_TEMPLATE: the rules of the caller's parameter array
 // (smcmc.h), the engine's packed layout of it (include/smcmc_event_sample.h) and the likelihood evaluated on the host
 // from that layout, the walk the device kernels make.
 #pragma once
@@ -41,8 +41,28 @@ inline const char* es_check(const double* p, size_t count) {
     return nullptr;
 }
 
-// the packed layout of a checked parameter array
-inline void es_pack(const double* p, std::vector<double>& out) {
+// ... when it is a well-formed sample of SMCMC_LIKE_EVENT_TEMPLATE: the same array and rules, and three more
+inline const char* et_check(const double* p, size_t count) {
+    if (const char* why = es_check(p, count)) return why;
+    if (p[4] != 1.0) return "EVENT_TEMPLATE: exposureRatio must be exactly 1 (example2 has no exposure ratio)";
+    const size_t nev = (size_t)p[0], nbins = (size_t)p[1];
+    const double* ev = p + SMCMC_ES_PARAM_HEADER + 3 * nbins;
+    size_t nsig = 0;
+    for (size_t e = 0; e < nev; ++e) nsig += (ev[6 * e + 1] > 0.0) ? 0 : 1;
+    if (nsig == 0) return "EVENT_TEMPLATE: at least one event must be signal (Type 0)";
+    if (nsig == nev) return "EVENT_TEMPLATE: at least one event must be background (Type > 0)";
+    return nullptr;
+}
+
+// the rules of `likelihood`'s parameter array (SMCMC_LIKE_EVENT_SAMPLE or SMCMC_LIKE_EVENT_TEMPLATE)
+inline const char* es_check_like(int likelihood, const double* p, size_t count) {
+    return likelihood == SMCMC_LIKE_EVENT_TEMPLATE ? et_check(p, count) : es_check(p, count);
+}
+
+// The packed layout of a checked parameter array.  by_class (SMCMC_LIKE_EVENT_TEMPLATE): the events stably partitioned,
+// signal first, and their number in the header; no histogram of that likelihood takes events of both classes, so every
+// sum keeps its order of additions.
+inline void es_pack(const double* p, std::vector<double>& out, bool by_class = false) {
     const size_t nev = (size_t)p[0], nbins = (size_t)p[1];
     out.assign((size_t)SMCMC_ES_HEADER + 3 * nbins + (size_t)SMCMC_ES_EVENT * nev, 0.0);
     const double pi = 3.14159265358979323846;
@@ -54,6 +74,12 @@ inline void es_pack(const double* p, std::vector<double>& out) {
     for (size_t i = 0; i < 3 * nbins; ++i) out[SMCMC_ES_HEADER + i] = p[SMCMC_ES_PARAM_HEADER + i];
     const double* ev = p + SMCMC_ES_PARAM_HEADER + 3 * nbins;
     double* dst = out.data() + SMCMC_ES_HEADER + 3 * nbins;
+    size_t nsig = 0;
+    if (by_class) {
+        for (size_t e = 0; e < nev; ++e) nsig += (ev[6 * e + 1] > 0.0) ? 0 : 1;
+        out[SMCMC_ES_H_NSIGNAL] = (double)nsig;
+    }
+    size_t at[2] = {0, nsig};                                       // the next packed slot of a signal / a background event
     for (size_t e = 0; e < nev; ++e) {
         const double* q = ev + 6 * e;
         const double mass = q[0], true_mass = q[4], true_sigma = q[5];
@@ -62,7 +88,7 @@ inline void es_pack(const double* p, std::vector<double>& out) {
         nominalLogSigma = nominalLogSigma - nominalLogMass;                            // :59
         const double logMass = smcmc_log(mass);                                        // :61
         const double logSigma = (logMass - nominalLogMass) / nominalLogSigma;          // :62
-        double* d = dst + (size_t)SMCMC_ES_EVENT * e;
+        double* d = dst + (size_t)SMCMC_ES_EVENT * (by_class ? at[q[1] > 0.0 ? 1 : 0]++ : e);
         d[0] = nominalLogMass;
         d[1] = logMass - nominalLogMass;
         d[2] = logSigma;
@@ -92,6 +118,49 @@ inline double es_evaluate_packed(const double* pk, const double* point, double* 
     if (hist)
         for (int r = 0; r < 3 * nbins; ++r) hist[r] = h[r];
     return logl;
+}
+
+// SMCMC_LIKE_EVENT_TEMPLATE from the packed layout (made with by_class): log L at point[9]; hist (may be null): the
+// expectation [3][nbins] before the clamp; parts (may be null): S[3][nbins], B[3][nbins], IS, IB, ws, wb.  The device
+// kernels make this walk with these functions.
+inline double et_evaluate_packed(const double* pk, const double* point, double* hist, double* parts) {
+    const int nev = (int)pk[SMCMC_ES_H_NEVENTS], nbins = (int)pk[SMCMC_ES_H_NBINS], nsig = (int)pk[SMCMC_ES_H_NSIGNAL];
+    const int rows = 3 * nbins;
+    smcmc_es_scalars s;
+    smcmc_et_point_scalars(point, pk[SMCMC_ES_H_TRUE_FAKES], pk[SMCMC_ES_H_TRUE_EFF], pk[SMCMC_ES_H_TAN_FAKES],
+                           pk[SMCMC_ES_H_TAN_EFF], &s);
+    std::vector<double> h((size_t)2 * rows, 0.0);                   // S, then B
+    const double* ev = pk + SMCMC_ES_HEADER + rows;
+    double integral[2], norm[2];
+    for (int c = 0; c < 2; ++c) {
+        double* hc = h.data() + (size_t)c * rows;
+        for (int e = c ? nsig : 0; e < (c ? nev : nsig); ++e) {
+            const double* q = ev + (size_t)SMCMC_ES_EVENT * e;
+            const int cls = (int)q[4];
+            const int b = smcmc_es_event_bin(q[0], q[1], q[2], q[3], cls >> 1, cls & 1, &s, nbins, pk[SMCMC_ES_H_XMIN],
+                                             pk[SMCMC_ES_H_XMAX], pk[SMCMC_ES_H_RANGE], pk[SMCMC_ES_H_CUT]);
+            if (b >= 0) hc[b] = hc[b] + s.weight[cls];
+        }
+        double sum[3];
+        for (int k = 0; k < 3; ++k) {
+            sum[k] = 0.0;
+            for (int b = 0; b < nbins; ++b) sum[k] += hc[k * nbins + b];
+        }
+        integral[c] = smcmc_et_integral(sum[0], sum[1], sum[2]);
+        norm[c] = smcmc_et_norm(point[c], integral[c]);
+    }
+    double logl = 0.0;
+    for (int r = 0; r < rows; ++r) {
+        const double mc = smcmc_et_mc(smcmc_et_mc_signal(norm[0], h[r]), norm[1], h[(size_t)rows + r]);
+        if (hist) hist[r] = mc;
+        logl += smcmc_es_bin_term(pk[SMCMC_ES_HEADER + r], mc);
+    }
+    if (parts) {
+        for (int r = 0; r < 2 * rows; ++r) parts[r] = h[r];
+        parts[2 * rows] = integral[0]; parts[2 * rows + 1] = integral[1];
+        parts[2 * rows + 2] = norm[0]; parts[2 * rows + 3] = norm[1];
+    }
+    return smcmc_et_penalties(logl, point);
 }
 
 }  // namespace smcmc

@@ -12,10 +12,11 @@ namespace smcmc {
 
 template <int DP, int LIKE, bool EXACT, bool FULLU, bool MOM, bool SPECIAL>
 static hipError_t go(const StepParams& p, hipStream_t s) {
-    if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE) {
+    if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE || LIKE == SMCMC_LIKE_EVENT_TEMPLATE) {
         // the lanes' histograms in dynamic LDS (event_sample_loglike): more than the default limit
         auto kernel = step_kernel<DP, LIKE, EXACT, FULLU, MOM, SPECIAL>;
         if (p.like_lds_bytes <= 0 || p.like_lds_bytes > event_sample_lds_bytes(SMCMC_EVENT_SAMPLE_MAX_BINS)) return hipErrorInvalidValue;
+        if (LIKE == SMCMC_LIKE_EVENT_TEMPLATE && !p.like_park) return hipErrorInvalidValue;     // (the park image, with the parameters)
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  event_sample_lds_bytes(SMCMC_EVENT_SAMPLE_MAX_BINS));
         if (e != hipSuccess) return e;
@@ -31,7 +32,7 @@ template <>
 hipError_t launch_step_like<SMCMC_DP, SMCMC_LIKE>(const StepParams& p, bool exact, bool fullu, bool mom, bool special,
                                                   hipStream_t s) {
     constexpr int DP = SMCMC_DP, LIKE = SMCMC_LIKE;
-#if SMCMC_LIKE == 7   // SMCMC_LIKE_EVENT_SAMPLE: reference-order arithmetic only (the engine refuses the fused order)
+#if SMCMC_LIKE == 7 || SMCMC_LIKE == 8   // SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE: reference-order arithmetic only (the engine refuses the fused order)
     if (!exact) return hipErrorNotSupported;
     if (special) {
         if (fullu) return mom ? go<DP, LIKE, true, true, true, true>(p, s) : go<DP, LIKE, true, true, false, true>(p, s);
@@ -52,7 +53,7 @@ hipError_t launch_step_like<SMCMC_DP, SMCMC_LIKE>(const StepParams& p, bool exac
 #endif
 }
 
-#if (SMCMC_LIKE != 3 || defined(SMCMC_USER_LIKELIHOOD)) && SMCMC_LIKE != 7   // 3 = SMCMC_LIKE_USER, 7 = SMCMC_LIKE_EVENT_SAMPLE, which the
+#if (SMCMC_LIKE != 3 || defined(SMCMC_USER_LIKELIHOOD)) && SMCMC_LIKE != 7 && SMCMC_LIKE != 8   // 3 = SMCMC_LIKE_USER; 7, 8 = SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE, which the
 // variable-at-a-time engine refuses (enumerators, invisible to the preprocessor)
 // the variable-at-a-time chains on the same likelihood code (smcmc_vaat_kernel.hip.h)
 template <>

@@ -226,7 +226,8 @@ struct StepParams {
     int zero;                  // always 0; makes table addresses depend on the step so that the
                                // compiler does not hoist (and then spill) whole tables out of the loop
     unsigned long long* prof;  // section profile (SMCMC_STEP_PROFILE builds only): [group][kProfSlots][64] cycle sums, added to
-    int like_lds_bytes;        // SMCMC_LIKE_EVENT_SAMPLE: dynamic LDS of the launch, the lanes' histograms (event_sample_lds_bytes)
+    int like_lds_bytes;        // SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE: dynamic LDS of the launch, the lanes' histograms (event_sample_lds_bytes)
+    double* like_park;         // SMCMC_LIKE_EVENT_TEMPLATE: the park image [3 nbins][npad] (event_template_loglike)
 };
 
 // ---- Section profile of the step loop: -DSMCMC_STEP_PROFILE=1 (sections) or 2 (sections and every piece) ----
@@ -472,6 +473,91 @@ __device__ __forceinline__ double event_sample_loglike(const double (&p)[DP], cp
     return logl;
 }
 
+// ---- SMCMC_LIKE_EVENT_TEMPLATE (smcmc.h; the arithmetic is include/smcmc_event_sample.h) ----
+// Six histograms per lane do not fit (154 KB at 50 bins beside kEsStaticLds), so the dynamic LDS stays
+// event_sample_lds_bytes(nbins) and the fill runs twice: over the signal events [0, nsignal), then, the rows zeroed again,
+// over the background events [nsignal, nevents), whose batches start at nsignal -- no batch straddles the classes.
+// Between the passes the lane sums its rows to the signal's integral and writes ws * S[r], the signal's share of every
+// bin, to its column of the park image: park[r][chain] in device memory, a row one coalesced 512-byte store of the
+// wavefront.  The bin sum reads the share back and adds wb * B[r].  A lane reads only what it wrote itself, in program
+// order: no fence.  The image is scratch of one evaluation, no chain state.
+// The fill of a lane's column `col` (zeroed by the caller) with the events [ebeg, nev) of `ev`, batches counted from ebeg:
+// event_sample_loglike's loop, batch for batch.  A second copy of that text, because the event sample calling a function
+// here -- this one over [0, nevents), or one for the batch alone -- changed its step kernels' control flow (sixteen more
+// scalar branches, other register numbers), and with its loop written out they are what they were, instruction for
+// instruction (profiles/event_template_notes.md).
+__device__ __forceinline__ void event_template_fill(double* const col, const cptr_f64 ev, const int ebeg, const int nev,
+                                                  const smcmc_es_scalars& s, const int nbins, const int rows,
+                                                  const double xmin, const double xmax, const double range, const double cut) {
+    for (int e0 = ebeg; e0 < nev; e0 += kEsBatch) {
+        int idx[kEsBatch];
+        double w[kEsBatch], v[kEsBatch];
+#pragma unroll
+        for (int u = 0; u < kEsBatch; ++u) {
+            const bool in = e0 + u < nev;                                   // (wave-uniform)
+            const cptr_f64 q = ev + (size_t)(in ? e0 + u : nev - 1) * SMCMC_ES_EVENT;
+            const int cls = (int)q[4];
+            const int b = smcmc_es_event_bin(q[0], q[1], q[2], q[3], cls >> 1, cls & 1, &s, nbins, xmin, xmax, range, cut);
+            idx[u] = (in && b >= 0) ? b : rows;
+            w[u] = (cls == 0) ? s.weight[0] : (cls == 1) ? s.weight[1] : (cls == 2) ? s.weight[2] : s.weight[3];
+        }
+#pragma unroll
+        for (int u = 0; u < kEsBatch; ++u) v[u] = col[idx[u] * kWave];
+#pragma unroll
+        for (int u = 0; u < kEsBatch; ++u) {
+#pragma unroll
+            for (int j = 0; j < u; ++j) v[u] = (idx[j] == idx[u]) ? v[j] : v[u];
+            v[u] = v[u] + w[u];
+        }
+#pragma unroll
+        for (int u = 0; u < kEsBatch; ++u) col[idx[u] * kWave] = v[u];
+    }
+}
+__device__ __forceinline__ double event_template_integral(const double* col, int nbins) {
+    double sum[3];
+    for (int k = 0; k < 3; ++k) {
+        const double* h = col + (size_t)k * nbins * kWave;
+        double v = 0.0;
+        for (int b = 0; b < nbins; ++b) v += h[b * kWave];
+        sum[k] = v;
+    }
+    return smcmc_et_integral(sum[0], sum[1], sum[2]);
+}
+// park: this lane's column of the image, rows npad apart
+template <int DP>
+__device__ __forceinline__ double event_template_loglike(const double (&p)[DP], cptr_f64 prm, double* hist, int lane,
+                                                         double* park, size_t npad) {
+    static_assert(DP >= SMCMC_ES_DIM, "the nine systematic parameters");
+    const int nev = (int)prm[SMCMC_ES_H_NEVENTS], nbins = (int)prm[SMCMC_ES_H_NBINS], nsig = (int)prm[SMCMC_ES_H_NSIGNAL];
+    const double xmin = prm[SMCMC_ES_H_XMIN], xmax = prm[SMCMC_ES_H_XMAX], range = prm[SMCMC_ES_H_RANGE];
+    const double cut = prm[SMCMC_ES_H_CUT];
+    double pt[SMCMC_ES_DIM];
+#pragma unroll
+    for (int i = 0; i < SMCMC_ES_DIM; ++i) pt[i] = p[i];
+    smcmc_es_scalars s;
+    smcmc_et_point_scalars(pt, prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF], prm[SMCMC_ES_H_TAN_FAKES],
+                           prm[SMCMC_ES_H_TAN_EFF], &s);
+    const int rows = 3 * nbins;                 // row `rows`: the dropped events'
+    double* const col = hist + lane;
+    const cptr_f64 ev = prm + SMCMC_ES_HEADER + rows;
+    double wb = 0.0;
+#pragma nounroll
+    for (int c = 0; c < 2; ++c) {               // (one copy of the fill's code)
+        for (int r = 0; r <= rows; ++r) col[r * kWave] = 0.0;
+        event_template_fill(col, ev, c ? nsig : 0, c ? nev : nsig, s, nbins, rows, xmin, xmax, range, cut);
+        const double norm = smcmc_et_norm(c ? pt[1] : pt[0], event_template_integral(col, nbins));
+        if (c == 0)
+            for (int r = 0; r < rows; ++r) park[(size_t)r * npad] = smcmc_et_mc_signal(norm, col[r * kWave]);
+        else wb = norm;
+    }
+    // example2/FakeLikelihood.H:64-89: the bins of Close, Separated, DecayTag, in that order
+    const cptr_f64 data = prm + SMCMC_ES_HEADER;
+    double logl = 0.0;
+    for (int r = 0; r < rows; ++r)
+        logl += smcmc_es_bin_term(data[r], smcmc_et_mc(park[(size_t)r * npad], wb, col[r * kWave]));
+    return smcmc_et_penalties(logl, pt);
+}
+
 // SPECIAL = the variant that also knows uniform per-dimension proposals, the scan of one dimension
 // (TSimpleMCMC.H:685-716) and the read-back of the proposed point (:514); kept out of the common kernels, whose
 // register allocation it disturbs.
@@ -580,7 +666,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
 
     // SMCMC_LIKE_EVENT_SAMPLE: the lanes' histograms, hist[bin][lane] (event_sample_loglike), in dynamic LDS
     double* es_hist = nullptr;
-    if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE) {
+    if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE || LIKE == SMCMC_LIKE_EVENT_TEMPLATE) {
         extern __shared__ __attribute__((aligned(16))) double es_dynamic[];
         es_hist = es_dynamic;
     }
@@ -839,6 +925,8 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
             if (dense) logl_prop = loglike_quadform_lds<DP, EXACT, XL>(xcol, likep + p.zero * (s + 1));
         }
         else if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE) logl_prop = event_sample_loglike<DP>(xp, likep + p.zero * (s + 1), es_hist, lane);
+        else if constexpr (LIKE == SMCMC_LIKE_EVENT_TEMPLATE)
+            logl_prop = event_template_loglike<DP>(xp, likep + p.zero * (s + 1), es_hist, lane, p.like_park + chain, NP);
         else if constexpr (!RMS_AHEAD) logl_prop = loglike<DP, LIKE, EXACT>(xp, likep + p.zero * (s + 1), D);
         if constexpr (!RMS_AHEAD) SMCMC_PROF_MARK(PROF_LIKE);
         bool take;
@@ -1339,9 +1427,12 @@ inline hipError_t launch_step(const StepParams& p, int like, bool exact, bool fu
         case SMCMC_LIKE_CONSTRAINED:
             if constexpr (DP == 31 || DP == 63) return launch_step_like<DP, SMCMC_LIKE_CONSTRAINED>(p, exact, fullu, moments, special, stream);
             else return hipErrorInvalidValue;
-        // the event sample is built for the family of its nine dimensions only (kEsDP)
+        // the event sample and the event template are built for the family of their nine dimensions only (kEsDP)
         case SMCMC_LIKE_EVENT_SAMPLE:
             if constexpr (DP == kEsDP) return launch_step_like<DP, SMCMC_LIKE_EVENT_SAMPLE>(p, exact, fullu, moments, special, stream);
+            else return hipErrorInvalidValue;
+        case SMCMC_LIKE_EVENT_TEMPLATE:
+            if constexpr (DP == kEsDP) return launch_step_like<DP, SMCMC_LIKE_EVENT_TEMPLATE>(p, exact, fullu, moments, special, stream);
             else return hipErrorInvalidValue;
 #ifdef SMCMC_USER_LIKELIHOOD
         case SMCMC_LIKE_USER: return launch_step_like<DP, SMCMC_LIKE_USER>(p, exact, fullu, moments, special, stream);

@@ -116,28 +116,13 @@ __device__ __forceinline__ void pw_event_sample_scan(const int* post_bin, const 
         for (int r = 0; r < N; ++r) own[r] = (d == kWave * r) ? own[r] + wk : own[r];
     }
 }
-__device__ __forceinline__ double pw_event_sample(const double* p, const double* __restrict__ like) {
-    __shared__ int post_bin[kWave];
-    __shared__ __attribute__((aligned(16))) double post_w[kWave];
-    __shared__ __attribute__((aligned(16))) double term[kEsOwn * kWave];
-    const int lane = threadIdx.x;
-    const cptr_f64 prm = as_const(like);
-    const int nev = (int)prm[SMCMC_ES_H_NEVENTS], nbins = (int)prm[SMCMC_ES_H_NBINS];
-    const double xmin = prm[SMCMC_ES_H_XMIN], xmax = prm[SMCMC_ES_H_XMAX], range = prm[SMCMC_ES_H_RANGE];
-    const double cut = prm[SMCMC_ES_H_CUT];
-    double pt[SMCMC_ES_DIM];
-#pragma unroll
-    for (int i = 0; i < SMCMC_ES_DIM; ++i) pt[i] = p[i];
-    smcmc_es_scalars s;
-    smcmc_es_point_scalars(pt, prm[SMCMC_ES_H_EXPOSURE], prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF],
-                           prm[SMCMC_ES_H_TAN_FAKES], prm[SMCMC_ES_H_TAN_EFF], &s);
-    const int rows = 3 * nbins;
-    const int nown = (rows + kWave - 1) / kWave;        // registers of `own` in use (wave-uniform)
-    double own[kEsOwn];
-#pragma unroll
-    for (int r = 0; r < kEsOwn; ++r) own[r] = 0.0;
-    const double* const ev = like + SMCMC_ES_HEADER + rows;
-    for (int e0 = 0; e0 < nev; e0 += kWave) {
+// the deal-events / own-bins scan over the events [ebeg, nev) of `ev`, batches of 64 counted from ebeg; nown: the
+// registers of `own` in use (wave-uniform)
+__device__ __forceinline__ void pw_event_sample_range(const double* const ev, const int ebeg, const int nev, const smcmc_es_scalars& s,
+                                                      const int nbins, const int nown, const double xmin, const double xmax,
+                                                      const double range, const double cut, int* post_bin, double* post_w,
+                                                      const int lane, double (&own)[kEsOwn]) {
+    for (int e0 = ebeg; e0 < nev; e0 += kWave) {
         const int e = e0 + lane;
         int b = -1;
         double w = 0.0;
@@ -160,14 +145,9 @@ __device__ __forceinline__ double pw_event_sample(const double* p, const double*
             default: pw_event_sample_scan<kEsOwn>(post_bin, post_w, lane, own); break;
         }
     }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < kEsOwn; ++r) {
-        const int k = lane + kWave * r;
-        term[k] = (k < rows) ? smcmc_es_bin_term(like[SMCMC_ES_HEADER + k], own[r]) : 0.0;
-    }
-    __syncthreads();
-    // FakeLikelihood.H:53-78: the bins of Close, Separated, DecayTag, in that order
+}
+// the bin terms in `term` (entries from rows on +0) added in bin order, by every lane alike
+__device__ __forceinline__ double pw_event_sample_sum(const double* term, int rows) {
     double logl = 0.0;
     for (int k0 = 0; k0 < rows; k0 += kPwBatch) {
         double t[kPwBatch];
@@ -178,6 +158,110 @@ __device__ __forceinline__ double pw_event_sample(const double* p, const double*
             if (k0 + u < rows) logl += t[u];
     }
     return logl;
+}
+__device__ __forceinline__ double pw_event_sample(const double* p, const double* __restrict__ like) {
+    __shared__ int post_bin[kWave];
+    __shared__ __attribute__((aligned(16))) double post_w[kWave];
+    __shared__ __attribute__((aligned(16))) double term[kEsOwn * kWave];
+    const int lane = threadIdx.x;
+    const cptr_f64 prm = as_const(like);
+    const int nev = (int)prm[SMCMC_ES_H_NEVENTS], nbins = (int)prm[SMCMC_ES_H_NBINS];
+    const double xmin = prm[SMCMC_ES_H_XMIN], xmax = prm[SMCMC_ES_H_XMAX], range = prm[SMCMC_ES_H_RANGE];
+    const double cut = prm[SMCMC_ES_H_CUT];
+    double pt[SMCMC_ES_DIM];
+#pragma unroll
+    for (int i = 0; i < SMCMC_ES_DIM; ++i) pt[i] = p[i];
+    smcmc_es_scalars s;
+    smcmc_es_point_scalars(pt, prm[SMCMC_ES_H_EXPOSURE], prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF],
+                           prm[SMCMC_ES_H_TAN_FAKES], prm[SMCMC_ES_H_TAN_EFF], &s);
+    const int rows = 3 * nbins;
+    const int nown = (rows + kWave - 1) / kWave;        // registers of `own` in use (wave-uniform)
+    double own[kEsOwn];
+#pragma unroll
+    for (int r = 0; r < kEsOwn; ++r) own[r] = 0.0;
+    const double* const ev = like + SMCMC_ES_HEADER + rows;
+    pw_event_sample_range(ev, 0, nev, s, nbins, nown, xmin, xmax, range, cut, post_bin, post_w, lane, own);
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < kEsOwn; ++r) {
+        const int k = lane + kWave * r;
+        term[k] = (k < rows) ? smcmc_es_bin_term(like[SMCMC_ES_HEADER + k], own[r]) : 0.0;
+    }
+    __syncthreads();
+    // FakeLikelihood.H:53-78: the bins of Close, Separated, DecayTag, in that order
+    return pw_event_sample_sum(term, rows);
+}
+
+// SMCMC_LIKE_EVENT_TEMPLATE for one chain on 64 lanes: the scan above over the signal events, the owners' bins published
+// to `term` and summed by every lane alike to the class integral (three histograms, each over its bins ascending from +0,
+// then smcmc_et_integral's order); the owners keep ws * own[r] in kEsOwn registers more and start again from +0 over the
+// background events.  `hist`: the owners' bins in `term` (entries from 3 nbins on +0).
+__device__ __forceinline__ double pw_event_template_integral(const double* term, int nbins) {
+    double sum[3];
+    for (int h = 0; h < 3; ++h) {
+        const double* th = term + h * nbins;
+        double v = 0.0;
+        for (int b0 = 0; b0 < nbins; b0 += kPwBatch) {
+            double t[kPwBatch];
+#pragma unroll
+            for (int u = 0; u < kPwBatch; ++u) t[u] = th[b0 + u];      // (below 3 nbins + kPwBatch <= kEsOwn * 64: in range)
+#pragma unroll
+            for (int u = 0; u < kPwBatch; ++u)
+                if (b0 + u < nbins) v += t[u];
+        }
+        sum[h] = v;
+    }
+    return smcmc_et_integral(sum[0], sum[1], sum[2]);
+}
+__device__ __forceinline__ double pw_event_template(const double* p, const double* __restrict__ like) {
+    __shared__ int post_bin[kWave];
+    __shared__ __attribute__((aligned(16))) double post_w[kWave];
+    __shared__ __attribute__((aligned(16))) double term[kEsOwn * kWave];
+    const int lane = threadIdx.x;
+    const cptr_f64 prm = as_const(like);
+    const int nev = (int)prm[SMCMC_ES_H_NEVENTS], nbins = (int)prm[SMCMC_ES_H_NBINS], nsig = (int)prm[SMCMC_ES_H_NSIGNAL];
+    const double xmin = prm[SMCMC_ES_H_XMIN], xmax = prm[SMCMC_ES_H_XMAX], range = prm[SMCMC_ES_H_RANGE];
+    const double cut = prm[SMCMC_ES_H_CUT];
+    double pt[SMCMC_ES_DIM];
+#pragma unroll
+    for (int i = 0; i < SMCMC_ES_DIM; ++i) pt[i] = p[i];
+    smcmc_es_scalars s;
+    smcmc_et_point_scalars(pt, prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF], prm[SMCMC_ES_H_TAN_FAKES],
+                           prm[SMCMC_ES_H_TAN_EFF], &s);
+    const int rows = 3 * nbins;
+    const int nown = (rows + kWave - 1) / kWave;        // registers of `own` in use (wave-uniform)
+    const double* const ev = like + SMCMC_ES_HEADER + rows;
+    double own[kEsOwn], share[kEsOwn];
+    double wb = 0.0;
+#pragma nounroll
+    for (int c = 0; c < 2; ++c) {                       // (one copy of the scan's code)
+#pragma unroll
+        for (int r = 0; r < kEsOwn; ++r) own[r] = 0.0;
+        pw_event_sample_range(ev, c ? nsig : 0, c ? nev : nsig, s, nbins, nown, xmin, xmax, range, cut, post_bin, post_w, lane, own);
+        __syncthreads();                                // (every lane is done with the integral before)
+#pragma unroll
+        for (int r = 0; r < kEsOwn; ++r) {
+            const int k = lane + kWave * r;
+            term[k] = (k < rows) ? own[r] : 0.0;
+        }
+        __syncthreads();
+        const double norm = smcmc_et_norm(c ? pt[1] : pt[0], pw_event_template_integral(term, nbins));
+        if (c == 0) {
+#pragma unroll
+            for (int r = 0; r < kEsOwn; ++r) share[r] = smcmc_et_mc_signal(norm, own[r]);
+        } else {
+            wb = norm;
+        }
+    }
+    __syncthreads();                                    // the background's integral is read
+#pragma unroll
+    for (int r = 0; r < kEsOwn; ++r) {
+        const int k = lane + kWave * r;
+        term[k] = (k < rows) ? smcmc_es_bin_term(like[SMCMC_ES_HEADER + k], smcmc_et_mc(share[r], wb, own[r])) : 0.0;
+    }
+    __syncthreads();
+    // example2/FakeLikelihood.H:64-89: the bins of Close, Separated, DecayTag, in that order; then the penalties
+    return smcmc_et_penalties(pw_event_sample_sum(term, rows), pt);
 }
 
 // log L of the point in LDS (p[0 .. D)), in the reference's summation order: the arithmetic of serial_loglike<LIKE, true>
@@ -227,6 +311,8 @@ __device__ __forceinline__ double pw_loglike(const double* p, double pi, int D, 
         lsum = outside ? -1E+30 : lsum;
     } else if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE) {
         lsum = pw_event_sample(p, like);
+    } else if constexpr (LIKE == SMCMC_LIKE_EVENT_TEMPLATE) {
+        lsum = pw_event_template(p, like);
     } else if constexpr (LIKE == SMCMC_LIKE_CONSTRAINED) {
         // example4/TConstrainedLikelihood.H:26-46; like = {SummedValues, SummedConstraint, Expected[D], Prior[D]}
         double sum = pw_ordered_sum<DMAX>(pi, D, scratch);
@@ -602,7 +688,8 @@ __global__ void __launch_bounds__(kWave) perchain_wave_kernel(const PerChainPara
                 step_rms = __builtin_sqrt(ms);
             }
             PW_MARK(6)
-            if constexpr (LIKE == SMCMC_LIKE_QUADFORM || LIKE == SMCMC_LIKE_USER || LIKE == SMCMC_LIKE_EVENT_SAMPLE) {
+            if constexpr (LIKE == SMCMC_LIKE_QUADFORM || LIKE == SMCMC_LIKE_USER || LIKE == SMCMC_LIKE_EVENT_SAMPLE ||
+                          LIKE == SMCMC_LIKE_EVENT_TEMPLATE) {
                 __syncthreads();
                 ps[lane] = mine ? xpi : 0.0;
                 __syncthreads();
@@ -711,7 +798,7 @@ inline bool perchain_wave_serves(int like) {
 #endif
     return like == SMCMC_LIKE_ISO_GAUSS || like == SMCMC_LIKE_QUADFORM || like == SMCMC_LIKE_ROSENBROCK ||
            like == SMCMC_LIKE_ASYM || like == SMCMC_LIKE_HORRIFIC || like == SMCMC_LIKE_CONSTRAINED ||
-           like == SMCMC_LIKE_EVENT_SAMPLE;
+           like == SMCMC_LIKE_EVENT_SAMPLE || like == SMCMC_LIKE_EVENT_TEMPLATE;
 }
 
 hipError_t launch_perchain_wave(const PerChainParams& p, const PerChainRecord& rec, int like, hipStream_t stream);

@@ -38,6 +38,9 @@ hipError_t launch_perchain_wave(const PerChainParams& p, const PerChainRecord& r
         case SMCMC_LIKE_EVENT_SAMPLE:     // dim = 9: the smallest class of covariance registers, paired or not
             if (p.dim != SMCMC_ES_DIM) return hipErrorInvalidValue;
             return (p.nchains > 1024) ? go_wave<SMCMC_LIKE_EVENT_SAMPLE, 4, true>(p, rec, s) : go_wave<SMCMC_LIKE_EVENT_SAMPLE, 4>(p, rec, s);
+        case SMCMC_LIKE_EVENT_TEMPLATE:
+            if (p.dim != SMCMC_ES_DIM) return hipErrorInvalidValue;
+            return (p.nchains > 1024) ? go_wave<SMCMC_LIKE_EVENT_TEMPLATE, 4, true>(p, rec, s) : go_wave<SMCMC_LIKE_EVENT_TEMPLATE, 4>(p, rec, s);
 #ifdef SMCMC_USER_LIKELIHOOD
         case SMCMC_LIKE_USER: return go_wave_like<SMCMC_LIKE_USER>(p, rec, s);
 #endif

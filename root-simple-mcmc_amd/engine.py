@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (LIKE_ASYM, LIKE_CONSTRAINED, LIKE_EVENT_SAMPLE, LIKE_HORRIFIC, LIKE_ISO_GAUSS, LIKE_QUADFORM, LIKE_ROSENBROCK, LIKE_USER, MODE_FROZEN, MODE_PER_CHAIN, MODE_POOLED, P,  # noqa: F401
+from ._capi import (LIKE_ASYM, LIKE_CONSTRAINED, LIKE_EVENT_SAMPLE, LIKE_EVENT_TEMPLATE, LIKE_HORRIFIC, LIKE_ISO_GAUSS, LIKE_QUADFORM, LIKE_ROSENBROCK, LIKE_USER, MODE_FROZEN, MODE_PER_CHAIN, MODE_POOLED, P,  # noqa: F401
                     SmcmcError)
 # the reducers over a saved trace live in trace.py; their names stay importable from here
 from .trace import (Autocorrelation, AutocorrelationGrid, AutocorrelationPlan, Convergence, MacroAutocorrelation, Marginals,  # noqa: F401
@@ -79,6 +79,15 @@ class Engine(TraceReducers):
         if self.likelihood != LIKE_EVENT_SAMPLE or self._likelihood_params is None:
             raise SmcmcError(_capi.ERR_LOGIC, "EventSampleHistograms needs LIKE_EVENT_SAMPLE and its parameters")
         logl, hist = event_sample_evaluate(self._likelihood_params, point, histograms=True)
+        return hist, logl
+
+    def EventTemplateHistograms(self, point):
+        """LIKE_EVENT_TEMPLATE: the expectation [3][nbins] (Close, Separated, DecayTag) at `point`, as
+        FakeLikelihood::WriteSimulation (example2/FakeLikelihood.H:201-207) fills it, and the log-likelihood there:
+        (hist, logl).  Evaluated on the host by smcmc_event_template_evaluate, bit for bit what the device sums."""
+        if self.likelihood != LIKE_EVENT_TEMPLATE or self._likelihood_params is None:
+            raise SmcmcError(_capi.ERR_LOGIC, "EventTemplateHistograms needs LIKE_EVENT_TEMPLATE and its parameters")
+        logl, hist = event_template_evaluate(self._likelihood_params, point, histograms=True)
         return hist, logl
 
     def set_stream(self, stream):
@@ -432,6 +441,34 @@ def event_sample_evaluate(params, point, histograms=False):
     if st != _capi.OK:
         raise SmcmcError(st, lib.smcmc_event_sample_last_error().decode() or lib.smcmc_status_string(st).decode())
     return (logl.value, hist) if histograms else logl.value
+
+
+def event_template_evaluate(params, point, histograms=False, parts=False):
+    """smcmc_event_template_evaluate: LIKE_EVENT_TEMPLATE at `point` (9 values) on the host -- never to step a chain.
+    Returns logL; with histograms=True also the expectation mc[3][nbins] before the clamp; with parts=True also a dict of
+    the intermediate stages: S[3][nbins], B[3][nbins] (the signal's and the background's histograms), IS, IB (their
+    integrals), ws, wb (the two normalisations).  The order is (logL, hist, parts), without what was not asked for."""
+    lib = _capi.load()
+    prm = _f64(params).ravel()
+    pt = _f64(point).ravel()
+    if pt.size != 9:
+        raise SmcmcError(_capi.ERR_INVALID, "the event template has nine parameters")
+    nbins = int(prm[1]) if prm.size > 1 and np.isfinite(prm[1]) and 1 <= prm[1] <= _capi.EVENT_SAMPLE_MAX_BINS else 1
+    hist = np.zeros((3, nbins))
+    raw = np.zeros(6 * nbins + 4)
+    logl = C.c_double(0.0)
+    st = lib.smcmc_event_template_evaluate(_ptr(prm), prm.size, _ptr(pt), C.byref(logl), _ptr(hist) if histograms else None,
+                                           _ptr(raw) if parts else None)
+    if st != _capi.OK:
+        raise SmcmcError(st, lib.smcmc_event_sample_last_error().decode() or lib.smcmc_status_string(st).decode())
+    out = [logl.value]
+    if histograms:
+        out.append(hist)
+    if parts:
+        out.append({"S": raw[:3 * nbins].reshape(3, nbins).copy(), "B": raw[3 * nbins:6 * nbins].reshape(3, nbins).copy(),
+                    "IS": float(raw[6 * nbins]), "IB": float(raw[6 * nbins + 1]), "ws": float(raw[6 * nbins + 2]),
+                    "wb": float(raw[6 * nbins + 3])})
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 def event_sample_params(events, data, nbins, xmin, xmax, exposure_ratio=None, separation_cut=100.0, true_fakes=0.05,
