@@ -68,7 +68,12 @@ typedef enum {
      * background event counts, each class of the simulated sample is normalised by its own integral at every evaluation,
      * and penalty terms keep the corner cases in check (the definition follows below, "event template").  dim = 9; served
      * and refused exactly where SMCMC_LIKE_EVENT_SAMPLE is. */
-    SMCMC_LIKE_EVENT_TEMPLATE = 8
+    SMCMC_LIKE_EVENT_TEMPLATE = 8,
+    /* example3/FakeLikelihood.H with TFakeGP.H: the template fit with a fourth histogram (VeryClose) and two shapes of
+     * Gaussian-process control values that re-weight the background and the signal peak event by event, each with its
+     * quadratic-form penalty (the definition follows below, "event shape").  dim = 31; served and refused exactly where
+     * SMCMC_LIKE_EVENT_TEMPLATE is. */
+    SMCMC_LIKE_EVENT_SHAPE = 9
 } smcmc_likelihood;
 
 /* ---- SMCMC_LIKE_EVENT_SAMPLE: the definition ------------------------------------------------------------------
@@ -167,6 +172,70 @@ const char* smcmc_event_sample_last_error(void);
  * smcmc_event_sample_last_error serves this entry point too. */
 int smcmc_event_template_evaluate(const double* params, int count, const double* point, double* logl, double* hist,
                                   double* parts);
+
+/* ---- SMCMC_LIKE_EVENT_SHAPE: the definition -------------------------------------------------------------------
+ * Everything is SMCMC_LIKE_EVENT_TEMPLATE's but what follows.
+ *
+ * The point is p[31], in the order of example3/SystematicCorrection.H:11-26 (not example2's): 0 SignalWeight,
+ * 1 BackgroundWeight, 2 SignalSeparationScale, 3 BackgroundSeparationScale, 4 FakeMuDkProb, 5 MuDkEfficiency, 6 MassScale,
+ * 7 MassWidth, 8 MassSkew, 9 .. 19 BackgroundShape, 20 .. 30 SignalShape.
+ *
+ * The parameter array is 12 + 4 nbins + 121 + 169 + 6 nevents doubles:
+ *   { nevents, nbins, xmin, xmax, cutVeryClose (50), cutClose (100), trueFakes, trueEfficiency,
+ *     bkgLow (0), bkgHigh (500), sigLow (0), sigHigh (250),
+ *     data[4][nbins]      VeryClose, Close, Separated, DecayTag (example3/FakeLikelihood.H:68-102 sums them in this order),
+ *     KB[11][11], KS[13][13]   the two kernel matrices, what TFakeGP::SetKernel / GaussianKernel leave,
+ *     events[nevents][6]  as above }
+ * SMCMC_ERR_INVALID unless the count is exact, 1 <= nbins <= SMCMC_EVENT_SHAPE_MAX_BINS, and SMCMC_LIKE_EVENT_TEMPLATE's
+ * rules hold where they apply (every field finite, Mass, TrueMass, TrueMassSigma > 0, Type >= 0, xmin < xmax, the two
+ * fractions inside (0, 1), an event of either class), cutVeryClose <= cutClose, bkgLow < bkgHigh, sigLow < sigHigh, both
+ * kernels exactly symmetric and the inversion below succeeds on both.
+ *
+ * When the parameters are set, once, on the host: KinvB and KinvS, TMatrixD::Invert (TFakeGP.H:132-136) restated as an LU
+ * decomposition with partial pivoting and a forward and a back substitution per column of the inverse (smcmc::esh_invert;
+ * not pinned against ROOT), on the kernel as given; the centres of the
+ * control bins, centre(i) = low + i * bw + 0.5 * bw with bw = (high - low) / n (TAxis::GetBinCenter), n = 11 over
+ * [bkgLow, bkgHigh] and n = 13 over [sigLow, sigHigh]; and for every event the segment of its class's shape that its
+ * UNCORRECTED Mass x falls on (TH1::Interpolate; not pinned against ROOT, as the bin rule says of itself):
+ *   x <= centre(0): the value is y[0];  x >= centre(n - 1): the value is y[n - 1] -- y[.] itself, never y + 0 * slope;
+ *   otherwise b = int(n * (x - low) / (high - low)), k = b - 1 if x <= centre(b), else k = b, and the value is
+ *   y[k] + (x - centre(k)) * ((y[k + 1] - y[k]) / (centre(k + 1) - centre(k))).
+ *
+ * Once per evaluation: scale = p[6] / 10, width = exp(p[7] / 10), skew = 0.3 erf(p[8] / 10), sepS = exp(p[2] / 10),
+ * sepB = exp(p[3] / 10); cf = atan(tanFakes + p[4] / 10) / M_PI + 0.5 and ce = atan(tanEfficiency + p[5] / 10) / M_PI + 0.5
+ * (example3/SystematicCorrection.H:94-96, 110-112: the parameter divided by ten); the four class weights from cf and ce
+ * as above; the control values yB[i] = p[9 + i] / 10 (i < 11) and yS[0] = yS[12] = 0, yS[i + 1] = p[20 + i] / 10 (i < 11)
+ * (:136-149); the slopes (y[k + 1] - y[k]) / (centre(k + 1) - centre(k)).
+ * Per event: mass, separation and cuts as above; the weight is classWeight * exp(shape(Mass)), one un-fused product, the
+ * signal's shape for Type 0 and the background's for Type > 0 (:98-121).  The event goes to DecayTag if MuDk > 0, else to
+ * VeryClose if separation < cutVeryClose, else to Close if separation < cutClose, else to Separated
+ * (example3/FakeLikelihood.H:268-300).
+ *   1. Eight histograms, S[4][nbins] and B[4][nbins], in the order VeryClose, Close, Separated, DecayTag.
+ *   2. IS = ((sum DecayTagS + sum VeryCloseS) + sum CloseS) + sum SeparatedS (:303-306); ws = p[0] / IS; IB, wb likewise.
+ *   3. mc[h][b] = (0.0 + ws * S[h][b]) + wb * B[h][b].
+ *   4. The bin sum over VeryClose, Close, Separated, DecayTag (:68-102).
+ *   5. The penalties, in this order (:104-134): the two sign penalties on p[0] and p[1]; v = p[3] / 5.0, then p[4] / 1.0,
+ *      then p[5] / 1.0, each logL -= (0.5 * v) * v; logL -= penalty(yB, KinvB); logL -= penalty(yS, KinvS), with
+ *      penalty = sum_i sum_j (y[i] * y[j]) * Kinv(i, j), i outer, j inner, un-fused, from +0 (TFakeGP.H:137-145), over all
+ *      11 and all 13 control values, the signal's fixed zeros included.
+ *
+ * On the host: params / count as above, point[31]; *logl the log-likelihood, hist (may be NULL) mc[4][nbins] before the
+ * clamp, parts (may be NULL) 8 nbins + 6 + 121 + 169 doubles: S[4][nbins], B[4][nbins], IS, IB, ws, wb, penalty(B),
+ * penalty(S), KinvB[121], KinvS[169].  The same bits as the device; it never steps a chain.
+ * smcmc_event_sample_last_error serves this entry point too. */
+#define SMCMC_EVENT_SHAPE_MAX_BINS 59   /* the largest nbins whose 4 nbins + 1 histogram rows and 25 table rows of 64 doubles
+                                         * fit one workgroup's LDS beside the 31-wide step kernel's own (smcmc_kernels.hip.h
+                                         * derives and asserts it) */
+int smcmc_event_shape_evaluate(const double* params, int count, const double* point, double* logl, double* hist,
+                               double* parts);
+/* The two pieces of TFakeGP.H by themselves, for include/TFakeGP_amd.H and for tests; the arithmetic above, the same bits.
+ * smcmc_event_shape_gp_value: TFakeGP::GetValue(x) on n >= 1 control values y over [low, high] (low < high).
+ * smcmc_event_shape_gp_penalty: TFakeGP::GetPenalty for the n x n kernel (row-major, finite, exactly symmetric, n from 1
+ * to 64) and the control values y; inverse (may be NULL) receives the n x n inverse the sum was taken with.
+ * SMCMC_ERR_INVALID, with a message through smcmc_event_sample_last_error, when a rule is broken or the kernel cannot be
+ * inverted. */
+int smcmc_event_shape_gp_value(double low, double high, int n, const double* y, double x, double* value);
+int smcmc_event_shape_gp_penalty(const double* kernel, int n, const double* y, double* penalty, double* inverse);
 
 /* How the proposal covariance adapts over the ensemble. */
 typedef enum {

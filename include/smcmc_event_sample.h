@@ -16,6 +16,8 @@
  * of a bin and the penalties -- is the smcmc_et_* functions below.  For it es_pack partitions the events by class, signal
  * first and otherwise in the caller's order, and writes the number of signal events to the header (SMCMC_ES_H_NSIGNAL): no
  * histogram takes events of both classes, so no sum's order of additions changes.
+ *
+ * SMCMC_LIKE_EVENT_SHAPE (example3/) has a layout and functions of its own, smcmc_event_shape.h, included below.
  */
 #ifndef SMCMC_EVENT_SAMPLE_H_SEEN
 #define SMCMC_EVENT_SAMPLE_H_SEEN
@@ -148,5 +150,7 @@ SMCMC_HD double smcmc_et_penalties(double logl, const double* p) {
     logl -= (0.5 * v) * v;
     return logl;
 }
+
+#include "smcmc_event_shape.h"   /* SMCMC_LIKE_EVENT_SHAPE (example3/): the smcmc_esh_* functions */
 
 #endif

@@ -16,7 +16,9 @@ LIKE_ISO_GAUSS, LIKE_QUADFORM, LIKE_ROSENBROCK, LIKE_USER = 0, 1, 2, 3
 LIKE_ASYM, LIKE_HORRIFIC, LIKE_CONSTRAINED = 4, 5, 6   # the reference's stress targets (smcmc.h)
 LIKE_EVENT_SAMPLE = 7   # example/FakeLikelihood.H: binned Poisson likelihood over a simulated event sample, dim = 9
 LIKE_EVENT_TEMPLATE = 8   # example2/FakeLikelihood.H: the same sample as a template fit of the two event counts, dim = 9
+LIKE_EVENT_SHAPE = 9   # example3/FakeLikelihood.H + TFakeGP.H: the template fit with Gaussian-process shape weights, dim = 31
 EVENT_SAMPLE_MAX_BINS = 97   # SMCMC_EVENT_SAMPLE_MAX_BINS of include/smcmc.h
+EVENT_SHAPE_MAX_BINS = 59   # SMCMC_EVENT_SHAPE_MAX_BINS of include/smcmc.h
 MODE_FROZEN, MODE_POOLED, MODE_PER_CHAIN = 0, 1, 2
 
 PARAMS = ["COVARIANCE_WINDOW", "COVARIANCE_DEWEIGHT", "ACCEPTANCE_WINDOW", "ACCEPTANCE_DEWEIGHT",
@@ -202,6 +204,9 @@ SIGNATURES = {
     "smcmc_event_sample_evaluate": (C.c_int, [_dp, C.c_int, _dp, _dp, _dp]),
     "smcmc_event_sample_last_error": (C.c_char_p, []),
     "smcmc_event_template_evaluate": (C.c_int, [_dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "smcmc_event_shape_evaluate": (C.c_int, [_dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "smcmc_event_shape_gp_value": (C.c_int, [C.c_double, C.c_double, C.c_int, _dp, C.c_double, _dp]),
+    "smcmc_event_shape_gp_penalty": (C.c_int, [_dp, C.c_int, _dp, _dp, _dp]),
     "smcmc_selftest_detmath": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]),
     "smcmc_selftest_mfma": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp]),
     "smcmc_selftest_mfma_strip": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp]),

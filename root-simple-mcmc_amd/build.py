@@ -32,6 +32,8 @@ STRESS_DP = (31, 63)
 EVENT_SAMPLE_LIKELIHOOD = 7       # SMCMC_LIKE_EVENT_SAMPLE: dim = 9, so the one family pick_dp(9) gives (kEsDP of smcmc_kernels.hip.h)
 EVENT_TEMPLATE_LIKELIHOOD = 8     # SMCMC_LIKE_EVENT_TEMPLATE: the same nine dimensions, the same family
 EVENT_SAMPLE_DP = (15,)
+EVENT_SHAPE_LIKELIHOOD = 9        # SMCMC_LIKE_EVENT_SHAPE: dim = 31, the family of that size (kEshDP)
+EVENT_SHAPE_DP = (31,)
 
 
 def dp_list():
@@ -80,6 +82,9 @@ def _units(user_flag=None, name="user"):
     for dp in EVENT_SAMPLE_DP:
         for like in (EVENT_SAMPLE_LIKELIHOOD, EVENT_TEMPLATE_LIKELIHOOD):
             units.append(("smcmc_inst.hip", [f"-DSMCMC_DP={dp}", f"-DSMCMC_LIKE={like}"], f"inst_dp{dp}_l{like}"))
+    for dp in EVENT_SHAPE_DP:
+        units.append(("smcmc_inst.hip", [f"-DSMCMC_DP={dp}", f"-DSMCMC_LIKE={EVENT_SHAPE_LIKELIHOOD}"],
+                      f"inst_dp{dp}_l{EVENT_SHAPE_LIKELIHOOD}"))
     for w in (4, 8):
         units.append(("smcmc_panel_inst.hip", [f"-DSMCMC_PANEL_W={w}"], f"panel_w{w}"))
         if user_flag:   # a user likelihood as an HMC target (finite-difference / covariant gradient)

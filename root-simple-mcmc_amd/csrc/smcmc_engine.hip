@@ -84,8 +84,8 @@ struct smcmc_engine {
     DeviceBuffer<double> d_U;
     DeviceBuffer<double> d_Uop;    // large dimensions, fused order: U^T in matrix-operand order (smcmc_panel_mfma_kernel.hip.h)
     DeviceBuffer<double> d_like;
-    int like_lds_bytes = 0;   // SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE: dynamic LDS of a step launch (the lanes' histograms)
-    DeviceBuffer<double> d_like_park;   // SMCMC_LIKE_EVENT_TEMPLATE: the park image [3 nbins][npad] (event_template_loglike); no chain state
+    int like_lds_bytes = 0;   // SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE / _SHAPE: dynamic LDS of a step launch (the lanes' histograms)
+    DeviceBuffer<double> d_like_park;   // SMCMC_LIKE_EVENT_TEMPLATE / _SHAPE: the park image [3 or 4 nbins][npad] (event_template_loglike); no chain state
     // QUADFORM with a sparse Error matrix: the non-zero entries of Error^T, row by row (quadform_csr); empty = dense only
     DeviceBuffer<int32_t> d_like_rowptr;
     DeviceBuffer<int32_t> d_like_cols;
@@ -369,11 +369,12 @@ int upload_like(smcmc_engine* h) {
         if (!h->exact)
             return fail(h, SMCMC_ERR_UNSUPPORTED, "the event-sample likelihood runs in reference-order arithmetic only (SMCMC_P_EXACT_ARITHMETIC = 1)");
         std::vector<double> packed;
-        const bool tmpl = h->likelihood == SMCMC_LIKE_EVENT_TEMPLATE;
-        smcmc::es_pack(h->like_params.data(), packed, tmpl);       // (the template's events partitioned by class)
-        // the template's park image, [3 nbins][npad], comes with the parameters; all or nothing: a second allocation that
-        // fails leaves the engine with the images and sizes it had
-        const size_t park = tmpl ? (size_t)3 * (size_t)packed[SMCMC_ES_H_NBINS] * (size_t)h->npad : 0;
+        const bool tmpl = h->likelihood == SMCMC_LIKE_EVENT_TEMPLATE, shape = h->likelihood == SMCMC_LIKE_EVENT_SHAPE;
+        if (shape) smcmc::esh_pack(h->like_params.data(), packed);  // (the kernels inverted, the events located on their shapes)
+        else smcmc::es_pack(h->like_params.data(), packed, tmpl);  // (the template's events partitioned by class)
+        // the template's park image, [3 nbins][npad] (the shape's: [4 nbins][npad]), comes with the parameters; all or
+        // nothing: a second allocation that fails leaves the engine with the images and sizes it had
+        const size_t park = (tmpl ? (size_t)3 : shape ? (size_t)4 : (size_t)0) * (size_t)packed[SMCMC_ES_H_NBINS] * (size_t)h->npad;
         if (h->d_like.size() < packed.size() || h->d_like_park.size() < park) {
             HIP_TRY(h, hipStreamSynchronize(h->stream));          // nothing in flight reads the old images
             DeviceBuffer<double> like, image;
@@ -384,7 +385,8 @@ int upload_like(smcmc_engine* h) {
         }
         HIP_TRY(h, hipMemcpyAsync(h->d_like, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        h->like_lds_bytes = smcmc::event_sample_lds_bytes((int)packed[SMCMC_ES_H_NBINS]);
+        h->like_lds_bytes = shape ? smcmc::event_shape_lds_bytes((int)packed[SMCMC_ES_H_NBINS])
+                                  : smcmc::event_sample_lds_bytes((int)packed[SMCMC_ES_H_NBINS]);
         return SMCMC_OK;
     }
     if (stress_likelihood(h->likelihood)) {
@@ -1164,12 +1166,13 @@ int smcmc_create(int dim, int nchains, int likelihood, uint64_t seed, uint32_t c
     if (!out) return SMCMC_ERR_INVALID;
     *out = nullptr;
     if (dim < 1 || nchains < 1) return SMCMC_ERR_INVALID;
-    if (likelihood < SMCMC_LIKE_ISO_GAUSS || likelihood > SMCMC_LIKE_EVENT_TEMPLATE) return SMCMC_ERR_INVALID;
+    if (likelihood < SMCMC_LIKE_ISO_GAUSS || likelihood > SMCMC_LIKE_EVENT_SHAPE) return SMCMC_ERR_INVALID;
 #ifndef SMCMC_USER_LIKELIHOOD
     if (likelihood == SMCMC_LIKE_USER) return SMCMC_ERR_UNSUPPORTED;   // this build carries no user likelihood
 #endif
-    // the event sample has the nine systematic parameters of SystematicCorrection.H:11-22 and no other dimension
-    if (event_likelihood(likelihood) && dim != SMCMC_ES_DIM) return SMCMC_ERR_UNSUPPORTED;
+    // the event sample has the nine systematic parameters of SystematicCorrection.H:11-22 and no other dimension (the
+    // event shape: example3's 31)
+    if (event_likelihood(likelihood) && dim != event_likelihood_dim(likelihood)) return SMCMC_ERR_UNSUPPORTED;
     if (likelihood == SMCMC_LIKE_ROSENBROCK && dim < 2) return SMCMC_ERR_INVALID;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return SMCMC_ERR_NO_DEVICE;

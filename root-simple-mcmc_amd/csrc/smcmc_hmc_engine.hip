@@ -619,7 +619,7 @@ int smcmc_hmc_create(int dim, int nchains, int likelihood, uint64_t seed, uint32
     if (!out) return SMCMC_ERR_INVALID;
     *out = nullptr;
     if (dim < 1 || nchains < 1) return SMCMC_ERR_INVALID;
-    if (likelihood == SMCMC_LIKE_EVENT_SAMPLE || likelihood == SMCMC_LIKE_EVENT_TEMPLATE) return SMCMC_ERR_UNSUPPORTED;   // the Metropolis engine serves the event sample and the event template: it has no gradient and no HMC kernel
+    if (likelihood == SMCMC_LIKE_EVENT_SAMPLE || likelihood == SMCMC_LIKE_EVENT_TEMPLATE || likelihood == SMCMC_LIKE_EVENT_SHAPE) return SMCMC_ERR_UNSUPPORTED;   // the Metropolis engine serves the event sample, the event template and the event shape: it has no gradient and no HMC kernel
     if (likelihood < SMCMC_LIKE_ISO_GAUSS || likelihood > SMCMC_LIKE_CONSTRAINED) return SMCMC_ERR_INVALID;
 #ifndef SMCMC_USER_LIKELIHOOD_ANY_DIM
     // a compiled-in user likelihood is an HMC target when its header has the form that walks a point in device memory

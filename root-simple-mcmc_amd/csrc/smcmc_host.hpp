@@ -97,7 +97,11 @@ constexpr int kDPList[] = {SMCMC_FOR_EACH_DP(SMCMC_DP_ENTRY)};
 constexpr int kNumDP = sizeof(kDPList) / sizeof(kDPList[0]);
 
 // the likelihoods over a simulated event sample (smcmc_event_sample.h): one parameter array, one packed layout
-inline bool event_likelihood(int like) { return like == SMCMC_LIKE_EVENT_SAMPLE || like == SMCMC_LIKE_EVENT_TEMPLATE; }
+inline bool event_likelihood(int like) {
+    return like == SMCMC_LIKE_EVENT_SAMPLE || like == SMCMC_LIKE_EVENT_TEMPLATE || like == SMCMC_LIKE_EVENT_SHAPE;
+}
+// the one dimension an event likelihood has: the nine systematic parameters, or example3's 31
+inline int event_likelihood_dim(int like) { return like == SMCMC_LIKE_EVENT_SHAPE ? SMCMC_ESH_DIM : SMCMC_ES_DIM; }
 
 inline bool stress_likelihood(int like) {
     return like == SMCMC_LIKE_ASYM || like == SMCMC_LIKE_HORRIFIC || like == SMCMC_LIKE_CONSTRAINED;
@@ -154,7 +158,8 @@ int check_like_params(H* h, int like, size_t user_max, const char* user_rule, st
             prm = p;
             break;
         case SMCMC_LIKE_EVENT_SAMPLE:
-        case SMCMC_LIKE_EVENT_TEMPLATE: {
+        case SMCMC_LIKE_EVENT_TEMPLATE:
+        case SMCMC_LIKE_EVENT_SHAPE: {
             // only checked, like QUADFORM's matrix: the engine packs the sample in a layout of its own (es_pack)
             const char* why = es_check_like(like, p.data(), p.size());
             if (why) return fail(h, SMCMC_ERR_INVALID, why);

@@ -23,6 +23,17 @@ static hipError_t go(const StepParams& p, hipStream_t s) {
         hipLaunchKernelGGL(kernel, dim3(p.npad / kWave), dim3(kWave), (size_t)p.like_lds_bytes, s, p);
         return hipGetLastError();
     }
+    if constexpr (LIKE == SMCMC_LIKE_EVENT_SHAPE) {
+        // the lanes' histograms and shape tables in dynamic LDS (event_shape_loglike), and the park image
+        auto kernel = step_kernel<DP, LIKE, EXACT, FULLU, MOM, SPECIAL>;
+        if (p.like_lds_bytes <= 0 || p.like_lds_bytes > event_shape_lds_bytes(SMCMC_EVENT_SHAPE_MAX_BINS) || !p.like_park)
+            return hipErrorInvalidValue;
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 event_shape_lds_bytes(SMCMC_EVENT_SHAPE_MAX_BINS));
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(p.npad / kWave), dim3(kWave), (size_t)p.like_lds_bytes, s, p);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(HIP_KERNEL_NAME(step_kernel<DP, LIKE, EXACT, FULLU, MOM, SPECIAL>), dim3(p.npad / kWave),
                        dim3(kWave), 0, s, p);
     return hipGetLastError();
@@ -32,7 +43,7 @@ template <>
 hipError_t launch_step_like<SMCMC_DP, SMCMC_LIKE>(const StepParams& p, bool exact, bool fullu, bool mom, bool special,
                                                   hipStream_t s) {
     constexpr int DP = SMCMC_DP, LIKE = SMCMC_LIKE;
-#if SMCMC_LIKE == 7 || SMCMC_LIKE == 8   // SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE: reference-order arithmetic only (the engine refuses the fused order)
+#if SMCMC_LIKE == 7 || SMCMC_LIKE == 8 || SMCMC_LIKE == 9   // SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE / _SHAPE: reference-order arithmetic only (the engine refuses the fused order)
     if (!exact) return hipErrorNotSupported;
     if (special) {
         if (fullu) return mom ? go<DP, LIKE, true, true, true, true>(p, s) : go<DP, LIKE, true, true, false, true>(p, s);
@@ -53,7 +64,7 @@ hipError_t launch_step_like<SMCMC_DP, SMCMC_LIKE>(const StepParams& p, bool exac
 #endif
 }
 
-#if (SMCMC_LIKE != 3 || defined(SMCMC_USER_LIKELIHOOD)) && SMCMC_LIKE != 7 && SMCMC_LIKE != 8   // 3 = SMCMC_LIKE_USER; 7, 8 = SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE, which the
+#if (SMCMC_LIKE != 3 || defined(SMCMC_USER_LIKELIHOOD)) && SMCMC_LIKE != 7 && SMCMC_LIKE != 8 && SMCMC_LIKE != 9   // 3 = SMCMC_LIKE_USER; 7, 8, 9 = SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE / _SHAPE, which the
 // variable-at-a-time engine refuses (enumerators, invisible to the preprocessor)
 // the variable-at-a-time chains on the same likelihood code (smcmc_vaat_kernel.hip.h)
 template <>

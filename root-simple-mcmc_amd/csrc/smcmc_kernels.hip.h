@@ -226,8 +226,8 @@ struct StepParams {
     int zero;                  // always 0; makes table addresses depend on the step so that the
                                // compiler does not hoist (and then spill) whole tables out of the loop
     unsigned long long* prof;  // section profile (SMCMC_STEP_PROFILE builds only): [group][kProfSlots][64] cycle sums, added to
-    int like_lds_bytes;        // SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE: dynamic LDS of the launch, the lanes' histograms (event_sample_lds_bytes)
-    double* like_park;         // SMCMC_LIKE_EVENT_TEMPLATE: the park image [3 nbins][npad] (event_template_loglike)
+    int like_lds_bytes;        // SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE / _SHAPE: dynamic LDS of the launch, the lanes' histograms (event_sample_lds_bytes, event_shape_lds_bytes)
+    double* like_park;         // SMCMC_LIKE_EVENT_TEMPLATE / _SHAPE: the park image [3 or 4 nbins][npad] (event_template_loglike)
 };
 
 // ---- Section profile of the step loop: -DSMCMC_STEP_PROFILE=1 (sections) or 2 (sections and every piece) ----
@@ -558,6 +558,132 @@ __device__ __forceinline__ double event_template_loglike(const double (&p)[DP], 
     return smcmc_et_penalties(logl, pt);
 }
 
+// ---- SMCMC_LIKE_EVENT_SHAPE (smcmc.h; the arithmetic is include/smcmc_event_shape.h) ----
+// The event template's two passes and park image, with four histograms per lane -- hist[4 nbins + 1][lane], the park image
+// [4 nbins][npad] -- in the 31-wide family.  An event's weight is its class's weight times exp(shape), and the shape
+// reads the lane's control value y[k] and slope[k] at an index k that the packed event carries: wave-uniform, but known
+// only at run time, so a register array would go to scratch inside the event loop.  The tables sit in the dynamic LDS
+// behind the histograms as table[row][lane]: rows [0, n) the control values, rows [n, 2 n - 1) the slopes of the class
+// whose pass is running -- n = 13 and 25 rows for the signal, n = 11 and 21 rows for the background.
+constexpr int kEshDP = 31;
+constexpr int kEshTableRows = 2 * SMCMC_ESH_NS - 1;
+static_assert(SMCMC_ESH_NS >= SMCMC_ESH_NB, "the signal's tables are the larger");
+// static LDS of step_kernel<kEshDP, ...> at its largest (moment fold, full decomposition): point, decomposition, tables
+constexpr int kEshStaticLds = 8 * (XLayout<kEshDP, true, false>::DOUBLES + ULayout<kEshDP, true>::SIZE + 384) + 64;
+constexpr int event_shape_lds_bytes(int nbins) { return (4 * nbins + 1 + kEshTableRows) * kWave * 8; }
+static_assert(kEshStaticLds + event_shape_lds_bytes(SMCMC_EVENT_SHAPE_MAX_BINS) <= kEsLdsLimit &&
+              kEshStaticLds + event_shape_lds_bytes(SMCMC_EVENT_SHAPE_MAX_BINS + 1) > kEsLdsLimit,
+              "SMCMC_EVENT_SHAPE_MAX_BINS (smcmc.h) is the largest nbins whose histograms and tables fit one workgroup beside the kernel's static LDS");
+static_assert(SMCMC_EVENT_SHAPE_MAX_BINS >= 50, "example3's own 50 bins must fit: shrink the tables, not the histograms");
+// event_template_fill with the weight multiplied by exp(shape).  tab: this lane's column of the tables of the pass's
+// class, nctl its number of control values.
+__device__ __forceinline__ void event_shape_fill(double* const col, const double* const tab, const int nctl, const cptr_f64 ev,
+                                               const int ebeg, const int nev, const smcmc_es_scalars& s, const int nbins,
+                                               const int rows, const double xmin, const double xmax, const double range,
+                                               const double cut_very_close, const double cut_close) {
+    for (int e0 = ebeg; e0 < nev; e0 += kEsBatch) {
+        int idx[kEsBatch];
+        double w[kEsBatch], v[kEsBatch];
+#pragma unroll
+        for (int u = 0; u < kEsBatch; ++u) {
+            const bool in = e0 + u < nev;                                   // (wave-uniform)
+            const cptr_f64 q = ev + (size_t)(in ? e0 + u : nev - 1) * SMCMC_ESH_EVENT;
+            const int cls = (int)q[4];
+            const int k = (int)q[5];                                        // (wave-uniform; 0 <= k < nctl: esh_pack)
+            const int ks = (k < nctl - 1) ? k : nctl - 2;                   // (a clamped event at the last centre has no slope)
+            const int b = smcmc_esh_event_bin(q[0], q[1], q[2], q[3], cls >> 1, cls & 1, &s, nbins, xmin, xmax, range,
+                                              cut_very_close, cut_close);
+            idx[u] = (in && b >= 0) ? b : rows;
+            const double cw = (cls == 0) ? s.weight[0] : (cls == 1) ? s.weight[1] : (cls == 2) ? s.weight[2] : s.weight[3];
+            w[u] = smcmc_esh_weight(cw, smcmc_esh_shape(tab[k * kWave], tab[(nctl + ks) * kWave], q[6], q[7] != 0.0));
+        }
+#pragma unroll
+        for (int u = 0; u < kEsBatch; ++u) v[u] = col[idx[u] * kWave];
+#pragma unroll
+        for (int u = 0; u < kEsBatch; ++u) {
+#pragma unroll
+            for (int j = 0; j < u; ++j) v[u] = (idx[j] == idx[u]) ? v[j] : v[u];
+            v[u] = v[u] + w[u];
+        }
+#pragma unroll
+        for (int u = 0; u < kEsBatch; ++u) col[idx[u] * kWave] = v[u];
+    }
+}
+__device__ __forceinline__ double event_shape_integral(const double* col, int nbins) {
+    double sum[4];
+    for (int k = 0; k < 4; ++k) {
+        const double* h = col + (size_t)k * nbins * kWave;
+        double v = 0.0;
+        for (int b = 0; b < nbins; ++b) v += h[b * kWave];
+        sum[k] = v;
+    }
+    return smcmc_esh_integral(sum[0], sum[1], sum[2], sum[3]);
+}
+// TFakeGP::GetPenalty of N control values in registers, the inverse kernel through the constant address space
+template <int N>
+__device__ __forceinline__ double event_shape_penalty(const double (&y)[N], const cptr_f64 kinv) {
+    double penalty = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) penalty += smcmc_esh_gp_term(y[i], y[j], kinv[i * N + j]);
+    }
+    return penalty;
+}
+// this lane's column of the tables: the control values y and the slopes between the centres c
+template <int N>
+__device__ __forceinline__ void event_shape_tables(double* const tab, const double (&y)[N], const cptr_f64 c) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) tab[i * kWave] = y[i];
+#pragma unroll
+    for (int i = 0; i + 1 < N; ++i) tab[(N + i) * kWave] = smcmc_esh_slope(y[i], y[i + 1], c[i], c[i + 1]);
+}
+// park: this lane's column of the image, rows npad apart
+template <int DP>
+__device__ __forceinline__ double event_shape_loglike(const double (&p)[DP], cptr_f64 prm, double* hist, int lane,
+                                                      double* park, size_t npad) {
+    static_assert(DP >= SMCMC_ESH_DIM, "the 31 parameters of example3");
+    const int nev = (int)prm[SMCMC_ES_H_NEVENTS], nbins = (int)prm[SMCMC_ES_H_NBINS], nsig = (int)prm[SMCMC_ES_H_NSIGNAL];
+    const double xmin = prm[SMCMC_ES_H_XMIN], xmax = prm[SMCMC_ES_H_XMAX], range = prm[SMCMC_ES_H_RANGE];
+    const double cut_close = prm[SMCMC_ES_H_CUT], cut_very_close = prm[SMCMC_ESH_H_CUT_VERY_CLOSE];
+    double pt[SMCMC_ESH_DIM];
+#pragma unroll
+    for (int i = 0; i < SMCMC_ESH_DIM; ++i) pt[i] = p[i];
+    smcmc_es_scalars s;
+    smcmc_esh_point_scalars(pt, prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF], prm[SMCMC_ES_H_TAN_FAKES],
+                            prm[SMCMC_ES_H_TAN_EFF], &s);
+    double yb[SMCMC_ESH_NB], ys[SMCMC_ESH_NS];
+#pragma unroll
+    for (int i = 0; i < SMCMC_ESH_NB; ++i) yb[i] = smcmc_esh_control_b(pt, i);
+#pragma unroll
+    for (int i = 0; i < SMCMC_ESH_NS; ++i) ys[i] = smcmc_esh_control_s(pt, i);
+    const int rows = 4 * nbins;                 // row `rows`: the dropped events'
+    double* const col = hist + lane;
+    double* const tab = col + (size_t)(rows + 1) * kWave;
+    const cptr_f64 ev = prm + SMCMC_ESH_EVENTS(nbins);
+    double wb = 0.0;
+#pragma nounroll
+    for (int c = 0; c < 2; ++c) {               // (one copy of the fill's code)
+        for (int r = 0; r <= rows; ++r) col[r * kWave] = 0.0;
+        if (c == 0) event_shape_tables<SMCMC_ESH_NS>(tab, ys, prm + SMCMC_ESH_CENTRE_S(nbins));
+        else event_shape_tables<SMCMC_ESH_NB>(tab, yb, prm + SMCMC_ESH_CENTRE_B(nbins));
+        event_shape_fill(col, tab, c ? SMCMC_ESH_NB : SMCMC_ESH_NS, ev, c ? nsig : 0, c ? nev : nsig, s, nbins, rows, xmin, xmax,
+                         range, cut_very_close, cut_close);
+        const double norm = smcmc_et_norm(c ? pt[1] : pt[0], event_shape_integral(col, nbins));
+        if (c == 0)
+            for (int r = 0; r < rows; ++r) park[(size_t)r * npad] = smcmc_et_mc_signal(norm, col[r * kWave]);
+        else wb = norm;
+    }
+    // example3/FakeLikelihood.H:68-102: the bins of VeryClose, Close, Separated, DecayTag, in that order
+    const cptr_f64 data = prm + SMCMC_ES_HEADER;
+    double logl = 0.0;
+    for (int r = 0; r < rows; ++r)
+        logl += smcmc_es_bin_term(data[r], smcmc_et_mc(park[(size_t)r * npad], wb, col[r * kWave]));
+    const double pen_b = event_shape_penalty<SMCMC_ESH_NB>(yb, prm + SMCMC_ESH_KINV_B(nbins));
+    const double pen_s = event_shape_penalty<SMCMC_ESH_NS>(ys, prm + SMCMC_ESH_KINV_S(nbins));
+    return smcmc_esh_penalties(logl, pt, pen_b, pen_s);
+}
+
 // SPECIAL = the variant that also knows uniform per-dimension proposals, the scan of one dimension
 // (TSimpleMCMC.H:685-716) and the read-back of the proposed point (:514); kept out of the common kernels, whose
 // register allocation it disturbs.
@@ -666,7 +792,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
 
     // SMCMC_LIKE_EVENT_SAMPLE: the lanes' histograms, hist[bin][lane] (event_sample_loglike), in dynamic LDS
     double* es_hist = nullptr;
-    if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE || LIKE == SMCMC_LIKE_EVENT_TEMPLATE) {
+    if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE || LIKE == SMCMC_LIKE_EVENT_TEMPLATE || LIKE == SMCMC_LIKE_EVENT_SHAPE) {
         extern __shared__ __attribute__((aligned(16))) double es_dynamic[];
         es_hist = es_dynamic;
     }
@@ -927,6 +1053,8 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         else if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE) logl_prop = event_sample_loglike<DP>(xp, likep + p.zero * (s + 1), es_hist, lane);
         else if constexpr (LIKE == SMCMC_LIKE_EVENT_TEMPLATE)
             logl_prop = event_template_loglike<DP>(xp, likep + p.zero * (s + 1), es_hist, lane, p.like_park + chain, NP);
+        else if constexpr (LIKE == SMCMC_LIKE_EVENT_SHAPE)
+            logl_prop = event_shape_loglike<DP>(xp, likep + p.zero * (s + 1), es_hist, lane, p.like_park + chain, NP);
         else if constexpr (!RMS_AHEAD) logl_prop = loglike<DP, LIKE, EXACT>(xp, likep + p.zero * (s + 1), D);
         if constexpr (!RMS_AHEAD) SMCMC_PROF_MARK(PROF_LIKE);
         bool take;
@@ -1433,6 +1561,10 @@ inline hipError_t launch_step(const StepParams& p, int like, bool exact, bool fu
             else return hipErrorInvalidValue;
         case SMCMC_LIKE_EVENT_TEMPLATE:
             if constexpr (DP == kEsDP) return launch_step_like<DP, SMCMC_LIKE_EVENT_TEMPLATE>(p, exact, fullu, moments, special, stream);
+            else return hipErrorInvalidValue;
+        // ... and the event shape for the family of its 31 (kEshDP)
+        case SMCMC_LIKE_EVENT_SHAPE:
+            if constexpr (DP == kEshDP) return launch_step_like<DP, SMCMC_LIKE_EVENT_SHAPE>(p, exact, fullu, moments, special, stream);
             else return hipErrorInvalidValue;
 #ifdef SMCMC_USER_LIKELIHOOD
         case SMCMC_LIKE_USER: return launch_step_like<DP, SMCMC_LIKE_USER>(p, exact, fullu, moments, special, stream);

@@ -264,6 +264,150 @@ __device__ __forceinline__ double pw_event_template(const double* p, const doubl
     return smcmc_et_penalties(pw_event_sample_sum(term, rows), pt);
 }
 
+// SMCMC_LIKE_EVENT_SHAPE (smcmc.h; the arithmetic is include/smcmc_event_shape.h) for one chain on 64 lanes: the event
+// template's two scans over four histograms laid end to end, the owners' bins in kEshOwn registers.  The lane that
+// corrects an event also forms its exp(shape); the segment k differs from lane to lane, so the control values and slopes
+// of both shapes sit in a small LDS table, written once per evaluation from the point in LDS:
+//   [0, 11) yB   [11, 21) slopeB   [21, 34) yS   [34, 46) slopeS
+constexpr int kEshOwn = (4 * SMCMC_EVENT_SHAPE_MAX_BINS + kWave - 1) / kWave;
+static_assert(kEshOwn <= kEsOwn, "pw_event_sample_scan takes the owners' registers as an array of kEsOwn");
+static_assert(kEshOwn * kWave >= 4 * SMCMC_EVENT_SHAPE_MAX_BINS + kPwBatch, "the last batch of the bin sum reads inside `term`");
+constexpr int kEshTabB = 0, kEshTabS = 2 * SMCMC_ESH_NB - 1, kEshTab = 2 * SMCMC_ESH_NB - 1 + 2 * SMCMC_ESH_NS - 1;
+// pw_event_sample_range with the weight multiplied by exp(shape); y: the control values of the pass's class in LDS,
+// nctl of them, and behind them the nctl - 1 slopes
+__device__ __forceinline__ void pw_event_shape_range(const double* const ev, const int ebeg, const int nev, const smcmc_es_scalars& s,
+                                                     const int nbins, const int nown, const double xmin, const double xmax,
+                                                     const double range, const double cut_very_close, const double cut_close,
+                                                     const double* y, const int nctl, int* post_bin, double* post_w,
+                                                     const int lane, double (&own)[kEsOwn]) {
+    for (int e0 = ebeg; e0 < nev; e0 += kWave) {
+        const int e = e0 + lane;
+        int b = -1;
+        double w = 0.0;
+        if (e < nev) {
+            const double* q = ev + (size_t)e * SMCMC_ESH_EVENT;
+            const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], dx = q[6];
+            const int cls = (int)q[4];
+            int k = (int)q[5];
+            k = (k < 0) ? 0 : (k > nctl - 1) ? nctl - 1 : k;            // (esh_pack's range; the table is not read outside it)
+            const int ks = (k < nctl - 1) ? k : nctl - 2;               // (a clamped event at the last centre has no slope)
+            const bool clamped = q[7] != 0.0;
+            b = smcmc_esh_event_bin(q0, q1, q2, q3, cls >> 1, cls & 1, &s, nbins, xmin, xmax, range, cut_very_close, cut_close);
+            const double cw = (cls == 0) ? s.weight[0] : (cls == 1) ? s.weight[1] : (cls == 2) ? s.weight[2] : s.weight[3];
+            w = smcmc_esh_weight(cw, smcmc_esh_shape(y[k], y[nctl + ks], dx, clamped));
+        }
+        __syncthreads();                                // the scan of the batch before is over
+        post_bin[lane] = b;
+        post_w[lane] = w;
+        __syncthreads();
+        switch (nown) {
+            case 1: pw_event_sample_scan<1>(post_bin, post_w, lane, own); break;
+            case 2: pw_event_sample_scan<(kEshOwn < 2 ? kEshOwn : 2)>(post_bin, post_w, lane, own); break;
+            case 3: pw_event_sample_scan<(kEshOwn < 3 ? kEshOwn : 3)>(post_bin, post_w, lane, own); break;
+            default: pw_event_sample_scan<kEshOwn>(post_bin, post_w, lane, own); break;     // (50 bins: 200 rows)
+        }
+    }
+}
+// `hist`: the owners' bins in `term` (entries from 4 nbins on +0)
+__device__ __forceinline__ double pw_event_shape_integral(const double* term, int nbins) {
+    double sum[4];
+    for (int h = 0; h < 4; ++h) {
+        const double* th = term + h * nbins;
+        double v = 0.0;
+        for (int b0 = 0; b0 < nbins; b0 += kPwBatch) {
+            double t[kPwBatch];
+#pragma unroll
+            for (int u = 0; u < kPwBatch; ++u) t[u] = th[b0 + u];      // (below 4 nbins + kPwBatch <= kEshOwn * 64: in range)
+#pragma unroll
+            for (int u = 0; u < kPwBatch; ++u)
+                if (b0 + u < nbins) v += t[u];
+        }
+        sum[h] = v;
+    }
+    return smcmc_esh_integral(sum[0], sum[1], sum[2], sum[3]);
+}
+// TFakeGP::GetPenalty of the n control values y in LDS, by every lane alike
+__device__ __forceinline__ double pw_event_shape_penalty(const double* y, const cptr_f64 kinv, int n) {
+    double penalty = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const double yi = y[i];
+        for (int j = 0; j < n; ++j) penalty += smcmc_esh_gp_term(yi, y[j], kinv[i * n + j]);
+    }
+    return penalty;
+}
+__device__ __forceinline__ double pw_event_shape(const double* p, const double* __restrict__ like) {
+    __shared__ int post_bin[kWave];
+    __shared__ __attribute__((aligned(16))) double post_w[kWave];
+    __shared__ __attribute__((aligned(16))) double term[kEshOwn * kWave];
+    __shared__ __attribute__((aligned(16))) double tab[kWave];      // (kEshTab = 46 entries in use)
+    static_assert(kEshTab <= kWave, "a lane an entry");
+    const int lane = threadIdx.x;
+    const cptr_f64 prm = as_const(like);
+    const int nev = (int)prm[SMCMC_ES_H_NEVENTS], nbins = (int)prm[SMCMC_ES_H_NBINS], nsig = (int)prm[SMCMC_ES_H_NSIGNAL];
+    const double xmin = prm[SMCMC_ES_H_XMIN], xmax = prm[SMCMC_ES_H_XMAX], range = prm[SMCMC_ES_H_RANGE];
+    const double cut_close = prm[SMCMC_ES_H_CUT], cut_very_close = prm[SMCMC_ESH_H_CUT_VERY_CLOSE];
+    double pt[SMCMC_ESH_DIM];
+#pragma unroll
+    for (int i = 0; i < SMCMC_ESH_DIM; ++i) pt[i] = p[i];
+    smcmc_es_scalars s;
+    smcmc_esh_point_scalars(pt, prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF], prm[SMCMC_ES_H_TAN_FAKES],
+                            prm[SMCMC_ES_H_TAN_EFF], &s);
+    // the tables: lane l forms entry l (a control value, or a slope from the two control values beside it)
+    {
+        const bool sig = lane >= kEshTabS;
+        const int l = sig ? lane - kEshTabS : lane;
+        const int n = sig ? SMCMC_ESH_NS : SMCMC_ESH_NB;
+        const bool is_slope = l >= n;
+        const int i = is_slope ? l - n : l;                             // the control value, or the segment
+        const int i0 = (i < n - 1) ? i : n - 1, i1 = (i + 1 < n) ? i + 1 : n - 1;      // (in range for the idle lanes too)
+        const double y0 = sig ? smcmc_esh_control_s(p, i0) : smcmc_esh_control_b(p, i0);
+        const double y1 = sig ? smcmc_esh_control_s(p, i1) : smcmc_esh_control_b(p, i1);
+        const double* c = like + (sig ? SMCMC_ESH_CENTRE_S(nbins) : SMCMC_ESH_CENTRE_B(nbins));
+        const double v = is_slope ? smcmc_esh_slope(y0, y1, c[i0], c[i1]) : y0;
+        __syncthreads();                                // (every lane is done with the tables of the evaluation before)
+        tab[lane] = (lane < kEshTab) ? v : 0.0;
+        __syncthreads();
+    }
+    const int rows = 4 * nbins;
+    const int nown = (rows + kWave - 1) / kWave;        // registers of `own` in use (wave-uniform)
+    const double* const ev = like + SMCMC_ESH_EVENTS(nbins);
+    double own[kEsOwn], share[kEshOwn];
+    double wb = 0.0;
+#pragma nounroll
+    for (int c = 0; c < 2; ++c) {                       // (one copy of the scan's code)
+#pragma unroll
+        for (int r = 0; r < kEsOwn; ++r) own[r] = 0.0;
+        pw_event_shape_range(ev, c ? nsig : 0, c ? nev : nsig, s, nbins, nown, xmin, xmax, range, cut_very_close, cut_close,
+                             tab + (c ? kEshTabB : kEshTabS), c ? SMCMC_ESH_NB : SMCMC_ESH_NS, post_bin, post_w, lane, own);
+        __syncthreads();                                // (every lane is done with the integral before)
+#pragma unroll
+        for (int r = 0; r < kEshOwn; ++r) {
+            const int k = lane + kWave * r;
+            term[k] = (k < rows) ? own[r] : 0.0;
+        }
+        __syncthreads();
+        const double norm = smcmc_et_norm(c ? pt[1] : pt[0], pw_event_shape_integral(term, nbins));
+        if (c == 0) {
+#pragma unroll
+            for (int r = 0; r < kEshOwn; ++r) share[r] = smcmc_et_mc_signal(norm, own[r]);
+        } else {
+            wb = norm;
+        }
+    }
+    __syncthreads();                                    // the background's integral is read
+#pragma unroll
+    for (int r = 0; r < kEshOwn; ++r) {
+        const int k = lane + kWave * r;
+        term[k] = (k < rows) ? smcmc_es_bin_term(like[SMCMC_ES_HEADER + k], smcmc_et_mc(share[r], wb, own[r])) : 0.0;
+    }
+    __syncthreads();
+    // example3/FakeLikelihood.H:68-102: the bins of VeryClose, Close, Separated, DecayTag, in that order; then the penalties
+    const double logl = pw_event_sample_sum(term, rows);
+    const double pen_b = pw_event_shape_penalty(tab + kEshTabB, prm + SMCMC_ESH_KINV_B(nbins), SMCMC_ESH_NB);
+    const double pen_s = pw_event_shape_penalty(tab + kEshTabS, prm + SMCMC_ESH_KINV_S(nbins), SMCMC_ESH_NS);
+    return smcmc_esh_penalties(logl, pt, pen_b, pen_s);
+}
+
 // log L of the point in LDS (p[0 .. D)), in the reference's summation order: the arithmetic of serial_loglike<LIKE, true>
 // (pi: this lane's coordinate of the same point)
 template <int LIKE, int DMAX>
@@ -313,6 +457,8 @@ __device__ __forceinline__ double pw_loglike(const double* p, double pi, int D, 
         lsum = pw_event_sample(p, like);
     } else if constexpr (LIKE == SMCMC_LIKE_EVENT_TEMPLATE) {
         lsum = pw_event_template(p, like);
+    } else if constexpr (LIKE == SMCMC_LIKE_EVENT_SHAPE) {
+        lsum = pw_event_shape(p, like);
     } else if constexpr (LIKE == SMCMC_LIKE_CONSTRAINED) {
         // example4/TConstrainedLikelihood.H:26-46; like = {SummedValues, SummedConstraint, Expected[D], Prior[D]}
         double sum = pw_ordered_sum<DMAX>(pi, D, scratch);
@@ -689,7 +835,7 @@ __global__ void __launch_bounds__(kWave) perchain_wave_kernel(const PerChainPara
             }
             PW_MARK(6)
             if constexpr (LIKE == SMCMC_LIKE_QUADFORM || LIKE == SMCMC_LIKE_USER || LIKE == SMCMC_LIKE_EVENT_SAMPLE ||
-                          LIKE == SMCMC_LIKE_EVENT_TEMPLATE) {
+                          LIKE == SMCMC_LIKE_EVENT_TEMPLATE || LIKE == SMCMC_LIKE_EVENT_SHAPE) {
                 __syncthreads();
                 ps[lane] = mine ? xpi : 0.0;
                 __syncthreads();
@@ -798,7 +944,7 @@ inline bool perchain_wave_serves(int like) {
 #endif
     return like == SMCMC_LIKE_ISO_GAUSS || like == SMCMC_LIKE_QUADFORM || like == SMCMC_LIKE_ROSENBROCK ||
            like == SMCMC_LIKE_ASYM || like == SMCMC_LIKE_HORRIFIC || like == SMCMC_LIKE_CONSTRAINED ||
-           like == SMCMC_LIKE_EVENT_SAMPLE || like == SMCMC_LIKE_EVENT_TEMPLATE;
+           like == SMCMC_LIKE_EVENT_SAMPLE || like == SMCMC_LIKE_EVENT_TEMPLATE || like == SMCMC_LIKE_EVENT_SHAPE;
 }
 
 hipError_t launch_perchain_wave(const PerChainParams& p, const PerChainRecord& rec, int like, hipStream_t stream);

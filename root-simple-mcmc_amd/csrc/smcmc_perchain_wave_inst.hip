@@ -41,6 +41,11 @@ hipError_t launch_perchain_wave(const PerChainParams& p, const PerChainRecord& r
         case SMCMC_LIKE_EVENT_TEMPLATE:
             if (p.dim != SMCMC_ES_DIM) return hipErrorInvalidValue;
             return (p.nchains > 1024) ? go_wave<SMCMC_LIKE_EVENT_TEMPLATE, 4, true>(p, rec, s) : go_wave<SMCMC_LIKE_EVENT_TEMPLATE, 4>(p, rec, s);
+        case SMCMC_LIKE_EVENT_SHAPE:      // dim = 31: twelve covariance registers, which have no paired form
+            if (p.dim != SMCMC_ESH_DIM) return hipErrorInvalidValue;
+            static_assert(SMCMC_ESH_DIM * (SMCMC_ESH_DIM + 1) / 2 > 4 * kWave && SMCMC_ESH_DIM * (SMCMC_ESH_DIM + 1) / 2 <= 12 * kWave,
+                          "perchain_wave_elements(31) is 12");
+            return go_wave<SMCMC_LIKE_EVENT_SHAPE, 12>(p, rec, s);
 #ifdef SMCMC_USER_LIKELIHOOD
         case SMCMC_LIKE_USER: return go_wave_like<SMCMC_LIKE_USER>(p, rec, s);
 #endif

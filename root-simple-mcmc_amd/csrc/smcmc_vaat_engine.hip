@@ -140,7 +140,7 @@ int smcmc_vaat_create(int dim, int nchains, int likelihood, uint64_t seed, uint3
     if (!out) return SMCMC_ERR_INVALID;
     *out = nullptr;
     if (dim < 1 || nchains < 1) return SMCMC_ERR_INVALID;
-    if (likelihood == SMCMC_LIKE_EVENT_SAMPLE || likelihood == SMCMC_LIKE_EVENT_TEMPLATE) return SMCMC_ERR_UNSUPPORTED;   // the Metropolis engine serves the event sample and the event template: no variable-at-a-time kernel is built for it
+    if (likelihood == SMCMC_LIKE_EVENT_SAMPLE || likelihood == SMCMC_LIKE_EVENT_TEMPLATE || likelihood == SMCMC_LIKE_EVENT_SHAPE) return SMCMC_ERR_UNSUPPORTED;   // the Metropolis engine serves the event sample, the event template and the event shape: no variable-at-a-time kernel is built for it
     if (likelihood < SMCMC_LIKE_ISO_GAUSS || likelihood > SMCMC_LIKE_CONSTRAINED) return SMCMC_ERR_INVALID;
 #ifndef SMCMC_USER_LIKELIHOOD
     if (likelihood == SMCMC_LIKE_USER) return SMCMC_ERR_UNSUPPORTED;   // this build carries no user likelihood

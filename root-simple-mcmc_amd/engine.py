@@ -6,11 +6,12 @@ read back, GetProposeStep()-style setters/getters named as in TSimpleMCMC.H:732-
 on top of the C ABI of include/smcmc.h.  All compute happens in the HIP library.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
 from . import _capi
-from ._capi import (LIKE_ASYM, LIKE_CONSTRAINED, LIKE_EVENT_SAMPLE, LIKE_EVENT_TEMPLATE, LIKE_HORRIFIC, LIKE_ISO_GAUSS, LIKE_QUADFORM, LIKE_ROSENBROCK, LIKE_USER, MODE_FROZEN, MODE_PER_CHAIN, MODE_POOLED, P,  # noqa: F401
+from ._capi import (LIKE_ASYM, LIKE_CONSTRAINED, LIKE_EVENT_SAMPLE, LIKE_EVENT_SHAPE, LIKE_EVENT_TEMPLATE, LIKE_HORRIFIC, LIKE_ISO_GAUSS, LIKE_QUADFORM, LIKE_ROSENBROCK, LIKE_USER, MODE_FROZEN, MODE_PER_CHAIN, MODE_POOLED, P,  # noqa: F401
                     SmcmcError)
 # the reducers over a saved trace live in trace.py; their names stay importable from here
 from .trace import (Autocorrelation, AutocorrelationGrid, AutocorrelationPlan, Convergence, MacroAutocorrelation, Marginals,  # noqa: F401
@@ -88,6 +89,15 @@ class Engine(TraceReducers):
         if self.likelihood != LIKE_EVENT_TEMPLATE or self._likelihood_params is None:
             raise SmcmcError(_capi.ERR_LOGIC, "EventTemplateHistograms needs LIKE_EVENT_TEMPLATE and its parameters")
         logl, hist = event_template_evaluate(self._likelihood_params, point, histograms=True)
+        return hist, logl
+
+    def EventShapeHistograms(self, point):
+        """LIKE_EVENT_SHAPE: the expectation [4][nbins] (VeryClose, Close, Separated, DecayTag) at `point`, as
+        FakeLikelihood::WriteSimulation (example3/FakeLikelihood.H:232-239) fills it, and the log-likelihood there:
+        (hist, logl).  Evaluated on the host by smcmc_event_shape_evaluate, bit for bit what the device sums."""
+        if self.likelihood != LIKE_EVENT_SHAPE or self._likelihood_params is None:
+            raise SmcmcError(_capi.ERR_LOGIC, "EventShapeHistograms needs LIKE_EVENT_SHAPE and its parameters")
+        logl, hist = event_shape_evaluate(self._likelihood_params, point, histograms=True)
         return hist, logl
 
     def set_stream(self, stream):
@@ -469,6 +479,64 @@ def event_template_evaluate(params, point, histograms=False, parts=False):
                     "IS": float(raw[6 * nbins]), "IB": float(raw[6 * nbins + 1]), "ws": float(raw[6 * nbins + 2]),
                     "wb": float(raw[6 * nbins + 3])})
     return out[0] if len(out) == 1 else tuple(out)
+
+
+def event_shape_evaluate(params, point, histograms=False, parts=False):
+    """smcmc_event_shape_evaluate: LIKE_EVENT_SHAPE at `point` (31 values) on the host -- never to step a chain.
+    Returns logL; with histograms=True also the expectation mc[4][nbins] before the clamp; with parts=True also a dict of
+    the intermediate stages: S[4][nbins], B[4][nbins], IS, IB, ws, wb, penB, penS (the two shape penalties) and KinvB[11][11],
+    KinvS[13][13] (the inverted kernels).  The order is (logL, hist, parts), without what was not asked for."""
+    lib = _capi.load()
+    prm = _f64(params).ravel()
+    pt = _f64(point).ravel()
+    if pt.size != 31:
+        raise SmcmcError(_capi.ERR_INVALID, "the event shape has 31 parameters")
+    nbins = int(prm[1]) if prm.size > 1 and np.isfinite(prm[1]) and 1 <= prm[1] <= _capi.EVENT_SHAPE_MAX_BINS else 1
+    hist = np.zeros((4, nbins))
+    raw = np.zeros(8 * nbins + 6 + 121 + 169)
+    logl = C.c_double(0.0)
+    st = lib.smcmc_event_shape_evaluate(_ptr(prm), prm.size, _ptr(pt), C.byref(logl), _ptr(hist) if histograms else None,
+                                        _ptr(raw) if parts else None)
+    if st != _capi.OK:
+        raise SmcmcError(st, lib.smcmc_event_sample_last_error().decode() or lib.smcmc_status_string(st).decode())
+    out = [logl.value]
+    if histograms:
+        out.append(hist)
+    if parts:
+        t = raw[8 * nbins:]
+        out.append({"S": raw[:4 * nbins].reshape(4, nbins).copy(), "B": raw[4 * nbins:8 * nbins].reshape(4, nbins).copy(),
+                    "IS": float(t[0]), "IB": float(t[1]), "ws": float(t[2]), "wb": float(t[3]), "penB": float(t[4]),
+                    "penS": float(t[5]), "KinvB": t[6:127].reshape(11, 11).copy(), "KinvS": t[127:296].reshape(13, 13).copy()})
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def event_shape_kernel(low, high, n, coherence, sigma=1.0, exponential=False):
+    """TFakeGP::GaussianKernel (TFakeGP.H:96-109; exponential=True: ExponentialKernel, :113-126) on n control bins over
+    [low, high]: the n x n kernel matrix, entries whose exponent passes 20 exactly zero."""
+    bw = (high - low) / n
+    c = [low + i * bw + 0.5 * bw for i in range(n)]
+    k = np.zeros((n, n))
+    for i in range(n):
+        for j in range(i, n):
+            r = (c[i] - c[j]) / coherence
+            r = abs(r) if exponential else 0.5 * r * r
+            k[i, j] = k[j, i] = 0.0 if r > 20 else sigma * sigma * math.exp(-r)
+    return k
+
+
+def event_shape_params(events, data, nbins, xmin, xmax, kernel_b=None, kernel_s=None, cut_very_close=50.0, cut_close=100.0,
+                       true_fakes=0.05, true_efficiency=0.5, bkg_range=(0.0, 500.0), sig_range=(0.0, 250.0)):
+    """The flat parameter array of LIKE_EVENT_SHAPE (include/smcmc.h).  events: [nevents][6] (Mass, Type, Separation, MuDk,
+    TrueMass, TrueMassSigma); data: [4][nbins] (VeryClose, Close, Separated, DecayTag); kernel_b [11][11] and kernel_s
+    [13][13]: the kernel matrices of the two shapes, by default example3's (SystematicCorrection.H:151-163): Gaussian,
+    coherence 100 and sigma 0.7 over the background's range, coherence 50 and sigma 1 over the signal's."""
+    events = _f64(events).reshape(-1, 6)
+    data = _f64(data).reshape(4, int(nbins))
+    kb = event_shape_kernel(bkg_range[0], bkg_range[1], 11, 100.0, 0.7) if kernel_b is None else _f64(kernel_b).reshape(11, 11)
+    ks = event_shape_kernel(sig_range[0], sig_range[1], 13, 50.0, 1.0) if kernel_s is None else _f64(kernel_s).reshape(13, 13)
+    head = [events.shape[0], int(nbins), xmin, xmax, cut_very_close, cut_close, true_fakes, true_efficiency,
+            bkg_range[0], bkg_range[1], sig_range[0], sig_range[1]]
+    return np.concatenate([np.asarray(head, dtype=np.float64), data.ravel(), kb.ravel(), ks.ravel(), events.ravel()])
 
 
 def event_sample_params(events, data, nbins, xmin, xmax, exposure_ratio=None, separation_cut=100.0, true_fakes=0.05,
