@@ -85,7 +85,7 @@ struct smcmc_engine {
     DeviceBuffer<double> d_Uop;    // large dimensions, fused order: U^T in matrix-operand order (smcmc_panel_mfma_kernel.hip.h)
     DeviceBuffer<double> d_like;
     int like_lds_bytes = 0;   // SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE / _SHAPE: dynamic LDS of a step launch (the lanes' histograms)
-    DeviceBuffer<double> d_like_park;   // SMCMC_LIKE_EVENT_TEMPLATE / _SHAPE: the park image [3 or 4 nbins][npad] (event_template_loglike); no chain state
+    DeviceBuffer<double> d_like_park;   // SMCMC_LIKE_EVENT_TEMPLATE / _SHAPE: the park image [3 or 4 nbins][npad] (event_two_pass_loglike); no chain state
     // QUADFORM with a sparse Error matrix: the non-zero entries of Error^T, row by row (quadform_csr); empty = dense only
     DeviceBuffer<int32_t> d_like_rowptr;
     DeviceBuffer<int32_t> d_like_cols;
@@ -370,8 +370,7 @@ int upload_like(smcmc_engine* h) {
             return fail(h, SMCMC_ERR_UNSUPPORTED, "the event-sample likelihood runs in reference-order arithmetic only (SMCMC_P_EXACT_ARITHMETIC = 1)");
         std::vector<double> packed;
         const bool tmpl = h->likelihood == SMCMC_LIKE_EVENT_TEMPLATE, shape = h->likelihood == SMCMC_LIKE_EVENT_SHAPE;
-        if (shape) smcmc::esh_pack(h->like_params.data(), packed);  // (the kernels inverted, the events located on their shapes)
-        else smcmc::es_pack(h->like_params.data(), packed, tmpl);  // (the template's events partitioned by class)
+        smcmc::es_pack(h->likelihood, h->like_params.data(), packed);
         // the template's park image, [3 nbins][npad] (the shape's: [4 nbins][npad]), comes with the parameters; all or
         // nothing: a second allocation that fails leaves the engine with the images and sizes it had
         const size_t park = (tmpl ? (size_t)3 : shape ? (size_t)4 : (size_t)0) * (size_t)packed[SMCMC_ES_H_NBINS] * (size_t)h->npad;
@@ -385,8 +384,7 @@ int upload_like(smcmc_engine* h) {
         }
         HIP_TRY(h, hipMemcpyAsync(h->d_like, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        h->like_lds_bytes = shape ? smcmc::event_shape_lds_bytes((int)packed[SMCMC_ES_H_NBINS])
-                                  : smcmc::event_sample_lds_bytes((int)packed[SMCMC_ES_H_NBINS]);
+        h->like_lds_bytes = smcmc::event_lds_bytes(h->likelihood, (int)packed[SMCMC_ES_H_NBINS]);
         return SMCMC_OK;
     }
     if (stress_likelihood(h->likelihood)) {

@@ -1,5 +1,6 @@
-// smcmc_event_sample.hip -- smcmc_event_sample_evaluate and smcmc_event_template_evaluate (include/smcmc.h):
-// SMCMC_LIKE_EVENT_SAMPLE and SMCMC_LIKE_EVENT_TEMPLATE evaluated on the host from the header the device kernels compile (include/smcmc_event_sample.h), for what the reference does outside
+// smcmc_event_sample.hip -- smcmc_event_sample_evaluate, smcmc_event_template_evaluate and smcmc_event_shape_evaluate
+// (include/smcmc.h): the three likelihoods over a simulated event sample evaluated on the host from the header the device
+// kernels compile (include/smcmc_event_sample.h), for what the reference does outside
 // Step(): Init()'s exposure ratio and WriteSimulation() (example/FakeLikelihood.H:107-143, 173-179).  No chain is
 // stepped here.  Compile with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -13,59 +14,46 @@
 
 namespace {
 thread_local std::string es_error;
-}
 
-extern "C" int smcmc_event_sample_evaluate(const double* params, int count, const double* point, double* logl, double* hist) {
+// what the three evaluators do before they walk: the arguments, the rules of the array, the packed layout
+int es_prepare(const char* entry, int likelihood, const double* params, int count, const double* point, const double* logl,
+               std::vector<double>& packed) {
     if (!point || !logl || count < 0) {
-        es_error = "smcmc_event_sample_evaluate: point and logl must be given";
+        es_error = std::string(entry) + ": point and logl must be given";
         return SMCMC_ERR_INVALID;
     }
-    const char* why = smcmc::es_check(params, (size_t)count);
+    const char* why = smcmc::es_check_like(likelihood, params, (size_t)count);
     if (why) {
         es_error = why;
         return SMCMC_ERR_INVALID;
     }
-    std::vector<double> packed;
-    smcmc::es_pack(params, packed);
-    *logl = smcmc::es_evaluate_packed(packed.data(), point, hist);
+    smcmc::es_pack(likelihood, params, packed);
     es_error.clear();
     return SMCMC_OK;
+}
+}
+
+extern "C" int smcmc_event_sample_evaluate(const double* params, int count, const double* point, double* logl, double* hist) {
+    std::vector<double> packed;
+    const int st = es_prepare("smcmc_event_sample_evaluate", SMCMC_LIKE_EVENT_SAMPLE, params, count, point, logl, packed);
+    if (st == SMCMC_OK) *logl = smcmc::es_evaluate_packed(packed.data(), point, hist);
+    return st;
 }
 
 extern "C" int smcmc_event_template_evaluate(const double* params, int count, const double* point, double* logl, double* hist,
                                              double* parts) {
-    if (!point || !logl || count < 0) {
-        es_error = "smcmc_event_template_evaluate: point and logl must be given";
-        return SMCMC_ERR_INVALID;
-    }
-    const char* why = smcmc::et_check(params, (size_t)count);
-    if (why) {
-        es_error = why;
-        return SMCMC_ERR_INVALID;
-    }
     std::vector<double> packed;
-    smcmc::es_pack(params, packed, true);
-    *logl = smcmc::et_evaluate_packed(packed.data(), point, hist, parts);
-    es_error.clear();
-    return SMCMC_OK;
+    const int st = es_prepare("smcmc_event_template_evaluate", SMCMC_LIKE_EVENT_TEMPLATE, params, count, point, logl, packed);
+    if (st == SMCMC_OK) *logl = smcmc::es_two_pass_packed(false, packed.data(), point, hist, parts);
+    return st;
 }
 
 extern "C" int smcmc_event_shape_evaluate(const double* params, int count, const double* point, double* logl, double* hist,
                                           double* parts) {
-    if (!point || !logl || count < 0) {
-        es_error = "smcmc_event_shape_evaluate: point and logl must be given";
-        return SMCMC_ERR_INVALID;
-    }
-    const char* why = smcmc::esh_check(params, (size_t)count);
-    if (why) {
-        es_error = why;
-        return SMCMC_ERR_INVALID;
-    }
     std::vector<double> packed;
-    smcmc::esh_pack(params, packed);
-    *logl = smcmc::esh_evaluate_packed(packed.data(), point, hist, parts);
-    es_error.clear();
-    return SMCMC_OK;
+    const int st = es_prepare("smcmc_event_shape_evaluate", SMCMC_LIKE_EVENT_SHAPE, params, count, point, logl, packed);
+    if (st == SMCMC_OK) *logl = smcmc::es_two_pass_packed(true, packed.data(), point, hist, parts);
+    return st;
 }
 
 extern "C" int smcmc_event_shape_gp_value(double low, double high, int n, const double* y, double x, double* value) {

@@ -12,24 +12,14 @@ namespace smcmc {
 
 template <int DP, int LIKE, bool EXACT, bool FULLU, bool MOM, bool SPECIAL>
 static hipError_t go(const StepParams& p, hipStream_t s) {
-    if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE || LIKE == SMCMC_LIKE_EVENT_TEMPLATE) {
-        // the lanes' histograms in dynamic LDS (event_sample_loglike): more than the default limit
+    if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE || LIKE == SMCMC_LIKE_EVENT_TEMPLATE || LIKE == SMCMC_LIKE_EVENT_SHAPE) {
+        // the lanes' histograms (and the shape's tables) in dynamic LDS: more than the default limit; the two-pass
+        // likelihoods' park image comes with the parameters
         auto kernel = step_kernel<DP, LIKE, EXACT, FULLU, MOM, SPECIAL>;
-        if (p.like_lds_bytes <= 0 || p.like_lds_bytes > event_sample_lds_bytes(SMCMC_EVENT_SAMPLE_MAX_BINS)) return hipErrorInvalidValue;
-        if (LIKE == SMCMC_LIKE_EVENT_TEMPLATE && !p.like_park) return hipErrorInvalidValue;     // (the park image, with the parameters)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 event_sample_lds_bytes(SMCMC_EVENT_SAMPLE_MAX_BINS));
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kernel, dim3(p.npad / kWave), dim3(kWave), (size_t)p.like_lds_bytes, s, p);
-        return hipGetLastError();
-    }
-    if constexpr (LIKE == SMCMC_LIKE_EVENT_SHAPE) {
-        // the lanes' histograms and shape tables in dynamic LDS (event_shape_loglike), and the park image
-        auto kernel = step_kernel<DP, LIKE, EXACT, FULLU, MOM, SPECIAL>;
-        if (p.like_lds_bytes <= 0 || p.like_lds_bytes > event_shape_lds_bytes(SMCMC_EVENT_SHAPE_MAX_BINS) || !p.like_park)
-            return hipErrorInvalidValue;
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 event_shape_lds_bytes(SMCMC_EVENT_SHAPE_MAX_BINS));
+        constexpr int cap = event_lds_bytes(LIKE, event_max_bins(LIKE));
+        if (p.like_lds_bytes <= 0 || p.like_lds_bytes > cap) return hipErrorInvalidValue;
+        if (LIKE != SMCMC_LIKE_EVENT_SAMPLE && !p.like_park) return hipErrorInvalidValue;
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kernel, dim3(p.npad / kWave), dim3(kWave), (size_t)p.like_lds_bytes, s, p);
         return hipGetLastError();

@@ -227,7 +227,7 @@ struct StepParams {
                                // compiler does not hoist (and then spill) whole tables out of the loop
     unsigned long long* prof;  // section profile (SMCMC_STEP_PROFILE builds only): [group][kProfSlots][64] cycle sums, added to
     int like_lds_bytes;        // SMCMC_LIKE_EVENT_SAMPLE / _TEMPLATE / _SHAPE: dynamic LDS of the launch, the lanes' histograms (event_sample_lds_bytes, event_shape_lds_bytes)
-    double* like_park;         // SMCMC_LIKE_EVENT_TEMPLATE / _SHAPE: the park image [3 or 4 nbins][npad] (event_template_loglike)
+    double* like_park;         // SMCMC_LIKE_EVENT_TEMPLATE / _SHAPE: the park image [3 or 4 nbins][npad] (event_two_pass_loglike)
 };
 
 // ---- Section profile of the step loop: -DSMCMC_STEP_PROFILE=1 (sections) or 2 (sections and every piece) ----
@@ -407,7 +407,8 @@ __device__ __forceinline__ double loglike(const double (&p)[DP], cptr_f64 prm, i
     return logl;
 }
 
-// ---- SMCMC_LIKE_EVENT_SAMPLE (smcmc.h; the arithmetic is include/smcmc_event_sample.h) ----
+// ---- The likelihoods over a simulated event sample (smcmc.h; the arithmetic is include/smcmc_event_sample.h): one
+// family, SMCMC_LIKE_EVENT_SAMPLE here, its two-pass members _TEMPLATE and _SHAPE below ----
 // One chain per lane.  Every lane walks all events in order; the packed sample is wave-uniform and comes through the
 // constant address space (a few scalar loads per event for the whole wavefront).  A lane's three histograms sit in
 // dynamic LDS as hist[bin][lane], bins laid end to end (Close, Separated, DecayTag) and one more row behind them that
@@ -473,98 +474,20 @@ __device__ __forceinline__ double event_sample_loglike(const double (&p)[DP], cp
     return logl;
 }
 
-// ---- SMCMC_LIKE_EVENT_TEMPLATE (smcmc.h; the arithmetic is include/smcmc_event_sample.h) ----
-// Six histograms per lane do not fit (154 KB at 50 bins beside kEsStaticLds), so the dynamic LDS stays
-// event_sample_lds_bytes(nbins) and the fill runs twice: over the signal events [0, nsignal), then, the rows zeroed again,
-// over the background events [nsignal, nevents), whose batches start at nsignal -- no batch straddles the classes.
-// Between the passes the lane sums its rows to the signal's integral and writes ws * S[r], the signal's share of every
-// bin, to its column of the park image: park[r][chain] in device memory, a row one coalesced 512-byte store of the
-// wavefront.  The bin sum reads the share back and adds wb * B[r].  A lane reads only what it wrote itself, in program
-// order: no fence.  The image is scratch of one evaluation, no chain state.
-// The fill of a lane's column `col` (zeroed by the caller) with the events [ebeg, nev) of `ev`, batches counted from ebeg:
-// event_sample_loglike's loop, batch for batch.  A second copy of that text, because the event sample calling a function
-// here -- this one over [0, nevents), or one for the batch alone -- changed its step kernels' control flow (sixteen more
-// scalar branches, other register numbers), and with its loop written out they are what they were, instruction for
-// instruction (profiles/event_template_notes.md).
-__device__ __forceinline__ void event_template_fill(double* const col, const cptr_f64 ev, const int ebeg, const int nev,
-                                                  const smcmc_es_scalars& s, const int nbins, const int rows,
-                                                  const double xmin, const double xmax, const double range, const double cut) {
-    for (int e0 = ebeg; e0 < nev; e0 += kEsBatch) {
-        int idx[kEsBatch];
-        double w[kEsBatch], v[kEsBatch];
-#pragma unroll
-        for (int u = 0; u < kEsBatch; ++u) {
-            const bool in = e0 + u < nev;                                   // (wave-uniform)
-            const cptr_f64 q = ev + (size_t)(in ? e0 + u : nev - 1) * SMCMC_ES_EVENT;
-            const int cls = (int)q[4];
-            const int b = smcmc_es_event_bin(q[0], q[1], q[2], q[3], cls >> 1, cls & 1, &s, nbins, xmin, xmax, range, cut);
-            idx[u] = (in && b >= 0) ? b : rows;
-            w[u] = (cls == 0) ? s.weight[0] : (cls == 1) ? s.weight[1] : (cls == 2) ? s.weight[2] : s.weight[3];
-        }
-#pragma unroll
-        for (int u = 0; u < kEsBatch; ++u) v[u] = col[idx[u] * kWave];
-#pragma unroll
-        for (int u = 0; u < kEsBatch; ++u) {
-#pragma unroll
-            for (int j = 0; j < u; ++j) v[u] = (idx[j] == idx[u]) ? v[j] : v[u];
-            v[u] = v[u] + w[u];
-        }
-#pragma unroll
-        for (int u = 0; u < kEsBatch; ++u) col[idx[u] * kWave] = v[u];
-    }
-}
-__device__ __forceinline__ double event_template_integral(const double* col, int nbins) {
-    double sum[3];
-    for (int k = 0; k < 3; ++k) {
-        const double* h = col + (size_t)k * nbins * kWave;
-        double v = 0.0;
-        for (int b = 0; b < nbins; ++b) v += h[b * kWave];
-        sum[k] = v;
-    }
-    return smcmc_et_integral(sum[0], sum[1], sum[2]);
-}
-// park: this lane's column of the image, rows npad apart
-template <int DP>
-__device__ __forceinline__ double event_template_loglike(const double (&p)[DP], cptr_f64 prm, double* hist, int lane,
-                                                         double* park, size_t npad) {
-    static_assert(DP >= SMCMC_ES_DIM, "the nine systematic parameters");
-    const int nev = (int)prm[SMCMC_ES_H_NEVENTS], nbins = (int)prm[SMCMC_ES_H_NBINS], nsig = (int)prm[SMCMC_ES_H_NSIGNAL];
-    const double xmin = prm[SMCMC_ES_H_XMIN], xmax = prm[SMCMC_ES_H_XMAX], range = prm[SMCMC_ES_H_RANGE];
-    const double cut = prm[SMCMC_ES_H_CUT];
-    double pt[SMCMC_ES_DIM];
-#pragma unroll
-    for (int i = 0; i < SMCMC_ES_DIM; ++i) pt[i] = p[i];
-    smcmc_es_scalars s;
-    smcmc_et_point_scalars(pt, prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF], prm[SMCMC_ES_H_TAN_FAKES],
-                           prm[SMCMC_ES_H_TAN_EFF], &s);
-    const int rows = 3 * nbins;                 // row `rows`: the dropped events'
-    double* const col = hist + lane;
-    const cptr_f64 ev = prm + SMCMC_ES_HEADER + rows;
-    double wb = 0.0;
-#pragma nounroll
-    for (int c = 0; c < 2; ++c) {               // (one copy of the fill's code)
-        for (int r = 0; r <= rows; ++r) col[r * kWave] = 0.0;
-        event_template_fill(col, ev, c ? nsig : 0, c ? nev : nsig, s, nbins, rows, xmin, xmax, range, cut);
-        const double norm = smcmc_et_norm(c ? pt[1] : pt[0], event_template_integral(col, nbins));
-        if (c == 0)
-            for (int r = 0; r < rows; ++r) park[(size_t)r * npad] = smcmc_et_mc_signal(norm, col[r * kWave]);
-        else wb = norm;
-    }
-    // example2/FakeLikelihood.H:64-89: the bins of Close, Separated, DecayTag, in that order
-    const cptr_f64 data = prm + SMCMC_ES_HEADER;
-    double logl = 0.0;
-    for (int r = 0; r < rows; ++r)
-        logl += smcmc_es_bin_term(data[r], smcmc_et_mc(park[(size_t)r * npad], wb, col[r * kWave]));
-    return smcmc_et_penalties(logl, pt);
-}
-
-// ---- SMCMC_LIKE_EVENT_SHAPE (smcmc.h; the arithmetic is include/smcmc_event_shape.h) ----
-// The event template's two passes and park image, with four histograms per lane -- hist[4 nbins + 1][lane], the park image
-// [4 nbins][npad] -- in the 31-wide family.  An event's weight is its class's weight times exp(shape), and the shape
-// reads the lane's control value y[k] and slope[k] at an index k that the packed event carries: wave-uniform, but known
-// only at run time, so a register array would go to scratch inside the event loop.  The tables sit in the dynamic LDS
-// behind the histograms as table[row][lane]: rows [0, n) the control values, rows [n, 2 n - 1) the slopes of the class
-// whose pass is running -- n = 13 and 25 rows for the signal, n = 11 and 21 rows for the background.
+// ---- SMCMC_LIKE_EVENT_TEMPLATE and SMCMC_LIKE_EVENT_SHAPE (smcmc.h): the two-pass members of the family ----
+// Six histograms per lane do not fit (154 KB at 50 bins beside kEsStaticLds), so a lane has the NH histograms of ONE class
+// -- hist[NH nbins + 1][lane], NH = 3 for the template and 4 for the shape -- and the fill runs twice: over the signal
+// events [0, nsignal), then, the rows zeroed again, over the background events [nsignal, nevents), whose batches start at
+// nsignal -- no batch straddles the classes.  Between the passes the lane sums its rows to the signal's integral and writes
+// ws * S[r], the signal's share of every bin, to its column of the park image: park[r][chain] in device memory, a row one
+// coalesced 512-byte store of the wavefront.  The bin sum reads the share back and adds wb * B[r].  A lane reads only what
+// it wrote itself, in program order: no fence.  The image is scratch of one evaluation, no chain state.
+//
+// The shape's weight of an event is its class's weight times exp(shape), and the shape reads the lane's control value y[k]
+// and slope[k] at an index k that the packed event carries: wave-uniform, but known only at run time, so a register array
+// would go to scratch inside the event loop.  The tables sit in the dynamic LDS behind the histograms as table[row][lane]:
+// rows [0, n) the control values, rows [n, 2 n - 1) the slopes of the class whose pass is running -- n = 13 and 25 rows
+// for the signal, n = 11 and 21 rows for the background.  The family the shape is built for (dim = 31):
 constexpr int kEshDP = 31;
 constexpr int kEshTableRows = 2 * SMCMC_ESH_NS - 1;
 static_assert(SMCMC_ESH_NS >= SMCMC_ESH_NB, "the signal's tables are the larger");
@@ -575,27 +498,46 @@ static_assert(kEshStaticLds + event_shape_lds_bytes(SMCMC_EVENT_SHAPE_MAX_BINS) 
               kEshStaticLds + event_shape_lds_bytes(SMCMC_EVENT_SHAPE_MAX_BINS + 1) > kEsLdsLimit,
               "SMCMC_EVENT_SHAPE_MAX_BINS (smcmc.h) is the largest nbins whose histograms and tables fit one workgroup beside the kernel's static LDS");
 static_assert(SMCMC_EVENT_SHAPE_MAX_BINS >= 50, "example3's own 50 bins must fit: shrink the tables, not the histograms");
-// event_template_fill with the weight multiplied by exp(shape).  tab: this lane's column of the tables of the pass's
-// class, nctl its number of control values.
-__device__ __forceinline__ void event_shape_fill(double* const col, const double* const tab, const int nctl, const cptr_f64 ev,
-                                               const int ebeg, const int nev, const smcmc_es_scalars& s, const int nbins,
-                                               const int rows, const double xmin, const double xmax, const double range,
-                                               const double cut_very_close, const double cut_close) {
+// the dynamic LDS of a launch and the largest nbins it is sized for, by likelihood
+constexpr int event_lds_bytes(int like, int nbins) {
+    return like == SMCMC_LIKE_EVENT_SHAPE ? event_shape_lds_bytes(nbins) : event_sample_lds_bytes(nbins);
+}
+constexpr int event_max_bins(int like) {
+    return like == SMCMC_LIKE_EVENT_SHAPE ? SMCMC_EVENT_SHAPE_MAX_BINS : SMCMC_EVENT_SAMPLE_MAX_BINS;
+}
+
+// The fill of a lane's column `col` (zeroed by the caller) with the events [ebeg, nev) of `ev`, batches counted from ebeg:
+// event_sample_loglike's loop, batch for batch, and for the two-pass likelihoods the one shared copy.  Not shared with
+// the event sample, because the event sample calling a function here -- this one over [0, nevents), or one for the batch
+// alone -- changed its step kernels' control flow (sixteen more scalar branches, other register numbers), and with its
+// loop written out they are what they were, instruction for instruction (profiles/event_template_notes.md).
+// SHAPE: eight doubles per event, four histograms and the weight multiplied by exp(shape); tab: this lane's column of the
+// tables of the pass's class, nctl its number of control values (neither is read without SHAPE, nor is cut_very_close).
+template <bool SHAPE>
+__device__ __forceinline__ void event_fill(double* const col, const double* const tab, const int nctl, const cptr_f64 ev,
+                                           const int ebeg, const int nev, const smcmc_es_scalars& s, const int nbins,
+                                           const int rows, const double xmin, const double xmax, const double range,
+                                           const double cut_very_close, const double cut) {
+    constexpr int STRIDE = SHAPE ? SMCMC_ESH_EVENT : SMCMC_ES_EVENT;
     for (int e0 = ebeg; e0 < nev; e0 += kEsBatch) {
         int idx[kEsBatch];
         double w[kEsBatch], v[kEsBatch];
 #pragma unroll
         for (int u = 0; u < kEsBatch; ++u) {
             const bool in = e0 + u < nev;                                   // (wave-uniform)
-            const cptr_f64 q = ev + (size_t)(in ? e0 + u : nev - 1) * SMCMC_ESH_EVENT;
+            const cptr_f64 q = ev + (size_t)(in ? e0 + u : nev - 1) * STRIDE;
             const int cls = (int)q[4];
-            const int k = (int)q[5];                                        // (wave-uniform; 0 <= k < nctl: esh_pack)
-            const int ks = (k < nctl - 1) ? k : nctl - 2;                   // (a clamped event at the last centre has no slope)
-            const int b = smcmc_esh_event_bin(q[0], q[1], q[2], q[3], cls >> 1, cls & 1, &s, nbins, xmin, xmax, range,
-                                              cut_very_close, cut_close);
+            int b, k = 0, ks = 0;
+            if constexpr (SHAPE) {
+                k = (int)q[5];                                              // (wave-uniform; 0 <= k < nctl: es_pack)
+                ks = (k < nctl - 1) ? k : nctl - 2;                         // (a clamped event at the last centre has no slope)
+                b = smcmc_esh_event_bin(q[0], q[1], q[2], q[3], cls >> 1, cls & 1, &s, nbins, xmin, xmax, range, cut_very_close, cut);
+            } else {
+                b = smcmc_es_event_bin(q[0], q[1], q[2], q[3], cls >> 1, cls & 1, &s, nbins, xmin, xmax, range, cut);
+            }
             idx[u] = (in && b >= 0) ? b : rows;
-            const double cw = (cls == 0) ? s.weight[0] : (cls == 1) ? s.weight[1] : (cls == 2) ? s.weight[2] : s.weight[3];
-            w[u] = smcmc_esh_weight(cw, smcmc_esh_shape(tab[k * kWave], tab[(nctl + ks) * kWave], q[6], q[7] != 0.0));
+            w[u] = (cls == 0) ? s.weight[0] : (cls == 1) ? s.weight[1] : (cls == 2) ? s.weight[2] : s.weight[3];
+            if constexpr (SHAPE) w[u] = smcmc_esh_weight(w[u], smcmc_esh_shape(tab[k * kWave], tab[(nctl + ks) * kWave], q[6], q[7] != 0.0));
         }
 #pragma unroll
         for (int u = 0; u < kEsBatch; ++u) v[u] = col[idx[u] * kWave];
@@ -609,15 +551,17 @@ __device__ __forceinline__ void event_shape_fill(double* const col, const double
         for (int u = 0; u < kEsBatch; ++u) col[idx[u] * kWave] = v[u];
     }
 }
-__device__ __forceinline__ double event_shape_integral(const double* col, int nbins) {
-    double sum[4];
-    for (int k = 0; k < 4; ++k) {
+// a class's integral from the lane's NH histograms
+template <int NH>
+__device__ __forceinline__ double event_integral(const double* col, int nbins) {
+    double sum[NH];
+    for (int k = 0; k < NH; ++k) {
         const double* h = col + (size_t)k * nbins * kWave;
         double v = 0.0;
         for (int b = 0; b < nbins; ++b) v += h[b * kWave];
         sum[k] = v;
     }
-    return smcmc_esh_integral(sum[0], sum[1], sum[2], sum[3]);
+    return smcmc_et_integral(sum, NH);
 }
 // TFakeGP::GetPenalty of N control values in registers, the inverse kernel through the constant address space
 template <int N>
@@ -630,7 +574,7 @@ __device__ __forceinline__ double event_shape_penalty(const double (&y)[N], cons
     }
     return penalty;
 }
-// this lane's column of the tables: the control values y and the slopes between the centres c
+// this lane's column of the shape's tables: the control values y and the slopes between the centres c
 template <int N>
 __device__ __forceinline__ void event_shape_tables(double* const tab, const double (&y)[N], const cptr_f64 c) {
 #pragma unroll
@@ -638,50 +582,64 @@ __device__ __forceinline__ void event_shape_tables(double* const tab, const doub
 #pragma unroll
     for (int i = 0; i + 1 < N; ++i) tab[(N + i) * kWave] = smcmc_esh_slope(y[i], y[i + 1], c[i], c[i + 1]);
 }
+// The two-pass likelihood: zero, fill, integral, norm, park after pass 0, then the bin sum from park plus wb * col
+// (example2/FakeLikelihood.H:64-89, example3/FakeLikelihood.H:68-102: the bins of [VeryClose,] Close, Separated, DecayTag,
+// in that order) and the penalties.  The shape writes its tables before each pass and adds its two penalties after.
 // park: this lane's column of the image, rows npad apart
-template <int DP>
-__device__ __forceinline__ double event_shape_loglike(const double (&p)[DP], cptr_f64 prm, double* hist, int lane,
-                                                      double* park, size_t npad) {
-    static_assert(DP >= SMCMC_ESH_DIM, "the 31 parameters of example3");
+template <int DP, bool SHAPE>
+__device__ __forceinline__ double event_two_pass_loglike(const double (&p)[DP], cptr_f64 prm, double* hist, int lane,
+                                                         double* park, size_t npad) {
+    constexpr int DIM = SHAPE ? SMCMC_ESH_DIM : SMCMC_ES_DIM, NH = SHAPE ? 4 : 3;
+    static_assert(DP >= DIM, "the nine systematic parameters, or the 31 parameters of example3");
     const int nev = (int)prm[SMCMC_ES_H_NEVENTS], nbins = (int)prm[SMCMC_ES_H_NBINS], nsig = (int)prm[SMCMC_ES_H_NSIGNAL];
     const double xmin = prm[SMCMC_ES_H_XMIN], xmax = prm[SMCMC_ES_H_XMAX], range = prm[SMCMC_ES_H_RANGE];
-    const double cut_close = prm[SMCMC_ES_H_CUT], cut_very_close = prm[SMCMC_ESH_H_CUT_VERY_CLOSE];
-    double pt[SMCMC_ESH_DIM];
+    const double cut = prm[SMCMC_ES_H_CUT], cut_very_close = SHAPE ? prm[SMCMC_ESH_H_CUT_VERY_CLOSE] : 0.0;
+    double pt[DIM];
 #pragma unroll
-    for (int i = 0; i < SMCMC_ESH_DIM; ++i) pt[i] = p[i];
+    for (int i = 0; i < DIM; ++i) pt[i] = p[i];
     smcmc_es_scalars s;
-    smcmc_esh_point_scalars(pt, prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF], prm[SMCMC_ES_H_TAN_FAKES],
-                            prm[SMCMC_ES_H_TAN_EFF], &s);
-    double yb[SMCMC_ESH_NB], ys[SMCMC_ESH_NS];
+    double yb[SHAPE ? SMCMC_ESH_NB : 1], ys[SHAPE ? SMCMC_ESH_NS : 1];
+    if constexpr (SHAPE) {
+        smcmc_esh_point_scalars(pt, prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF], prm[SMCMC_ES_H_TAN_FAKES],
+                                prm[SMCMC_ES_H_TAN_EFF], &s);
 #pragma unroll
-    for (int i = 0; i < SMCMC_ESH_NB; ++i) yb[i] = smcmc_esh_control_b(pt, i);
+        for (int i = 0; i < SMCMC_ESH_NB; ++i) yb[i] = smcmc_esh_control_b(pt, i);
 #pragma unroll
-    for (int i = 0; i < SMCMC_ESH_NS; ++i) ys[i] = smcmc_esh_control_s(pt, i);
-    const int rows = 4 * nbins;                 // row `rows`: the dropped events'
+        for (int i = 0; i < SMCMC_ESH_NS; ++i) ys[i] = smcmc_esh_control_s(pt, i);
+    } else {
+        smcmc_et_point_scalars(pt, prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF], prm[SMCMC_ES_H_TAN_FAKES],
+                               prm[SMCMC_ES_H_TAN_EFF], &s);
+    }
+    const int rows = NH * nbins;                // row `rows`: the dropped events'
     double* const col = hist + lane;
-    double* const tab = col + (size_t)(rows + 1) * kWave;
-    const cptr_f64 ev = prm + SMCMC_ESH_EVENTS(nbins);
+    double* const tab = col + (size_t)(rows + 1) * kWave;       // (the shape's alone)
+    const cptr_f64 ev = prm + (SHAPE ? SMCMC_ESH_EVENTS(nbins) : SMCMC_ES_HEADER + rows);
     double wb = 0.0;
 #pragma nounroll
     for (int c = 0; c < 2; ++c) {               // (one copy of the fill's code)
         for (int r = 0; r <= rows; ++r) col[r * kWave] = 0.0;
-        if (c == 0) event_shape_tables<SMCMC_ESH_NS>(tab, ys, prm + SMCMC_ESH_CENTRE_S(nbins));
-        else event_shape_tables<SMCMC_ESH_NB>(tab, yb, prm + SMCMC_ESH_CENTRE_B(nbins));
-        event_shape_fill(col, tab, c ? SMCMC_ESH_NB : SMCMC_ESH_NS, ev, c ? nsig : 0, c ? nev : nsig, s, nbins, rows, xmin, xmax,
-                         range, cut_very_close, cut_close);
-        const double norm = smcmc_et_norm(c ? pt[1] : pt[0], event_shape_integral(col, nbins));
+        if constexpr (SHAPE) {
+            if (c == 0) event_shape_tables<SMCMC_ESH_NS>(tab, ys, prm + SMCMC_ESH_CENTRE_S(nbins));
+            else event_shape_tables<SMCMC_ESH_NB>(tab, yb, prm + SMCMC_ESH_CENTRE_B(nbins));
+        }
+        event_fill<SHAPE>(col, tab, c ? SMCMC_ESH_NB : SMCMC_ESH_NS, ev, c ? nsig : 0, c ? nev : nsig, s, nbins, rows, xmin, xmax,
+                          range, cut_very_close, cut);
+        const double norm = smcmc_et_norm(c ? pt[1] : pt[0], event_integral<NH>(col, nbins));
         if (c == 0)
             for (int r = 0; r < rows; ++r) park[(size_t)r * npad] = smcmc_et_mc_signal(norm, col[r * kWave]);
         else wb = norm;
     }
-    // example3/FakeLikelihood.H:68-102: the bins of VeryClose, Close, Separated, DecayTag, in that order
     const cptr_f64 data = prm + SMCMC_ES_HEADER;
     double logl = 0.0;
     for (int r = 0; r < rows; ++r)
         logl += smcmc_es_bin_term(data[r], smcmc_et_mc(park[(size_t)r * npad], wb, col[r * kWave]));
-    const double pen_b = event_shape_penalty<SMCMC_ESH_NB>(yb, prm + SMCMC_ESH_KINV_B(nbins));
-    const double pen_s = event_shape_penalty<SMCMC_ESH_NS>(ys, prm + SMCMC_ESH_KINV_S(nbins));
-    return smcmc_esh_penalties(logl, pt, pen_b, pen_s);
+    if constexpr (SHAPE) {
+        const double pen_b = event_shape_penalty<SMCMC_ESH_NB>(yb, prm + SMCMC_ESH_KINV_B(nbins));
+        const double pen_s = event_shape_penalty<SMCMC_ESH_NS>(ys, prm + SMCMC_ESH_KINV_S(nbins));
+        return smcmc_esh_penalties(logl, pt, pen_b, pen_s);
+    } else {
+        return smcmc_et_penalties(logl, pt[0], pt[1], pt[6], pt[7], pt[8]);
+    }
 }
 
 // SPECIAL = the variant that also knows uniform per-dimension proposals, the scan of one dimension
@@ -1052,9 +1010,9 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         }
         else if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE) logl_prop = event_sample_loglike<DP>(xp, likep + p.zero * (s + 1), es_hist, lane);
         else if constexpr (LIKE == SMCMC_LIKE_EVENT_TEMPLATE)
-            logl_prop = event_template_loglike<DP>(xp, likep + p.zero * (s + 1), es_hist, lane, p.like_park + chain, NP);
+            logl_prop = event_two_pass_loglike<DP, false>(xp, likep + p.zero * (s + 1), es_hist, lane, p.like_park + chain, NP);
         else if constexpr (LIKE == SMCMC_LIKE_EVENT_SHAPE)
-            logl_prop = event_shape_loglike<DP>(xp, likep + p.zero * (s + 1), es_hist, lane, p.like_park + chain, NP);
+            logl_prop = event_two_pass_loglike<DP, true>(xp, likep + p.zero * (s + 1), es_hist, lane, p.like_park + chain, NP);
         else if constexpr (!RMS_AHEAD) logl_prop = loglike<DP, LIKE, EXACT>(xp, likep + p.zero * (s + 1), D);
         if constexpr (!RMS_AHEAD) SMCMC_PROF_MARK(PROF_LIKE);
         bool take;

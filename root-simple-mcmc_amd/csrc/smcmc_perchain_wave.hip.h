@@ -104,6 +104,10 @@ __device__ __forceinline__ double pw_ordered_sum(double t, int n, double* scratc
 // p: the point in LDS (ps).  Static LDS: 64 posts and the bin terms, 3.3 KB.
 constexpr int kEsOwn = (3 * SMCMC_EVENT_SAMPLE_MAX_BINS + kWave - 1) / kWave;
 static_assert(kEsOwn * kWave >= 3 * SMCMC_EVENT_SAMPLE_MAX_BINS + kPwBatch, "the last batch of the bin sum reads inside `term`");
+// ... and of the four histograms of SMCMC_LIKE_EVENT_SHAPE
+constexpr int kEshOwn = (4 * SMCMC_EVENT_SHAPE_MAX_BINS + kWave - 1) / kWave;
+static_assert(kEshOwn <= kEsOwn, "pw_event_sample_scan takes the owners' registers as an array of kEsOwn");
+static_assert(kEshOwn * kWave >= 4 * SMCMC_EVENT_SHAPE_MAX_BINS + kPwBatch, "the last batch of the bin sum reads inside `term`");
 // the scan of one batch's posts by a lane that owns N bins (N compile-time: with the count as a run-time bound of the
 // inner loop every post cost five scalar branches, 2.7 ms per step at 30 000 events instead of 1.3)
 template <int N>
@@ -116,22 +120,40 @@ __device__ __forceinline__ void pw_event_sample_scan(const int* post_bin, const 
         for (int r = 0; r < N; ++r) own[r] = (d == kWave * r) ? own[r] + wk : own[r];
     }
 }
-// the deal-events / own-bins scan over the events [ebeg, nev) of `ev`, batches of 64 counted from ebeg; nown: the
-// registers of `own` in use (wave-uniform)
-__device__ __forceinline__ void pw_event_sample_range(const double* const ev, const int ebeg, const int nev, const smcmc_es_scalars& s,
-                                                      const int nbins, const int nown, const double xmin, const double xmax,
-                                                      const double range, const double cut, int* post_bin, double* post_w,
-                                                      const int lane, double (&own)[kEsOwn]) {
+// The deal-events / own-bins scan over the events [ebeg, nev) of `ev`, batches of 64 counted from ebeg; nown: the
+// registers of `own` in use (wave-uniform).  SHAPE: eight doubles per event, four histograms and the weight multiplied by
+// exp(shape), which the lane that corrects the event forms too; y: the control values of the pass's class in LDS, nctl of
+// them, and behind them the nctl - 1 slopes (neither is read without SHAPE, nor is cut_very_close).
+template <bool SHAPE>
+__device__ __forceinline__ void pw_event_range(const double* const ev, const int ebeg, const int nev, const smcmc_es_scalars& s,
+                                               const int nbins, const int nown, const double xmin, const double xmax,
+                                               const double range, const double cut_very_close, const double cut,
+                                               const double* y, const int nctl, int* post_bin, double* post_w,
+                                               const int lane, double (&own)[kEsOwn]) {
+    constexpr int STRIDE = SHAPE ? SMCMC_ESH_EVENT : SMCMC_ES_EVENT;
+    constexpr int OWN = SHAPE ? kEshOwn : kEsOwn;       // (50 bins: 150 rows and 3 registers, the shape's 200 rows and 4)
+    static_assert(OWN >= 4, "the switch below names the counts up to four");
     for (int e0 = ebeg; e0 < nev; e0 += kWave) {
         const int e = e0 + lane;
         int b = -1;
         double w = 0.0;
         if (e < nev) {
-            const double* q = ev + (size_t)e * SMCMC_ES_EVENT;
+            const double* q = ev + (size_t)e * STRIDE;
             const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
             const int cls = (int)q[4];
-            b = smcmc_es_event_bin(q0, q1, q2, q3, cls >> 1, cls & 1, &s, nbins, xmin, xmax, range, cut);
-            w = (cls == 0) ? s.weight[0] : (cls == 1) ? s.weight[1] : (cls == 2) ? s.weight[2] : s.weight[3];
+            if constexpr (SHAPE) {
+                const double dx = q[6];
+                int k = (int)q[5];
+                k = (k < 0) ? 0 : (k > nctl - 1) ? nctl - 1 : k;        // (es_pack's range; the table is not read outside it)
+                const int ks = (k < nctl - 1) ? k : nctl - 2;           // (a clamped event at the last centre has no slope)
+                const bool clamped = q[7] != 0.0;
+                b = smcmc_esh_event_bin(q0, q1, q2, q3, cls >> 1, cls & 1, &s, nbins, xmin, xmax, range, cut_very_close, cut);
+                const double cw = (cls == 0) ? s.weight[0] : (cls == 1) ? s.weight[1] : (cls == 2) ? s.weight[2] : s.weight[3];
+                w = smcmc_esh_weight(cw, smcmc_esh_shape(y[k], y[nctl + ks], dx, clamped));
+            } else {
+                b = smcmc_es_event_bin(q0, q1, q2, q3, cls >> 1, cls & 1, &s, nbins, xmin, xmax, range, cut);
+                w = (cls == 0) ? s.weight[0] : (cls == 1) ? s.weight[1] : (cls == 2) ? s.weight[2] : s.weight[3];
+            }
         }
         __syncthreads();                                // the scan of the batch before is over
         post_bin[lane] = b;
@@ -140,9 +162,14 @@ __device__ __forceinline__ void pw_event_sample_range(const double* const ev, co
         switch (nown) {
             case 1: pw_event_sample_scan<1>(post_bin, post_w, lane, own); break;
             case 2: pw_event_sample_scan<2>(post_bin, post_w, lane, own); break;
-            case 3: pw_event_sample_scan<3>(post_bin, post_w, lane, own); break;     // (50 bins: 150 rows)
-            case 4: pw_event_sample_scan<(kEsOwn < 4 ? kEsOwn : 4)>(post_bin, post_w, lane, own); break;
-            default: pw_event_sample_scan<kEsOwn>(post_bin, post_w, lane, own); break;
+            case 3: pw_event_sample_scan<3>(post_bin, post_w, lane, own); break;
+            case 4:
+                if constexpr (OWN > 4) {
+                    pw_event_sample_scan<4>(post_bin, post_w, lane, own);
+                    break;
+                }
+                [[fallthrough]];                        // (four are all the shape's owners have)
+            default: pw_event_sample_scan<OWN>(post_bin, post_w, lane, own); break;
         }
     }
 }
@@ -180,7 +207,7 @@ __device__ __forceinline__ double pw_event_sample(const double* p, const double*
 #pragma unroll
     for (int r = 0; r < kEsOwn; ++r) own[r] = 0.0;
     const double* const ev = like + SMCMC_ES_HEADER + rows;
-    pw_event_sample_range(ev, 0, nev, s, nbins, nown, xmin, xmax, range, cut, post_bin, post_w, lane, own);
+    pw_event_range<false>(ev, 0, nev, s, nbins, nown, xmin, xmax, range, 0.0, cut, nullptr, 0, post_bin, post_w, lane, own);
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < kEsOwn; ++r) {
@@ -192,139 +219,27 @@ __device__ __forceinline__ double pw_event_sample(const double* p, const double*
     return pw_event_sample_sum(term, rows);
 }
 
-// SMCMC_LIKE_EVENT_TEMPLATE for one chain on 64 lanes: the scan above over the signal events, the owners' bins published
-// to `term` and summed by every lane alike to the class integral (three histograms, each over its bins ascending from +0,
-// then smcmc_et_integral's order); the owners keep ws * own[r] in kEsOwn registers more and start again from +0 over the
-// background events.  `hist`: the owners' bins in `term` (entries from 3 nbins on +0).
-__device__ __forceinline__ double pw_event_template_integral(const double* term, int nbins) {
-    double sum[3];
-    for (int h = 0; h < 3; ++h) {
+// SMCMC_LIKE_EVENT_TEMPLATE and SMCMC_LIKE_EVENT_SHAPE for one chain on 64 lanes: the scan above over the signal events,
+// the owners' bins published to `term` and summed by every lane alike to the class integral (NH histograms, each over its
+// bins ascending from +0, then smcmc_et_integral's order); the owners keep ws * own[r] in as many registers more and start
+// again from +0 over the background events.  `hist`: the owners' bins in `term` (entries from NH nbins on +0).
+template <int NH>
+__device__ __forceinline__ double pw_event_integral(const double* term, int nbins) {
+    double sum[NH];
+    for (int h = 0; h < NH; ++h) {
         const double* th = term + h * nbins;
         double v = 0.0;
         for (int b0 = 0; b0 < nbins; b0 += kPwBatch) {
             double t[kPwBatch];
 #pragma unroll
-            for (int u = 0; u < kPwBatch; ++u) t[u] = th[b0 + u];      // (below 3 nbins + kPwBatch <= kEsOwn * 64: in range)
+            for (int u = 0; u < kPwBatch; ++u) t[u] = th[b0 + u];      // (below NH nbins + kPwBatch <= the owners' registers * 64: in range)
 #pragma unroll
             for (int u = 0; u < kPwBatch; ++u)
                 if (b0 + u < nbins) v += t[u];
         }
         sum[h] = v;
     }
-    return smcmc_et_integral(sum[0], sum[1], sum[2]);
-}
-__device__ __forceinline__ double pw_event_template(const double* p, const double* __restrict__ like) {
-    __shared__ int post_bin[kWave];
-    __shared__ __attribute__((aligned(16))) double post_w[kWave];
-    __shared__ __attribute__((aligned(16))) double term[kEsOwn * kWave];
-    const int lane = threadIdx.x;
-    const cptr_f64 prm = as_const(like);
-    const int nev = (int)prm[SMCMC_ES_H_NEVENTS], nbins = (int)prm[SMCMC_ES_H_NBINS], nsig = (int)prm[SMCMC_ES_H_NSIGNAL];
-    const double xmin = prm[SMCMC_ES_H_XMIN], xmax = prm[SMCMC_ES_H_XMAX], range = prm[SMCMC_ES_H_RANGE];
-    const double cut = prm[SMCMC_ES_H_CUT];
-    double pt[SMCMC_ES_DIM];
-#pragma unroll
-    for (int i = 0; i < SMCMC_ES_DIM; ++i) pt[i] = p[i];
-    smcmc_es_scalars s;
-    smcmc_et_point_scalars(pt, prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF], prm[SMCMC_ES_H_TAN_FAKES],
-                           prm[SMCMC_ES_H_TAN_EFF], &s);
-    const int rows = 3 * nbins;
-    const int nown = (rows + kWave - 1) / kWave;        // registers of `own` in use (wave-uniform)
-    const double* const ev = like + SMCMC_ES_HEADER + rows;
-    double own[kEsOwn], share[kEsOwn];
-    double wb = 0.0;
-#pragma nounroll
-    for (int c = 0; c < 2; ++c) {                       // (one copy of the scan's code)
-#pragma unroll
-        for (int r = 0; r < kEsOwn; ++r) own[r] = 0.0;
-        pw_event_sample_range(ev, c ? nsig : 0, c ? nev : nsig, s, nbins, nown, xmin, xmax, range, cut, post_bin, post_w, lane, own);
-        __syncthreads();                                // (every lane is done with the integral before)
-#pragma unroll
-        for (int r = 0; r < kEsOwn; ++r) {
-            const int k = lane + kWave * r;
-            term[k] = (k < rows) ? own[r] : 0.0;
-        }
-        __syncthreads();
-        const double norm = smcmc_et_norm(c ? pt[1] : pt[0], pw_event_template_integral(term, nbins));
-        if (c == 0) {
-#pragma unroll
-            for (int r = 0; r < kEsOwn; ++r) share[r] = smcmc_et_mc_signal(norm, own[r]);
-        } else {
-            wb = norm;
-        }
-    }
-    __syncthreads();                                    // the background's integral is read
-#pragma unroll
-    for (int r = 0; r < kEsOwn; ++r) {
-        const int k = lane + kWave * r;
-        term[k] = (k < rows) ? smcmc_es_bin_term(like[SMCMC_ES_HEADER + k], smcmc_et_mc(share[r], wb, own[r])) : 0.0;
-    }
-    __syncthreads();
-    // example2/FakeLikelihood.H:64-89: the bins of Close, Separated, DecayTag, in that order; then the penalties
-    return smcmc_et_penalties(pw_event_sample_sum(term, rows), pt);
-}
-
-// SMCMC_LIKE_EVENT_SHAPE (smcmc.h; the arithmetic is include/smcmc_event_shape.h) for one chain on 64 lanes: the event
-// template's two scans over four histograms laid end to end, the owners' bins in kEshOwn registers.  The lane that
-// corrects an event also forms its exp(shape); the segment k differs from lane to lane, so the control values and slopes
-// of both shapes sit in a small LDS table, written once per evaluation from the point in LDS:
-//   [0, 11) yB   [11, 21) slopeB   [21, 34) yS   [34, 46) slopeS
-constexpr int kEshOwn = (4 * SMCMC_EVENT_SHAPE_MAX_BINS + kWave - 1) / kWave;
-static_assert(kEshOwn <= kEsOwn, "pw_event_sample_scan takes the owners' registers as an array of kEsOwn");
-static_assert(kEshOwn * kWave >= 4 * SMCMC_EVENT_SHAPE_MAX_BINS + kPwBatch, "the last batch of the bin sum reads inside `term`");
-constexpr int kEshTabB = 0, kEshTabS = 2 * SMCMC_ESH_NB - 1, kEshTab = 2 * SMCMC_ESH_NB - 1 + 2 * SMCMC_ESH_NS - 1;
-// pw_event_sample_range with the weight multiplied by exp(shape); y: the control values of the pass's class in LDS,
-// nctl of them, and behind them the nctl - 1 slopes
-__device__ __forceinline__ void pw_event_shape_range(const double* const ev, const int ebeg, const int nev, const smcmc_es_scalars& s,
-                                                     const int nbins, const int nown, const double xmin, const double xmax,
-                                                     const double range, const double cut_very_close, const double cut_close,
-                                                     const double* y, const int nctl, int* post_bin, double* post_w,
-                                                     const int lane, double (&own)[kEsOwn]) {
-    for (int e0 = ebeg; e0 < nev; e0 += kWave) {
-        const int e = e0 + lane;
-        int b = -1;
-        double w = 0.0;
-        if (e < nev) {
-            const double* q = ev + (size_t)e * SMCMC_ESH_EVENT;
-            const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], dx = q[6];
-            const int cls = (int)q[4];
-            int k = (int)q[5];
-            k = (k < 0) ? 0 : (k > nctl - 1) ? nctl - 1 : k;            // (esh_pack's range; the table is not read outside it)
-            const int ks = (k < nctl - 1) ? k : nctl - 2;               // (a clamped event at the last centre has no slope)
-            const bool clamped = q[7] != 0.0;
-            b = smcmc_esh_event_bin(q0, q1, q2, q3, cls >> 1, cls & 1, &s, nbins, xmin, xmax, range, cut_very_close, cut_close);
-            const double cw = (cls == 0) ? s.weight[0] : (cls == 1) ? s.weight[1] : (cls == 2) ? s.weight[2] : s.weight[3];
-            w = smcmc_esh_weight(cw, smcmc_esh_shape(y[k], y[nctl + ks], dx, clamped));
-        }
-        __syncthreads();                                // the scan of the batch before is over
-        post_bin[lane] = b;
-        post_w[lane] = w;
-        __syncthreads();
-        switch (nown) {
-            case 1: pw_event_sample_scan<1>(post_bin, post_w, lane, own); break;
-            case 2: pw_event_sample_scan<(kEshOwn < 2 ? kEshOwn : 2)>(post_bin, post_w, lane, own); break;
-            case 3: pw_event_sample_scan<(kEshOwn < 3 ? kEshOwn : 3)>(post_bin, post_w, lane, own); break;
-            default: pw_event_sample_scan<kEshOwn>(post_bin, post_w, lane, own); break;     // (50 bins: 200 rows)
-        }
-    }
-}
-// `hist`: the owners' bins in `term` (entries from 4 nbins on +0)
-__device__ __forceinline__ double pw_event_shape_integral(const double* term, int nbins) {
-    double sum[4];
-    for (int h = 0; h < 4; ++h) {
-        const double* th = term + h * nbins;
-        double v = 0.0;
-        for (int b0 = 0; b0 < nbins; b0 += kPwBatch) {
-            double t[kPwBatch];
-#pragma unroll
-            for (int u = 0; u < kPwBatch; ++u) t[u] = th[b0 + u];      // (below 4 nbins + kPwBatch <= kEshOwn * 64: in range)
-#pragma unroll
-            for (int u = 0; u < kPwBatch; ++u)
-                if (b0 + u < nbins) v += t[u];
-        }
-        sum[h] = v;
-    }
-    return smcmc_esh_integral(sum[0], sum[1], sum[2], sum[3]);
+    return smcmc_et_integral(sum, NH);
 }
 // TFakeGP::GetPenalty of the n control values y in LDS, by every lane alike
 __device__ __forceinline__ double pw_event_shape_penalty(const double* y, const cptr_f64 kinv, int n) {
@@ -335,25 +250,33 @@ __device__ __forceinline__ double pw_event_shape_penalty(const double* y, const 
     }
     return penalty;
 }
-__device__ __forceinline__ double pw_event_shape(const double* p, const double* __restrict__ like) {
+// The two scans, the bin sum (example2/FakeLikelihood.H:64-89, example3/FakeLikelihood.H:68-102: the bins of [VeryClose,]
+// Close, Separated, DecayTag, in that order) and the penalties.  What the shape adds: the segment k of an event's shape
+// differs from lane to lane, so the control values and slopes of both shapes sit in a small LDS table, written once per
+// evaluation from the point in LDS:
+//   [0, 11) yB   [11, 21) slopeB   [21, 34) yS   [34, 46) slopeS
+constexpr int kEshTabB = 0, kEshTabS = 2 * SMCMC_ESH_NB - 1, kEshTab = 2 * SMCMC_ESH_NB - 1 + 2 * SMCMC_ESH_NS - 1;
+template <bool SHAPE>
+__device__ __forceinline__ double pw_event_two_scan(const double* p, const double* __restrict__ like) {
+    constexpr int DIM = SHAPE ? SMCMC_ESH_DIM : SMCMC_ES_DIM, NH = SHAPE ? 4 : 3, OWN = SHAPE ? kEshOwn : kEsOwn;
     __shared__ int post_bin[kWave];
     __shared__ __attribute__((aligned(16))) double post_w[kWave];
-    __shared__ __attribute__((aligned(16))) double term[kEshOwn * kWave];
-    __shared__ __attribute__((aligned(16))) double tab[kWave];      // (kEshTab = 46 entries in use)
+    __shared__ __attribute__((aligned(16))) double term[OWN * kWave];
+    __shared__ __attribute__((aligned(16))) double tab[SHAPE ? kWave : 1];    // (the shape's: kEshTab = 46 entries in use)
     static_assert(kEshTab <= kWave, "a lane an entry");
     const int lane = threadIdx.x;
     const cptr_f64 prm = as_const(like);
     const int nev = (int)prm[SMCMC_ES_H_NEVENTS], nbins = (int)prm[SMCMC_ES_H_NBINS], nsig = (int)prm[SMCMC_ES_H_NSIGNAL];
     const double xmin = prm[SMCMC_ES_H_XMIN], xmax = prm[SMCMC_ES_H_XMAX], range = prm[SMCMC_ES_H_RANGE];
-    const double cut_close = prm[SMCMC_ES_H_CUT], cut_very_close = prm[SMCMC_ESH_H_CUT_VERY_CLOSE];
-    double pt[SMCMC_ESH_DIM];
+    const double cut = prm[SMCMC_ES_H_CUT], cut_very_close = SHAPE ? prm[SMCMC_ESH_H_CUT_VERY_CLOSE] : 0.0;
+    double pt[DIM];
 #pragma unroll
-    for (int i = 0; i < SMCMC_ESH_DIM; ++i) pt[i] = p[i];
+    for (int i = 0; i < DIM; ++i) pt[i] = p[i];
     smcmc_es_scalars s;
-    smcmc_esh_point_scalars(pt, prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF], prm[SMCMC_ES_H_TAN_FAKES],
-                            prm[SMCMC_ES_H_TAN_EFF], &s);
-    // the tables: lane l forms entry l (a control value, or a slope from the two control values beside it)
-    {
+    if constexpr (SHAPE) {
+        smcmc_esh_point_scalars(pt, prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF], prm[SMCMC_ES_H_TAN_FAKES],
+                                prm[SMCMC_ES_H_TAN_EFF], &s);
+        // the tables: lane l forms entry l (a control value, or a slope from the two control values beside it)
         const bool sig = lane >= kEshTabS;
         const int l = sig ? lane - kEshTabS : lane;
         const int n = sig ? SMCMC_ESH_NS : SMCMC_ESH_NB;
@@ -367,45 +290,52 @@ __device__ __forceinline__ double pw_event_shape(const double* p, const double* 
         __syncthreads();                                // (every lane is done with the tables of the evaluation before)
         tab[lane] = (lane < kEshTab) ? v : 0.0;
         __syncthreads();
+    } else {
+        smcmc_et_point_scalars(pt, prm[SMCMC_ES_H_TRUE_FAKES], prm[SMCMC_ES_H_TRUE_EFF], prm[SMCMC_ES_H_TAN_FAKES],
+                               prm[SMCMC_ES_H_TAN_EFF], &s);
     }
-    const int rows = 4 * nbins;
+    const int rows = NH * nbins;
     const int nown = (rows + kWave - 1) / kWave;        // registers of `own` in use (wave-uniform)
-    const double* const ev = like + SMCMC_ESH_EVENTS(nbins);
-    double own[kEsOwn], share[kEshOwn];
+    const double* const ev = like + (SHAPE ? SMCMC_ESH_EVENTS(nbins) : SMCMC_ES_HEADER + rows);
+    double own[kEsOwn], share[OWN];
     double wb = 0.0;
 #pragma nounroll
     for (int c = 0; c < 2; ++c) {                       // (one copy of the scan's code)
 #pragma unroll
         for (int r = 0; r < kEsOwn; ++r) own[r] = 0.0;
-        pw_event_shape_range(ev, c ? nsig : 0, c ? nev : nsig, s, nbins, nown, xmin, xmax, range, cut_very_close, cut_close,
-                             tab + (c ? kEshTabB : kEshTabS), c ? SMCMC_ESH_NB : SMCMC_ESH_NS, post_bin, post_w, lane, own);
+        pw_event_range<SHAPE>(ev, c ? nsig : 0, c ? nev : nsig, s, nbins, nown, xmin, xmax, range, cut_very_close, cut,
+                              SHAPE ? tab + (c ? kEshTabB : kEshTabS) : nullptr, c ? SMCMC_ESH_NB : SMCMC_ESH_NS, post_bin, post_w,
+                              lane, own);
         __syncthreads();                                // (every lane is done with the integral before)
 #pragma unroll
-        for (int r = 0; r < kEshOwn; ++r) {
+        for (int r = 0; r < OWN; ++r) {
             const int k = lane + kWave * r;
             term[k] = (k < rows) ? own[r] : 0.0;
         }
         __syncthreads();
-        const double norm = smcmc_et_norm(c ? pt[1] : pt[0], pw_event_shape_integral(term, nbins));
+        const double norm = smcmc_et_norm(c ? pt[1] : pt[0], pw_event_integral<NH>(term, nbins));
         if (c == 0) {
 #pragma unroll
-            for (int r = 0; r < kEshOwn; ++r) share[r] = smcmc_et_mc_signal(norm, own[r]);
+            for (int r = 0; r < OWN; ++r) share[r] = smcmc_et_mc_signal(norm, own[r]);
         } else {
             wb = norm;
         }
     }
     __syncthreads();                                    // the background's integral is read
 #pragma unroll
-    for (int r = 0; r < kEshOwn; ++r) {
+    for (int r = 0; r < OWN; ++r) {
         const int k = lane + kWave * r;
         term[k] = (k < rows) ? smcmc_es_bin_term(like[SMCMC_ES_HEADER + k], smcmc_et_mc(share[r], wb, own[r])) : 0.0;
     }
     __syncthreads();
-    // example3/FakeLikelihood.H:68-102: the bins of VeryClose, Close, Separated, DecayTag, in that order; then the penalties
     const double logl = pw_event_sample_sum(term, rows);
-    const double pen_b = pw_event_shape_penalty(tab + kEshTabB, prm + SMCMC_ESH_KINV_B(nbins), SMCMC_ESH_NB);
-    const double pen_s = pw_event_shape_penalty(tab + kEshTabS, prm + SMCMC_ESH_KINV_S(nbins), SMCMC_ESH_NS);
-    return smcmc_esh_penalties(logl, pt, pen_b, pen_s);
+    if constexpr (SHAPE) {
+        const double pen_b = pw_event_shape_penalty(tab + kEshTabB, prm + SMCMC_ESH_KINV_B(nbins), SMCMC_ESH_NB);
+        const double pen_s = pw_event_shape_penalty(tab + kEshTabS, prm + SMCMC_ESH_KINV_S(nbins), SMCMC_ESH_NS);
+        return smcmc_esh_penalties(logl, pt, pen_b, pen_s);
+    } else {
+        return smcmc_et_penalties(logl, pt[0], pt[1], pt[6], pt[7], pt[8]);
+    }
 }
 
 // log L of the point in LDS (p[0 .. D)), in the reference's summation order: the arithmetic of serial_loglike<LIKE, true>
@@ -456,9 +386,9 @@ __device__ __forceinline__ double pw_loglike(const double* p, double pi, int D, 
     } else if constexpr (LIKE == SMCMC_LIKE_EVENT_SAMPLE) {
         lsum = pw_event_sample(p, like);
     } else if constexpr (LIKE == SMCMC_LIKE_EVENT_TEMPLATE) {
-        lsum = pw_event_template(p, like);
+        lsum = pw_event_two_scan<false>(p, like);
     } else if constexpr (LIKE == SMCMC_LIKE_EVENT_SHAPE) {
-        lsum = pw_event_shape(p, like);
+        lsum = pw_event_two_scan<true>(p, like);
     } else if constexpr (LIKE == SMCMC_LIKE_CONSTRAINED) {
         // example4/TConstrainedLikelihood.H:26-46; like = {SummedValues, SummedConstraint, Expected[D], Prior[D]}
         double sum = pw_ordered_sum<DMAX>(pi, D, scratch);

@@ -73,32 +73,30 @@ class Engine(TraceReducers):
         except Exception:
             pass
 
+    def _event_histograms(self, who, like, name, evaluate, point):
+        """(hist, logl) of one of the likelihoods over a simulated event sample, from its host evaluator"""
+        if self.likelihood != like or self._likelihood_params is None:
+            raise SmcmcError(_capi.ERR_LOGIC, "%s needs %s and its parameters" % (who, name))
+        logl, hist = evaluate(self._likelihood_params, point, histograms=True)
+        return hist, logl
+
     def EventSampleHistograms(self, point):
         """LIKE_EVENT_SAMPLE: the three simulated histograms [3][nbins] (Close, Separated, DecayTag) at `point`, as
         FakeLikelihood::WriteSimulation (example/FakeLikelihood.H:173-179) fills them, and the log-likelihood there:
         (hist, logl).  Evaluated on the host by smcmc_event_sample_evaluate, bit for bit what the device sums."""
-        if self.likelihood != LIKE_EVENT_SAMPLE or self._likelihood_params is None:
-            raise SmcmcError(_capi.ERR_LOGIC, "EventSampleHistograms needs LIKE_EVENT_SAMPLE and its parameters")
-        logl, hist = event_sample_evaluate(self._likelihood_params, point, histograms=True)
-        return hist, logl
+        return self._event_histograms("EventSampleHistograms", LIKE_EVENT_SAMPLE, "LIKE_EVENT_SAMPLE", event_sample_evaluate, point)
 
     def EventTemplateHistograms(self, point):
         """LIKE_EVENT_TEMPLATE: the expectation [3][nbins] (Close, Separated, DecayTag) at `point`, as
         FakeLikelihood::WriteSimulation (example2/FakeLikelihood.H:201-207) fills it, and the log-likelihood there:
         (hist, logl).  Evaluated on the host by smcmc_event_template_evaluate, bit for bit what the device sums."""
-        if self.likelihood != LIKE_EVENT_TEMPLATE or self._likelihood_params is None:
-            raise SmcmcError(_capi.ERR_LOGIC, "EventTemplateHistograms needs LIKE_EVENT_TEMPLATE and its parameters")
-        logl, hist = event_template_evaluate(self._likelihood_params, point, histograms=True)
-        return hist, logl
+        return self._event_histograms("EventTemplateHistograms", LIKE_EVENT_TEMPLATE, "LIKE_EVENT_TEMPLATE", event_template_evaluate, point)
 
     def EventShapeHistograms(self, point):
         """LIKE_EVENT_SHAPE: the expectation [4][nbins] (VeryClose, Close, Separated, DecayTag) at `point`, as
         FakeLikelihood::WriteSimulation (example3/FakeLikelihood.H:232-239) fills it, and the log-likelihood there:
         (hist, logl).  Evaluated on the host by smcmc_event_shape_evaluate, bit for bit what the device sums."""
-        if self.likelihood != LIKE_EVENT_SHAPE or self._likelihood_params is None:
-            raise SmcmcError(_capi.ERR_LOGIC, "EventShapeHistograms needs LIKE_EVENT_SHAPE and its parameters")
-        logl, hist = event_shape_evaluate(self._likelihood_params, point, histograms=True)
-        return hist, logl
+        return self._event_histograms("EventShapeHistograms", LIKE_EVENT_SHAPE, "LIKE_EVENT_SHAPE", event_shape_evaluate, point)
 
     def set_stream(self, stream):
         """stream: a raw hipStream_t value (e.g. torch.cuda.current_stream().cuda_stream)."""
@@ -436,21 +434,49 @@ class PosteriorMoments:
         return self.s2 / self.n - np.outer(mu, mu)
 
 
-def event_sample_evaluate(params, point, histograms=False):
-    """smcmc_event_sample_evaluate: LIKE_EVENT_SAMPLE at `point` (9 values) on the host, for the exposure ratio and the
-    simulated histograms -- never to step a chain.  Returns logL, or (logL, hist[3][nbins]) with histograms=True."""
+def _event_evaluate(entry, what, dim, nh, max_bins, nparts, params, point, histograms, parts):
+    """One of the three host evaluators of the likelihoods over a simulated event sample, `entry` of the library: nh
+    histograms, a point of `dim` values, nparts doubles of intermediate stages (0: the entry takes none).  Returns
+    (logL, nbins, hist or None, raw parts or None)."""
     lib = _capi.load()
     prm = _f64(params).ravel()
     pt = _f64(point).ravel()
-    if pt.size != 9:
-        raise SmcmcError(_capi.ERR_INVALID, "the event sample has nine parameters")
-    nbins = int(prm[1]) if prm.size > 1 and np.isfinite(prm[1]) and 1 <= prm[1] <= _capi.EVENT_SAMPLE_MAX_BINS else 1
-    hist = np.zeros((3, nbins))
+    if pt.size != dim:
+        raise SmcmcError(_capi.ERR_INVALID, what)
+    nbins = int(prm[1]) if prm.size > 1 and np.isfinite(prm[1]) and 1 <= prm[1] <= max_bins else 1
+    hist = np.zeros((nh, nbins))
+    raw = np.zeros(2 * nh * nbins + nparts)
     logl = C.c_double(0.0)
-    st = lib.smcmc_event_sample_evaluate(_ptr(prm), prm.size, _ptr(pt), C.byref(logl), _ptr(hist) if histograms else None)
+    args = [_ptr(prm), prm.size, _ptr(pt), C.byref(logl), _ptr(hist) if histograms else None]
+    if nparts:
+        args.append(_ptr(raw) if parts else None)
+    st = getattr(lib, entry)(*args)
     if st != _capi.OK:
         raise SmcmcError(st, lib.smcmc_event_sample_last_error().decode() or lib.smcmc_status_string(st).decode())
-    return (logl.value, hist) if histograms else logl.value
+    return logl.value, nbins, hist if histograms else None, raw if parts else None
+
+
+def _event_result(logl, nbins, nh, hist, raw, extra=None):
+    """(logL, hist, parts) without what was not asked for; parts: S, B, IS, IB, ws, wb and what extra(tail) adds"""
+    out = [logl]
+    if hist is not None:
+        out.append(hist)
+    if raw is not None:
+        t = raw[2 * nh * nbins:]
+        d = {"S": raw[:nh * nbins].reshape(nh, nbins).copy(), "B": raw[nh * nbins:2 * nh * nbins].reshape(nh, nbins).copy(),
+             "IS": float(t[0]), "IB": float(t[1]), "ws": float(t[2]), "wb": float(t[3])}
+        if extra:
+            d.update(extra(t))
+        out.append(d)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def event_sample_evaluate(params, point, histograms=False):
+    """smcmc_event_sample_evaluate: LIKE_EVENT_SAMPLE at `point` (9 values) on the host, for the exposure ratio and the
+    simulated histograms -- never to step a chain.  Returns logL, or (logL, hist[3][nbins]) with histograms=True."""
+    logl, nbins, hist, _ = _event_evaluate("smcmc_event_sample_evaluate", "the event sample has nine parameters", 9, 3,
+                                           _capi.EVENT_SAMPLE_MAX_BINS, 0, params, point, histograms, False)
+    return _event_result(logl, nbins, 3, hist, None)
 
 
 def event_template_evaluate(params, point, histograms=False, parts=False):
@@ -458,27 +484,9 @@ def event_template_evaluate(params, point, histograms=False, parts=False):
     Returns logL; with histograms=True also the expectation mc[3][nbins] before the clamp; with parts=True also a dict of
     the intermediate stages: S[3][nbins], B[3][nbins] (the signal's and the background's histograms), IS, IB (their
     integrals), ws, wb (the two normalisations).  The order is (logL, hist, parts), without what was not asked for."""
-    lib = _capi.load()
-    prm = _f64(params).ravel()
-    pt = _f64(point).ravel()
-    if pt.size != 9:
-        raise SmcmcError(_capi.ERR_INVALID, "the event template has nine parameters")
-    nbins = int(prm[1]) if prm.size > 1 and np.isfinite(prm[1]) and 1 <= prm[1] <= _capi.EVENT_SAMPLE_MAX_BINS else 1
-    hist = np.zeros((3, nbins))
-    raw = np.zeros(6 * nbins + 4)
-    logl = C.c_double(0.0)
-    st = lib.smcmc_event_template_evaluate(_ptr(prm), prm.size, _ptr(pt), C.byref(logl), _ptr(hist) if histograms else None,
-                                           _ptr(raw) if parts else None)
-    if st != _capi.OK:
-        raise SmcmcError(st, lib.smcmc_event_sample_last_error().decode() or lib.smcmc_status_string(st).decode())
-    out = [logl.value]
-    if histograms:
-        out.append(hist)
-    if parts:
-        out.append({"S": raw[:3 * nbins].reshape(3, nbins).copy(), "B": raw[3 * nbins:6 * nbins].reshape(3, nbins).copy(),
-                    "IS": float(raw[6 * nbins]), "IB": float(raw[6 * nbins + 1]), "ws": float(raw[6 * nbins + 2]),
-                    "wb": float(raw[6 * nbins + 3])})
-    return out[0] if len(out) == 1 else tuple(out)
+    logl, nbins, hist, raw = _event_evaluate("smcmc_event_template_evaluate", "the event template has nine parameters", 9, 3,
+                                             _capi.EVENT_SAMPLE_MAX_BINS, 4, params, point, histograms, parts)
+    return _event_result(logl, nbins, 3, hist, raw)
 
 
 def event_shape_evaluate(params, point, histograms=False, parts=False):
@@ -486,28 +494,10 @@ def event_shape_evaluate(params, point, histograms=False, parts=False):
     Returns logL; with histograms=True also the expectation mc[4][nbins] before the clamp; with parts=True also a dict of
     the intermediate stages: S[4][nbins], B[4][nbins], IS, IB, ws, wb, penB, penS (the two shape penalties) and KinvB[11][11],
     KinvS[13][13] (the inverted kernels).  The order is (logL, hist, parts), without what was not asked for."""
-    lib = _capi.load()
-    prm = _f64(params).ravel()
-    pt = _f64(point).ravel()
-    if pt.size != 31:
-        raise SmcmcError(_capi.ERR_INVALID, "the event shape has 31 parameters")
-    nbins = int(prm[1]) if prm.size > 1 and np.isfinite(prm[1]) and 1 <= prm[1] <= _capi.EVENT_SHAPE_MAX_BINS else 1
-    hist = np.zeros((4, nbins))
-    raw = np.zeros(8 * nbins + 6 + 121 + 169)
-    logl = C.c_double(0.0)
-    st = lib.smcmc_event_shape_evaluate(_ptr(prm), prm.size, _ptr(pt), C.byref(logl), _ptr(hist) if histograms else None,
-                                        _ptr(raw) if parts else None)
-    if st != _capi.OK:
-        raise SmcmcError(st, lib.smcmc_event_sample_last_error().decode() or lib.smcmc_status_string(st).decode())
-    out = [logl.value]
-    if histograms:
-        out.append(hist)
-    if parts:
-        t = raw[8 * nbins:]
-        out.append({"S": raw[:4 * nbins].reshape(4, nbins).copy(), "B": raw[4 * nbins:8 * nbins].reshape(4, nbins).copy(),
-                    "IS": float(t[0]), "IB": float(t[1]), "ws": float(t[2]), "wb": float(t[3]), "penB": float(t[4]),
-                    "penS": float(t[5]), "KinvB": t[6:127].reshape(11, 11).copy(), "KinvS": t[127:296].reshape(13, 13).copy()})
-    return out[0] if len(out) == 1 else tuple(out)
+    logl, nbins, hist, raw = _event_evaluate("smcmc_event_shape_evaluate", "the event shape has 31 parameters", 31, 4,
+                                             _capi.EVENT_SHAPE_MAX_BINS, 6 + 121 + 169, params, point, histograms, parts)
+    return _event_result(logl, nbins, 4, hist, raw, lambda t: {
+        "penB": float(t[4]), "penS": float(t[5]), "KinvB": t[6:127].reshape(11, 11).copy(), "KinvS": t[127:296].reshape(13, 13).copy()})
 
 
 def event_shape_kernel(low, high, n, coherence, sigma=1.0, exponential=False):

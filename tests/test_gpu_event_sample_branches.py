@@ -6,7 +6,7 @@ EventSampleHistograms gives that evaluation's bins.
   pw_event_sample (SMCMC_MODE_PER_CHAIN)   `switch (nown)`: 22 bins case 2, 64 bins case 3 at its upper edge, 65 bins
                                            case 4, 86 and 97 bins the default; 97 bins is also where the ordered bin sum
                                            reads furthest past `rows`; 1, 37, 63 events: less than one batch of 64; 65,
-                                           129: batches plus one
+                                           129: batches plus one; 1 025 chains: the paired form of the kernel
   event_sample_loglike (frozen, pooled)    97 bins: the largest dynamic LDS; 1 bin: three rows and the spare row, where
                                            a batch of four holds every shape of equal indices; 1, 2, 3 events: no full
                                            batch; 5: one and one
@@ -103,6 +103,35 @@ def test_per_chain_wave_kernel_at_the_extreme_points(gpu, oracle, name):
                      mode=gpu.MODE_PER_CHAIN)
     assert eng.Start(_starts(oracle, 3, 79))
     _check_extreme_points(gpu, eng, params, eng.lane("logl"))
+    eng.close()
+
+
+def test_per_chain_wave_kernel_paired_form_above_1024_chains(gpu, oracle):
+    """1 025 chains: the first count at which the per-chain wave kernel is launched in its paired form
+    (perchain_wave_kernel<EVENT_SAMPLE, 4, PAIRED = true>), which no other event test reaches.  65 signal and 2
+    background events: a second batch of 64 that holds one event; 22 bins: 66 rows, two owner registers.  Start, then two
+    steps: every chain's start and accepted likelihood is the host definition at its point, bit for bit and NaN as NaN,
+    and for chains 0, 1 and 1 024 the Python restatement's too."""
+    tref = _load("event_template_ref")                   # (keep_classes: ref.truncate cannot choose the class counts)
+    params = tref.keep_classes(ref.make_sample(oracle, 70, 8, 22, 112), 65, 2)
+    assert tref.class_counts(params) == (65, 2)
+    host, be = Host(gpu, params), ref.deterministic(oracle, gpu)
+    nchains = 1025
+    eng = gpu.Engine(9, nchains=nchains, likelihood=gpu.LIKE_EVENT_SAMPLE, likelihood_params=params, seed=SEED,
+                     mode=gpu.MODE_PER_CHAIN)
+    assert eng.get_param("PERCHAIN_WAVE") == 1.0
+    x0 = np.random.default_rng(80).uniform(-1.0, 1.0, (9, nchains))
+    assert eng.Start(x0)
+    for when, steps in (("start", 0), ("accepted", 2)):
+        if steps:
+            eng.Step(steps)
+        x, logl = eng.GetAccepted(), eng.lane("logl")
+        assert logl.shape == (nchains,)
+        for c in range(nchains):
+            assert tref.same(logl[c], host(x[:, c])), "%s, chain %d" % (when, c)
+        for c in (0, 1, 1024):
+            assert tref.same(logl[c], ref.evaluate(params, x[:, c], be)[0]), "%s, chain %d: the restatement" % (when, c)
+    assert not np.array_equal(x, x0)
     eng.close()
 
 

@@ -101,3 +101,34 @@ def test_per_chain_wave_kernel_class_boundary(gpu, oracle, counts):
     params = tcases.counted(oracle, "per_chain", *counts)
     assert tref.class_counts(params) == counts
     _per_chain(gpu, oracle, params, "%d + %d events" % counts)
+
+
+def test_per_chain_wave_kernel_paired_form_above_1024_chains(gpu, oracle):
+    """1 025 chains: the first count at which the per-chain wave kernel is launched in its paired form
+    (perchain_wave_kernel<EVENT_TEMPLATE, 4, PAIRED = true>), which no other event test reaches.  65 signal and 2
+    background events: a second batch of 64 of the signal's scan that holds one event; 22 bins: 66 rows, two owner
+    registers.  Start, then two steps: every chain's start and accepted likelihood is the host definition at its point,
+    bit for bit and NaN as NaN, and for chains 0, 1 and 1 024 the Python restatement's too."""
+    params = tref.keep_classes(tcases.light_background_first(tref.make_sample(oracle, 70, 8, 22, 112)), 65, 2)
+    assert tref.class_counts(params) == (65, 2)
+    host, be = tcases.Host(gpu, params), ref.deterministic(oracle, gpu)
+    nchains = 1025
+    eng = gpu.Engine(9, nchains=nchains, likelihood=gpu.LIKE_EVENT_TEMPLATE, likelihood_params=params, seed=SEED,
+                     mode=gpu.MODE_PER_CHAIN)
+    assert eng.get_param("PERCHAIN_WAVE") == 1.0
+    x0 = np.random.default_rng(81).uniform(-1.0, 1.0, (9, nchains))
+    total = float(np.sum(params[8:8 + 3 * 22]))             # the two counts: the data's total shared out and jittered
+    x0[0] = 0.4 * total * (1.0 + 0.1 * x0[0])
+    x0[1] = 0.6 * total * (1.0 + 0.1 * x0[1])
+    assert eng.Start(x0)
+    for when, steps in (("start", 0), ("accepted", 2)):
+        if steps:
+            eng.Step(steps)
+        x, logl = eng.GetAccepted(), eng.lane("logl")
+        assert logl.shape == (nchains,)
+        for c in range(nchains):
+            assert tref.same(logl[c], host(x[:, c])), "%s, chain %d" % (when, c)
+        for c in (0, 1, 1024):
+            assert tref.same(logl[c], tref.evaluate(params, x[:, c], be)[0]), "%s, chain %d: the restatement" % (when, c)
+    assert not np.array_equal(x, x0)
+    eng.close()
