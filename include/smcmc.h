@@ -915,6 +915,36 @@ int smcmc_trace_convergence(const double* trace_device, int nslots, int dim, int
                             int nchains_padded, int nsegments, const double* centre, double* chain_sums_device,
                             double* sum, double* sumsq_of_sums, double* within, void* stream);
 
+/* ---- posterior reducer: the event family's histograms over a saved trace ----------
+ * FakeLikelihood::WriteSimulation (example/FakeLikelihood.H:173-179, example2/FakeLikelihood.H:201-207,
+ * example3/FakeLikelihood.H:232-239) writes the simulated histograms at ONE point, and every FakeMCMC.C draws them over the
+ * data after a burn-in or a cycle.  This is that product for every point of a saved trace: the posterior mean and spread of
+ * every histogram bin, the band around the prediction.
+ *   likelihood   SMCMC_LIKE_EVENT_SAMPLE, SMCMC_LIKE_EVENT_TEMPLATE or SMCMC_LIKE_EVENT_SHAPE; dim = 9, 9 or 31 is implied
+ *   params       that likelihood's flat parameter array [count], under the rules of smcmc_set_likelihood_params
+ *   rows         NH * nbins, NH = 3, 3 or 4: the histograms laid end to end in the order of the host evaluators' `hist`
+ * Over trace_device[slot][dim_stride][nchains_padded] (as smcmc_step_save wrote it; rows >= dim and lanes >= nchains are
+ * never read into a result): for every slot t and live chain c < nchains, h[t][.][c] and logl[t][c] are `hist` and `*logl`
+ * of the likelihood's host evaluator (smcmc_event_sample_evaluate, _template_, _shape_) at x[t][0 .. dim)[c], bit for bit,
+ * NaN as NaN -- the bin contents for the event sample, the expectation before the clamp for the other two.  With
+ * y = h[t][r][c] - centre[r] (`centre`: [rows] host; NULL = the origin):
+ *   sum[r]   = sum_{t, c < nchains} y
+ *   sumsq[r] = sum_{t, c < nchains} y * y       the product rounded once, then added (un-fused, as everywhere in the family)
+ * Host outputs [rows] and raw sums so that ranks can add theirs; the number of terms is nslots * nchains.  A point that
+ * makes a class's integral 0 gives NaN histograms on the host and here, and the NaN goes into its rows' sums.
+ * hist_device: optional device output [slot][rows][nchains_padded] that receives h itself, lanes >= nchains +0.0: the raw
+ * material of bin-to-bin covariances and per-bin quantiles.  logl_device: optional device output [slot][nchains_padded],
+ * the layout of smcmc_step_save's save_logl, likewise.
+ * Fixed summation order (smcmc_event_predictive.hip states it): the same bits on every run, a function of (params, trace,
+ * centre, nslots, nchains) alone -- not of whether the optional outputs are asked for, nor of what the padding lanes hold.
+ * SMCMC_ERR_INVALID, with nothing launched and nothing written: another likelihood; a parameter array that breaks a rule
+ * (the text through smcmc_event_sample_last_error, as the evaluators give it); nslots < 1, dim_stride < dim, nchains < 1,
+ * nchains_padded < nchains or not a multiple of 64, trace_device NULL; sum or sumsq NULL.  SMCMC_ERR_NO_DEVICE without a
+ * GPU, checked after all of these.  `stream` is a hipStream_t or NULL. */
+int smcmc_event_predictive_sums(int likelihood, const double* params, int count, const double* trace_device, int nslots,
+                                int dim_stride, int nchains, int nchains_padded, const double* centre, double* hist_device,
+                                double* logl_device, double* sum, double* sumsq, void* stream);
+
 /* ---- the Gaussian stand-in chain of a mean and a covariance ---------------------
  * CholeskyChain.C:18-66: covariance = U^T U with U upper triangular (:39-46; here the row-ordered routine the adaptive
  * proposal uses, a pivot that is not positive and finite is SMCMC_ERR_RUNTIME and nothing is launched or written, where

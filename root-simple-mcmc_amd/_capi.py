@@ -221,6 +221,8 @@ SIGNATURES = {
     "smcmc_trace_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_void_p]),
     "smcmc_trace_convergence": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_void_p,
                                           _dp, _dp, _dp, C.c_void_p]),
+    "smcmc_event_predictive_sums": (C.c_int, [C.c_int, _dp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
+                                              C.c_void_p, C.c_void_p, _dp, _dp, C.c_void_p]),
     "smcmc_cholesky_chain": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
                                        C.c_void_p, _dp, C.c_void_p]),
 }

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "smcmc.h"
+#include "smcmc_event_sample_error.hpp"
 #include "smcmc_event_sample_host.hpp"
 
 namespace {
@@ -32,6 +33,8 @@ int es_prepare(const char* entry, int likelihood, const double* params, int coun
     return SMCMC_OK;
 }
 }
+
+void smcmc::es_set_last_error(const std::string& text) { es_error = text; }
 
 extern "C" int smcmc_event_sample_evaluate(const double* params, int count, const double* point, double* logl, double* hist) {
     std::vector<double> packed;

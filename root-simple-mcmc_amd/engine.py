@@ -15,7 +15,8 @@ from ._capi import (LIKE_ASYM, LIKE_CONSTRAINED, LIKE_EVENT_SAMPLE, LIKE_EVENT_S
                     SmcmcError)
 # the reducers over a saved trace live in trace.py; their names stay importable from here
 from .trace import (Autocorrelation, AutocorrelationGrid, AutocorrelationPlan, Convergence, MacroAutocorrelation, Marginals,  # noqa: F401
-                    TraceMoments, TraceReducers, autocorrelation_plan, cholesky_chain, _f64, _ptr)
+                    PosteriorPredictive, TraceMoments, TraceReducers, autocorrelation_plan, cholesky_chain, event_predictive,
+                    _f64, _ptr)
 
 
 class Engine(TraceReducers):
@@ -97,6 +98,19 @@ class Engine(TraceReducers):
         FakeLikelihood::WriteSimulation (example3/FakeLikelihood.H:232-239) fills it, and the log-likelihood there:
         (hist, logl).  Evaluated on the host by smcmc_event_shape_evaluate, bit for bit what the device sums."""
         return self._event_histograms("EventShapeHistograms", LIKE_EVENT_SHAPE, "LIKE_EVENT_SHAPE", event_shape_evaluate, point)
+
+    def PosteriorPredictive(self, trace_ptr, nslots, centre=None, histograms_ptr=None, logl_ptr=None, stream=0):
+        """LIKE_EVENT_SAMPLE, _TEMPLATE, _SHAPE: the simulated histograms of the engine's likelihood at every point of a
+        trace StepSave wrote, taken on the device (smcmc_event_predictive_sums) and summed per bin about `centre`
+        ([NH][nbins]; default: the origin): WriteSimulation over the whole posterior, where the *Histograms methods
+        above serve one point.  histograms_ptr / logl_ptr: optional device memory [nslots][NH nbins][nchains_padded] /
+        [nslots][nchains_padded] that receives every point's histograms / log-likelihood.  Returns a
+        PosteriorPredictive: mean and spread per bin, the band around the prediction."""
+        if self.likelihood not in (LIKE_EVENT_SAMPLE, LIKE_EVENT_TEMPLATE, LIKE_EVENT_SHAPE) or self._likelihood_params is None:
+            raise SmcmcError(_capi.ERR_LOGIC, "PosteriorPredictive needs LIKE_EVENT_SAMPLE, LIKE_EVENT_TEMPLATE or "
+                                              "LIKE_EVENT_SHAPE and its parameters")
+        return event_predictive(self.likelihood, self._likelihood_params, trace_ptr, nslots, self._trace_dim_stride,
+                                self.nchains, self.nchains_padded, centre, histograms_ptr, logl_ptr, stream, _lib=self._lib)
 
     def set_stream(self, stream):
         """stream: a raw hipStream_t value (e.g. torch.cuda.current_stream().cuda_stream)."""

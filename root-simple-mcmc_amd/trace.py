@@ -5,7 +5,9 @@ dim_padded rows per slot, HmcEngine.StepSave / copy_positions and VaatEngine.ste
 reducers of the HIP library (smcmc_autocorrelation_sums, smcmc_autocorrelation_grid_sums, smcmc_trace_ranges,
 smcmc_marginal_histograms, smcmc_trace_moments, smcmc_trace_convergence; include/smcmc.h) take any of them.  The result
 classes are host-side numpy over the raw sums and have nothing to do with any engine; `TraceReducers` gives an engine
-class the six methods that call the library on a trace of its own layout.
+class the six methods that call the library on a trace of its own layout.  `event_predictive` and its result,
+`PosteriorPredictive`, are the seventh reducer (smcmc_event_predictive_sums): it needs a likelihood over a simulated event
+sample besides the trace, so only Engine, the one engine that serves that family, has a method for it.
 """
 import ctypes as C
 
@@ -616,6 +618,104 @@ def _convergence(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchain
                                       nsegments, None if c is None else _ptr(c), None, _ptr(total), _ptr(sumsq),
                                       _ptr(within), C.c_void_p(int(stream))))
     return Convergence(total, sumsq, within, nslots // nsegments, nsegments * nchains, c)
+
+
+class PosteriorPredictive:
+    """The posterior-predictive histograms of a saved trace under one of the likelihoods over a simulated event sample
+    (LIKE_EVENT_SAMPLE, _TEMPLATE, _SHAPE): what FakeLikelihood::WriteSimulation writes at one point, over every point,
+    from the raw sums of smcmc_event_predictive_sums about `centre`: sum[h][b] = sum y, sumsq[h][b] = sum y y,
+    y = hist - centre, over n = nslots * nchains points.
+      names    the histograms: ("Close", "Separated", "DecayTag"), for the shape "VeryClose" first
+      data     [NH][nbins], the observed histograms the simulation is drawn over (the parameter array's)
+      mean     [NH][nbins], centre + sum / n
+      spread   [NH][nbins], sqrt(sumsq / n - (sum / n)^2): the band around the prediction (about a centre near the mean,
+               e.g. the mean of one earlier pass, the difference cancels less)
+    Sums of several ranks add (`+`): the right operand is re-centred on the left one's centre first."""
+
+    NAMES = ("VeryClose", "Close", "Separated", "DecayTag")
+
+    def __init__(self, total, sumsq, nslots, nchains, data, centre=None):
+        self.data = _f64(data).copy()
+        if self.data.ndim != 2 or self.data.shape[0] not in (3, 4) or self.data.shape[1] < 1:
+            raise ValueError("data must be [3][nbins] or [4][nbins]")
+        shape = self.data.shape
+        total, sumsq = _f64(total), _f64(sumsq)
+        centre = np.zeros(shape) if centre is None else _f64(centre)
+        if total.size != self.data.size or sumsq.size != self.data.size or centre.size != self.data.size:
+            raise ValueError("sum, sumsq and centre must hold one value per bin of data[NH][nbins]")
+        self.sum, self.sumsq, self.centre = total.reshape(shape).copy(), sumsq.reshape(shape).copy(), centre.reshape(shape).copy()
+        self.nslots, self.nchains = int(nslots), int(nchains)
+        self.names = self.NAMES[4 - shape[0]:]
+
+    @property
+    def n(self):
+        return float(self.nslots) * float(self.nchains)
+
+    def about(self, centre):
+        """The same sums taken about another point: with s = old centre - new centre, y' = y + s."""
+        centre = _f64(centre)
+        if centre.size != self.data.size:
+            raise ValueError("centre must hold one value per bin of data[NH][nbins]")
+        centre = centre.reshape(self.data.shape)
+        s, n = self.centre - centre, self.n
+        return PosteriorPredictive(self.sum + n * s, self.sumsq + 2.0 * s * self.sum + n * s * s, self.nslots, self.nchains,
+                                   self.data, centre)
+
+    def __add__(self, other):
+        if self.nslots != other.nslots:
+            raise ValueError("traces of different lengths do not pool")
+        if self.data.shape != other.data.shape:
+            raise ValueError("histograms of different shapes do not pool")
+        o = other if np.array_equal(other.centre, self.centre) else other.about(self.centre)
+        return PosteriorPredictive(self.sum + o.sum, self.sumsq + o.sumsq, self.nslots, self.nchains + o.nchains, self.data,
+                                   self.centre)
+
+    @property
+    def mean(self):
+        return self.centre + self.sum / self.n
+
+    @property
+    def spread(self):
+        m = self.sum / self.n
+        return np.sqrt(self.sumsq / self.n - m * m)
+
+
+def _event_data_shape(likelihood, prm):
+    """(header, NH, nbins) of a likelihood's parameter array; nbins = 1 where the array does not say (the library
+    refuses such an array with its own words)"""
+    shape = likelihood == _capi.LIKE_EVENT_SHAPE
+    header, nh = (12, 4) if shape else (8, 3)
+    max_bins = _capi.EVENT_SHAPE_MAX_BINS if shape else _capi.EVENT_SAMPLE_MAX_BINS
+    nbins = int(prm[1]) if prm.size > 1 and np.isfinite(prm[1]) and 1 <= prm[1] <= max_bins else 1
+    return header, nh, nbins
+
+
+def event_predictive(likelihood, params, trace_ptr, nslots, dim_stride, nchains, nchains_padded, centre=None,
+                     histograms_ptr=None, logl_ptr=None, stream=0, _lib=None):
+    """smcmc_event_predictive_sums: the simulated histograms of LIKE_EVENT_SAMPLE, _TEMPLATE or _SHAPE with the flat
+    parameter array `params` at every point of the trace at `trace_ptr` ([nslots][dim_stride][nchains_padded] on the
+    device, as StepSave wrote it), summed per bin about `centre` ([NH][nbins]; default: the origin).  histograms_ptr:
+    optional device memory [nslots][NH nbins][nchains_padded] that receives every point's histograms; logl_ptr: optional
+    device memory [nslots][nchains_padded] that receives every point's log-likelihood.  Returns a PosteriorPredictive.
+    (_lib: the library an engine has loaded, for Engine.PosteriorPredictive.)"""
+    lib = _lib or _capi.load()
+    likelihood = int(likelihood)
+    prm = _f64(params).ravel()
+    header, nh, nbins = _event_data_shape(likelihood, prm)
+    rows = nh * nbins
+    c = None if centre is None else _f64(centre).ravel()
+    if c is not None and c.size != rows:
+        raise ValueError("centre must be [NH][nbins]")
+    total, sumsq = np.zeros(rows), np.zeros(rows)
+    st = lib.smcmc_event_predictive_sums(likelihood, _ptr(prm), prm.size, C.c_void_p(int(trace_ptr)), int(nslots),
+                                         int(dim_stride), int(nchains), int(nchains_padded), None if c is None else _ptr(c),
+                                         C.c_void_p(int(histograms_ptr)) if histograms_ptr else None,
+                                         C.c_void_p(int(logl_ptr)) if logl_ptr else None, _ptr(total), _ptr(sumsq),
+                                         C.c_void_p(int(stream)))
+    if st != _capi.OK:
+        raise SmcmcError(st, lib.smcmc_event_sample_last_error().decode() or lib.smcmc_status_string(st).decode())
+    data = prm[header:header + rows].reshape(nh, nbins)
+    return PosteriorPredictive(total, sumsq, nslots, nchains, data, c)
 
 
 def cholesky_chain(mean, covariance, nslots, nchains, seed=20240607, chain_offset=0, dim_stride=None, stream=0):
