@@ -945,6 +945,57 @@ int smcmc_event_predictive_sums(int likelihood, const double* params, int count,
                                 int dim_stride, int nchains, int nchains_padded, const double* centre, double* hist_device,
                                 double* logl_device, double* sum, double* sumsq, void* stream);
 
+/* ---- posterior reducer: exact order statistics of a saved trace (quantiles, credible intervals) ----
+ * The median and the 68 % / 95 % credible interval of a parameter, or the quantile band of a predicted bin, are order
+ * statistics of a row of the trace: selected values, not sums, so the result is the bits of an entry and the same on every
+ * run.  The reference has no counterpart; this definition IS the engine's, not numpy's or ROOT's.
+ *   the order   with b the 64 bits of a double, key(x) = b ^ (b >> 63 ? 0xFFFFFFFFFFFFFFFF : 0x8000000000000000), and
+ *               every NaN, of either sign, gets key = 0xFFFFFFFFFFFFFFFF.  Unsigned comparison of keys is the total order
+ *               -inf < ... < -0 < +0 < ... < +inf < NaN.  value(key) is the inverse, the quiet NaN 0x7FF8000000000000 for
+ *               the all-ones key.  One copy for host and device: include/smcmc_order_key.h; the two host functions below
+ *               are that copy.
+ *   a row       the N = nslots * nchains entries x[t][d][c], c < nchains, of trace_device[slot][dim_stride][nchains_padded]
+ *               (as smcmc_step_save, smcmc_vaat_step_save or smcmc_hmc_copy_positions wrote it, or the hist_device of
+ *               smcmc_event_predictive_sums with dim = dim_stride = rows).  Padding lanes and rows >= dim are never read
+ *               into a result.  dim is not bounded by the largest dimension the kernels step: it is bounded by the grid,
+ *               dim <= SMCMC_ORDER_MAX_DIM.
+ * The selection is a radix selection from the most significant byte down: SMCMC_ORDER_PASSES passes of
+ * SMCMC_ORDER_DIGIT_BITS bits.
+ *
+ * The pass primitive (what ranks combine): pass p in 0 .. 7, prefixes[d][i] (host, [dim][nprefix]) the top 8p bits of a
+ * key, right-aligned; ignored at p = 0, where it may be NULL.  counts[d][i][g] (host, [dim][nprefix][256]) receives the
+ * number of entries of row d with  key >> (64 - 8p) == prefixes[d][i]  and  (key >> (56 - 8p)) & 255 == g  (at p = 0 the
+ * first condition is empty).  A prefix with bits above its 8p is matched by no entry.  Counts are integers: ranks add
+ * theirs exactly, and every run gives the same numbers.
+ *
+ * The reducer: ranks[r] (host, [nranks]) are zero-based, each < N; repeats and any order are allowed.
+ *   values[d][r]   the entry of row d with exactly ranks[r] entries before it in key order, as value(key): the bits of an
+ *                  entry of the trace, a NaN as the canonical one
+ *   below[d][r]    optional: the number of entries of row d with a smaller key than that entry's
+ *   equal[d][r]    optional: the number with the same key (>= 1).  below <= ranks[r] < below + equal; a Metropolis trace
+ *                  repeats a value at every rejected step, so ties are the normal case
+ * all host, [dim][nranks].  Eight passes of the primitive's kernel run on `stream`; between passes a small kernel picks each
+ * (row, rank)'s digit from the 256 counts and carries the residual rank; the host synchronises once, at the end.
+ *
+ * SMCMC_ERR_INVALID, with nothing launched and nothing written: trace_device, ranks, values (the reducer), counts or, at
+ * p > 0, prefixes (the primitive) NULL; nranks < 1 or > SMCMC_ORDER_MAX_RANKS; a rank >= N; nslots < 1; dim < 1 or
+ * > SMCMC_ORDER_MAX_DIM; dim_stride < dim; nchains < 1; nchains_padded < nchains or not a multiple of 64; pass outside
+ * 0 .. 7; nprefix outside 1 .. SMCMC_ORDER_MAX_RANKS.  SMCMC_ERR_NO_DEVICE without a GPU, checked after all of these.
+ * `stream` is a hipStream_t or NULL. */
+#define SMCMC_ORDER_DIGIT_BITS 8
+#define SMCMC_ORDER_PASSES 8
+#define SMCMC_ORDER_MAX_RANKS 32
+#define SMCMC_ORDER_MAX_DIM 65535           /* rows: the grid's y extent */
+uint64_t smcmc_order_key(double x);
+double smcmc_order_value(uint64_t key);
+int smcmc_order_chunk_entries(void);        /* entries of a row one workgroup counts (more only where a launch would exceed 2 048 workgroups) */
+int smcmc_trace_digit_counts(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
+                             int nchains_padded, int pass, int nprefix, const uint64_t* prefixes, uint64_t* counts,
+                             void* stream);
+int smcmc_trace_order_statistics(const double* trace_device, int nslots, int dim, int dim_stride, int nchains,
+                                 int nchains_padded, int nranks, const uint64_t* ranks, double* values, uint64_t* below,
+                                 uint64_t* equal, void* stream);
+
 /* ---- the Gaussian stand-in chain of a mean and a covariance ---------------------
  * CholeskyChain.C:18-66: covariance = U^T U with U upper triangular (:39-46; here the row-ordered routine the adaptive
  * proposal uses, a pivot that is not positive and finite is SMCMC_ERR_RUNTIME and nothing is launched or written, where

@@ -225,7 +225,15 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p, _dp, _dp, C.c_void_p]),
     "smcmc_cholesky_chain": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
                                        C.c_void_p, _dp, C.c_void_p]),
+    "smcmc_order_key": (C.c_uint64, [C.c_double]),
+    "smcmc_order_value": (C.c_double, [C.c_uint64]),
+    "smcmc_order_chunk_entries": (C.c_int, []),
+    "smcmc_trace_digit_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _up, _up,
+                                           C.c_void_p]),
+    "smcmc_trace_order_statistics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _up, _dp, _up,
+                                               _up, C.c_void_p]),
 }
+ORDER_DIGIT_BITS, ORDER_PASSES, ORDER_MAX_RANKS, ORDER_MAX_DIM = 8, 8, 32, 65535   # SMCMC_ORDER_* of include/smcmc.h
 AUTOCORR_LAGS = 64
 AUTOCORR_GRID_MAX_LAGS = 512   # SMCMC_AUTOCORR_GRID_MAX_LAGS of include/smcmc.h
 MARGINAL_MAX_BINS1, MARGINAL_MAX_BINS2, MARGINAL_MAX_PAIR_DIMS = 1000, 126, 32   # SMCMC_MARGINAL_MAX_* of include/smcmc.h

@@ -72,7 +72,8 @@ def _units(user_flag=None, name="user"):
              ("smcmc_pooled_update.hip", [], "pooled_update"), ("smcmc_perchain_inst.hip", [], "perchain"),
              wave, wg, stream,
              ("smcmc_panel_mfma_inst.hip", [], "panel_mfma"), ("smcmc_fold_inst.hip", [], "fold"),
-             ("smcmc_event_sample.hip", [], "event_sample"), ("smcmc_event_predictive.hip", [], "event_predictive")]
+             ("smcmc_event_sample.hip", [], "event_sample"), ("smcmc_event_predictive.hip", [], "event_predictive"),
+             ("smcmc_order_statistics.hip", [], "order_statistics")]
     for dp in dp_list():
         for like in LIKELIHOODS:
             units.append(("smcmc_inst.hip", [f"-DSMCMC_DP={dp}", f"-DSMCMC_LIKE={like}"], f"inst_dp{dp}_l{like}"))
@@ -176,7 +177,8 @@ def _compile(unit):
 # no scratch (private segment), which the compiler's resource report (-Rpass-analysis=kernel-resource-usage) states
 # per kernel.  A unit that spills is refused, not built.
 NO_SCRATCH_SOURCES = ("smcmc_perchain_wg_inst.hip", "smcmc_perchain_stream_inst.hip", "smcmc_marginals.hip", "smcmc_trace_moments.hip",
-                      "smcmc_convergence.hip", "smcmc_autocorr_grid.hip", "smcmc_event_predictive.hip")
+                      "smcmc_convergence.hip", "smcmc_autocorr_grid.hip", "smcmc_event_predictive.hip",
+                      "smcmc_order_statistics.hip")
 
 
 def _check_no_scratch(name, obj, remarks):
@@ -306,7 +308,9 @@ def build(jobs=None, verbose=False, user_likelihood=None, output=None, with_plai
         if not units:
             continue
         objs = [built[u[2]][0] for u in units]
-        if any(built[u[2]][1] for u in units) or not os.path.exists(lib_path):
+        # an object shared with another library may have been rebuilt by an earlier call: the library's age decides too
+        if (any(built[u[2]][1] for u in units) or not os.path.exists(lib_path)
+                or os.path.getmtime(lib_path) < max(os.path.getmtime(o) for o in objs)):
             _link(objs, lib_path)
         result = lib_path
     return result

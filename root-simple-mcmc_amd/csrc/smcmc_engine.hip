@@ -1137,7 +1137,7 @@ int launch(smcmc_engine* h, int nsteps, int metropolis, int stride, double* save
 
 extern "C" {
 
-int smcmc_version(void) { return 100; }
+int smcmc_version(void) { return 101; }
 int smcmc_max_register_dim(void) { return kDPList[kNumDP - 1]; }
 int smcmc_max_perchain_dim(void) { return smcmc::kWgMaxDim; }
 int smcmc_max_perchain_stream_dim(void) { return smcmc::kStMaxDim; }

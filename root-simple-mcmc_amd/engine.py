@@ -15,8 +15,9 @@ from ._capi import (LIKE_ASYM, LIKE_CONSTRAINED, LIKE_EVENT_SAMPLE, LIKE_EVENT_S
                     SmcmcError)
 # the reducers over a saved trace live in trace.py; their names stay importable from here
 from .trace import (Autocorrelation, AutocorrelationGrid, AutocorrelationPlan, Convergence, MacroAutocorrelation, Marginals,  # noqa: F401
-                    PosteriorPredictive, TraceMoments, TraceReducers, autocorrelation_plan, cholesky_chain, event_predictive,
-                    _f64, _ptr)
+                    PosteriorPredictive, TraceMoments, TraceQuantiles, TraceReducers, autocorrelation_plan, cholesky_chain,
+                    event_predictive, order_keys, order_statistics_combined, order_values, quantile_ranks, trace_digit_counts,
+                    _event_data_shape, _f64, _order_statistics, _ptr)
 
 
 class Engine(TraceReducers):
@@ -111,6 +112,18 @@ class Engine(TraceReducers):
                                               "LIKE_EVENT_SHAPE and its parameters")
         return event_predictive(self.likelihood, self._likelihood_params, trace_ptr, nslots, self._trace_dim_stride,
                                 self.nchains, self.nchains_padded, centre, histograms_ptr, logl_ptr, stream, _lib=self._lib)
+
+    def PredictiveQuantiles(self, histograms_ptr, nslots, q=(0.025, 0.16, 0.5, 0.84, 0.975), stream=0):
+        """The quantile band of every predicted bin: exact order statistics (smcmc_trace_order_statistics) over the
+        device buffer [nslots][NH nbins][nchains_padded] that PosteriorPredictive(..., histograms_ptr=...) filled, one
+        row per bin.  Returns a TraceQuantiles whose results are [NH][nbins]."""
+        if self.likelihood not in (LIKE_EVENT_SAMPLE, LIKE_EVENT_TEMPLATE, LIKE_EVENT_SHAPE) or self._likelihood_params is None:
+            raise SmcmcError(_capi.ERR_LOGIC, "PredictiveQuantiles needs LIKE_EVENT_SAMPLE, LIKE_EVENT_TEMPLATE or "
+                                              "LIKE_EVENT_SHAPE and its parameters")
+        _, nh, nbins = _event_data_shape(self.likelihood, self._likelihood_params)
+        rows = nh * nbins
+        return _order_statistics(self._lib, self._check, histograms_ptr, nslots, rows, rows, self.nchains, self.nchains_padded,
+                                 quantile_ranks(int(nslots) * self.nchains, q), stream, shape=(nh, nbins))
 
     def set_stream(self, stream):
         """stream: a raw hipStream_t value (e.g. torch.cuda.current_stream().cuda_stream)."""

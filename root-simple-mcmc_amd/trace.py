@@ -7,7 +7,9 @@ smcmc_marginal_histograms, smcmc_trace_moments, smcmc_trace_convergence; include
 classes are host-side numpy over the raw sums and have nothing to do with any engine; `TraceReducers` gives an engine
 class the six methods that call the library on a trace of its own layout.  `event_predictive` and its result,
 `PosteriorPredictive`, are the seventh reducer (smcmc_event_predictive_sums): it needs a likelihood over a simulated event
-sample besides the trace, so only Engine, the one engine that serves that family, has a method for it.
+sample besides the trace, so only Engine, the one engine that serves that family, has a method for it.  The order
+statistics (smcmc_trace_order_statistics, smcmc_trace_digit_counts; `TraceQuantiles`) are selected values, not sums: the
+mixin's OrderStatistics, Quantiles and DigitCounts, and order_statistics_combined for several ranks' shards.
 """
 import ctypes as C
 
@@ -83,6 +85,27 @@ class TraceReducers:
         plain form), each about its own mean.  Pass a `centre` near the mean, e.g. TraceMoments(...).mean from one
         earlier pass: the variance of the segment means cancels like any E[yy] - E[y]^2.  Returns a Convergence."""
         return _convergence(self._lib, self._check, trace_ptr, nslots, *self._trace_shape(), nsegments, centre, stream)
+
+    def OrderStatistics(self, trace_ptr, nslots, ranks, stream=0):
+        """Exact order statistics of every dimension of a trace StepSave wrote, selected on the device
+        (smcmc_trace_order_statistics): for each zero-based rank < nslots * nchains the entry with that many entries
+        before it in the order of include/smcmc_order_key.h, with the numbers of smaller and of equal entries.  More than
+        32 ranks are taken in several calls.  Returns a TraceQuantiles."""
+        return _order_statistics(self._lib, self._check, trace_ptr, nslots, *self._trace_shape(), ranks, stream)
+
+    def Quantiles(self, trace_ptr, nslots, q=(0.025, 0.16, 0.5, 0.84, 0.975), stream=0):
+        """The quantiles `q` of every dimension of a trace StepSave wrote -- the median and the 68 % and 95 % credible
+        intervals by default -- from exact order statistics taken on the device: only the ranks floor((N - 1) q) and
+        ceil((N - 1) q) that TraceQuantiles.quantile interpolates between are asked for.  Returns a TraceQuantiles."""
+        return _order_statistics(self._lib, self._check, trace_ptr, nslots, *self._trace_shape(),
+                                 quantile_ranks(int(nslots) * self.nchains, q), stream)
+
+    def DigitCounts(self, trace_ptr, nslots, pass_, prefixes=None, nprefix=None, stream=0):
+        """One pass of the selection over this engine's trace (smcmc_trace_digit_counts): counts[dim][nprefix][256], the
+        `count_fn` of order_statistics_combined for one rank's shard.  prefixes: [dim][nprefix] (None at pass 0, where
+        nprefix says how many copies of the counts to return; default 1)."""
+        return trace_digit_counts(trace_ptr, nslots, *self._trace_shape(), pass_, prefixes, nprefix, stream, _lib=self._lib,
+                                  _check=self._check)
 
 
 class Autocorrelation:
@@ -716,6 +739,176 @@ def event_predictive(likelihood, params, trace_ptr, nslots, dim_stride, nchains,
         raise SmcmcError(st, lib.smcmc_event_sample_last_error().decode() or lib.smcmc_status_string(st).decode())
     data = prm[header:header + rows].reshape(nh, nbins)
     return PosteriorPredictive(total, sumsq, nslots, nchains, data, c)
+
+
+_u64 = np.uint64
+_up = C.POINTER(C.c_uint64)
+_SIGN, _ONES = _u64(0x8000000000000000), _u64(0xFFFFFFFFFFFFFFFF)
+
+
+def order_keys(x):
+    """key(x) of include/smcmc_order_key.h for an array of doubles: uint64, whose unsigned order is
+    -inf < ... < -0 < +0 < ... < +inf < NaN (every NaN the all-ones key)."""
+    x = _f64(x)
+    b = x.view(_u64)
+    return np.where(np.isnan(x), _ONES, b ^ np.where(b >> _u64(63) != 0, _ONES, _SIGN))
+
+
+def order_values(keys):
+    """value(key), the inverse of order_keys (the quiet NaN 0x7FF8000000000000 for the all-ones key)."""
+    k = np.ascontiguousarray(keys, dtype=_u64)
+    b = np.where(k == _ONES, _u64(0x7FF8000000000000), k ^ np.where(k >> _u64(63) != 0, _SIGN, _ONES))
+    return np.ascontiguousarray(b).view(np.float64)
+
+
+def quantile_ranks(n, q):
+    """The distinct ranks, ascending, that the quantiles `q` of n entries interpolate between: floor((n - 1) q) and
+    ceil((n - 1) q) for every q in [0, 1]."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("no entries")
+    ranks = set()
+    for p in np.atleast_1d(_f64(q)):
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("a quantile's probability lies in [0, 1]")
+        h = float(n - 1) * float(p)
+        ranks.update((int(np.floor(h)), int(np.ceil(h))))
+    return np.array(sorted(ranks), dtype=_u64)
+
+
+class TraceQuantiles:
+    """Exact order statistics of the rows of a saved trace (smcmc_trace_order_statistics; include/smcmc.h has the order)
+    and the quantiles between them.  Over the n = nslots * nchains entries of each row:
+      ranks  [R]       the zero-based ranks asked for
+      values [rows][R] the entry with exactly ranks[r] entries before it: the bits of an entry of the trace
+      below  [rows][R] uint64, the entries with a smaller key than that one
+      equal  [rows][R] uint64, the entries with the same key (a rejected step repeats a value: ties are the normal case)
+      quantile(q)      with h = (n - 1) q, lo = floor(h), hi = ceil(h): v_lo + (h - lo) (v_hi - v_lo), numpy's "linear"
+                       method; both ranks must be among `ranks` (Quantiles asks for them)
+      median           quantile(0.5)
+      interval(level)  the central credible interval holding `level` of the entries: the quantiles (1 -+ level) / 2
+    Results have the shape `shape` of the rows ([dim]; [NH][nbins] for the predictive histograms), a sequence of
+    probabilities adds a last axis.  Selected values do not add: ranks combine the counts of the passes instead
+    (order_statistics_combined)."""
+
+    def __init__(self, ranks, values, below, equal, n, shape=None):
+        self.ranks = np.array(ranks, dtype=_u64).ravel()
+        self.values = _f64(values).copy()
+        self.below, self.equal = np.array(below, dtype=_u64), np.array(equal, dtype=_u64)
+        self.n = int(n)
+        want = (self.values.shape[0] if self.values.ndim == 2 else -1, self.ranks.size)
+        if self.values.shape != want or self.below.shape != want or self.equal.shape != want:
+            raise ValueError("ranks[R] and values, below, equal [rows][R] do not fit together")
+        self.shape = (want[0],) if shape is None else tuple(int(s) for s in shape)
+        if int(np.prod(self.shape)) != want[0]:
+            raise ValueError("shape does not hold the rows")
+        self._column = {int(r): i for i, r in enumerate(self.ranks)}
+
+    def value_at(self, rank):
+        """[rows]: the entry of every row at `rank`"""
+        if int(rank) not in self._column:
+            raise KeyError("rank %d was not asked for" % int(rank))
+        return self.values[:, self._column[int(rank)]]
+
+    def _quantile(self, q):
+        q = float(q)
+        if not 0.0 <= q <= 1.0:
+            raise ValueError("a quantile's probability lies in [0, 1]")
+        h = float(self.n - 1) * q
+        lo, hi = int(np.floor(h)), int(np.ceil(h))
+        v_lo, v_hi = self.value_at(lo), self.value_at(hi)
+        return v_lo + (h - lo) * (v_hi - v_lo)
+
+    def quantile(self, q):
+        if np.ndim(q) == 0:
+            return self._quantile(q).reshape(self.shape)
+        return np.stack([self._quantile(p) for p in q], axis=-1).reshape(self.shape + (len(q),))
+
+    @property
+    def median(self):
+        return self.quantile(0.5)
+
+    def interval(self, level=0.68):
+        """(lower, upper): the quantiles (1 - level) / 2 and (1 + level) / 2, the probabilities rounded to twelve decimals so
+        that level 0.68 asks for the 0.16 and 0.84 that Quantiles takes by default, not a neighbouring double"""
+        return self.quantile(round(0.5 * (1.0 - level), 12)), self.quantile(round(0.5 * (1.0 + level), 12))
+
+
+def _order_statistics(lib, check, trace_ptr, nslots, dim, dim_stride, nchains, nchains_padded, ranks, stream, shape=None):
+    """The body of the engines' OrderStatistics and Quantiles methods: calls of at most ORDER_MAX_RANKS ranks each."""
+    ranks = np.ascontiguousarray(ranks, dtype=_u64).ravel()
+    if ranks.size < 1:
+        raise ValueError("at least one rank")
+    nslots = int(nslots)
+    values = np.zeros((dim, ranks.size))
+    below, equal = np.zeros((dim, ranks.size), dtype=_u64), np.zeros((dim, ranks.size), dtype=_u64)
+    for i0 in range(0, ranks.size, _capi.ORDER_MAX_RANKS):
+        part = np.ascontiguousarray(ranks[i0:i0 + _capi.ORDER_MAX_RANKS])
+        v = np.zeros((dim, part.size))
+        b, e = np.zeros((dim, part.size), dtype=_u64), np.zeros((dim, part.size), dtype=_u64)
+        check(lib.smcmc_trace_order_statistics(C.c_void_p(int(trace_ptr)), nslots, dim, dim_stride, nchains, nchains_padded,
+                                               part.size, part.ctypes.data_as(_up), _ptr(v), b.ctypes.data_as(_up),
+                                               e.ctypes.data_as(_up), C.c_void_p(int(stream))))
+        values[:, i0:i0 + part.size], below[:, i0:i0 + part.size], equal[:, i0:i0 + part.size] = v, b, e
+    return TraceQuantiles(ranks, values, below, equal, nslots * nchains, shape)
+
+
+def trace_digit_counts(trace_ptr, nslots, dim, dim_stride, nchains, nchains_padded, pass_, prefixes=None, nprefix=None,
+                       stream=0, _lib=None, _check=None):
+    """smcmc_trace_digit_counts: counts[dim][nprefix][256] of pass `pass_` over the trace at `trace_ptr`
+    ([nslots][dim_stride][nchains_padded] on the device), uint64.  prefixes: [dim][nprefix] uint64, the top 8 pass_ bits
+    of a key each (None at pass 0; nprefix then says how many copies of the counts to return, default 1)."""
+    lib = _lib or _capi.load()
+    if prefixes is not None:
+        prefixes = np.ascontiguousarray(prefixes, dtype=_u64)
+        if prefixes.ndim != 2 or prefixes.shape[0] != dim:
+            raise ValueError("prefixes must be [dim][nprefix]")
+        nprefix = prefixes.shape[1]
+    nprefix = 1 if nprefix is None else int(nprefix)
+    counts = np.zeros((dim, max(nprefix, 0), 1 << _capi.ORDER_DIGIT_BITS), dtype=_u64)
+    st = lib.smcmc_trace_digit_counts(C.c_void_p(int(trace_ptr)), int(nslots), dim, dim_stride, nchains, nchains_padded,
+                                      int(pass_), nprefix, None if prefixes is None else prefixes.ctypes.data_as(_up),
+                                      counts.ctypes.data_as(_up), C.c_void_p(int(stream)))
+    if _check is not None:
+        _check(st)
+    elif st != _capi.OK:
+        raise SmcmcError(st, lib.smcmc_status_string(st).decode())
+    return counts
+
+
+def order_statistics_combined(count_fn, dim, n, ranks, shape=None):
+    """The eight-pass selection of smcmc_trace_order_statistics on the host, from any
+    count_fn(pass, prefixes) -> counts[dim][R][256]: prefixes is [dim][R] uint64 (None at pass 0: the counts of the whole
+    rows, one copy per rank or one for all), counts what smcmc_trace_digit_counts defines.  Several ranks, each calling
+    DigitCounts on its own shard of the chains and adding the arrays (an all-reduce of 256 R dim integers per pass), get
+    the ensemble's exact order statistics this way: n is the ensemble's nslots * nchains.  Returns a TraceQuantiles, bit
+    for bit what one call over the whole ensemble returns."""
+    ranks = np.array(ranks, dtype=_u64).ravel()
+    dim, n, R = int(dim), int(n), ranks.size
+    if not 1 <= R <= _capi.ORDER_MAX_RANKS:
+        raise ValueError("between 1 and %d ranks" % _capi.ORDER_MAX_RANKS)
+    if np.any(ranks >= _u64(n)):
+        raise ValueError("a rank is zero-based and below n")
+    ndigits, bits = 1 << _capi.ORDER_DIGIT_BITS, _u64(_capi.ORDER_DIGIT_BITS)
+    prefix = np.zeros((dim, R), dtype=_u64)
+    resid = np.tile(ranks, (dim, 1))
+    below, equal = np.zeros((dim, R), dtype=_u64), np.zeros((dim, R), dtype=_u64)
+    for p in range(_capi.ORDER_PASSES):
+        counts = np.asarray(count_fn(p, None if p == 0 else prefix.copy()), dtype=_u64)
+        if p == 0 and counts.size == dim * ndigits:
+            counts = np.repeat(counts.reshape(dim, 1, ndigits), R, axis=1)
+        counts = counts.reshape(dim, R, ndigits)
+        cum = np.cumsum(counts, axis=2, dtype=_u64)
+        g = (cum <= resid[:, :, None]).sum(axis=2)          # the first digit whose running count exceeds the residual rank
+        if np.any(g >= ndigits):
+            raise ValueError("pass %d: the counts hold fewer entries than a rank asks for" % p)
+        pick = g[:, :, None]
+        before = np.take_along_axis(cum - counts, pick, axis=2)[:, :, 0]
+        prefix = (prefix << bits) | g.astype(_u64)
+        resid, below = resid - before, below + before
+        if p == _capi.ORDER_PASSES - 1:
+            equal = np.take_along_axis(counts, pick, axis=2)[:, :, 0]
+    return TraceQuantiles(ranks, order_values(prefix), below, equal, n, shape)
 
 
 def cholesky_chain(mean, covariance, nslots, nchains, seed=20240607, chain_offset=0, dim_stride=None, stream=0):
