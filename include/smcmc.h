@@ -996,6 +996,57 @@ int smcmc_trace_order_statistics(const double* trace_device, int nslots, int dim
                                  int nchains_padded, int nranks, const uint64_t* ranks, double* values, uint64_t* below,
                                  uint64_t* equal, void* stream);
 
+/* ---- posterior reducer: the posterior-predictive check (replicated data and p-values) ----
+ * The band of smcmc_event_predictive_sums is around the EXPECTATION of a bin; the data scatter about it with Poisson noise.
+ * Whether the data fit the model is asked of replicated data: for every posterior point draw y_rep[r] ~ Poisson(mu[r]) from
+ * that point's expectation, compare the likelihood's own discrepancy on the replicate with the one on the observed data,
+ * and report the tail fractions (Gelman, Meng and Stern 1996).  The reference has no counterpart -- every FakeMCMC.C draws
+ * dataStack over the prediction and leaves the question to the eye -- so this definition IS the engine's.
+ *   the variate  include/smcmc_poisson.h states it line by line: mu = max(expectation, 0.001), the clamp of the bin term; one
+ *                Philox block per variate at (seed, global chain, step = global slot | row << 28 | replica << 44) on
+ *                SMCMC_STREAM_REPLICA; a 52-bit uniform; inversion of the cumulative distribution from 0 (mu < 16) or
+ *                outwards from the mode (mu >= 16).  A function of its inputs alone, the same bits on host and device.  It
+ *                is INVALID, and nothing is drawn, for an expectation that is NaN or infinite or mu > SMCMC_POISSON_MAX_MEAN.
+ *                smcmc_poisson_draw is that variate on the host (no GPU needed): `chain` and `slot` are the global ones;
+ *                *valid = 0 and *y = NaN when invalid.  SMCMC_ERR_INVALID, nothing written: y or valid NULL, slot >= 2^28,
+ *                row >= 2^16, replica >= 2^16.
+ *   input        hist_device[slot][rows][nchains_padded]: what smcmc_event_predictive_sums leaves in its hist_device, or any
+ *                buffer of Poisson means in that layout; lanes >= nchains are never read into a result.  data[rows]: host,
+ *                finite and >= 0.  Group g of ngroups is the rows [g rows / ngroups, (g + 1) rows / ngroups): for the event
+ *                family one group per histogram.
+ *   a point      (t, c < nchains) is VALID when the variate is at every one of its rows.  For a valid point
+ *                  y[r]     = the variate at (seed, chain_offset + c, slot_offset + t, r, replica) and mu[r]
+ *                  T_obs[g] = sum_r smcmc_es_bin_term(data[r], mu[r]),  T_rep[g] = sum_r smcmc_es_bin_term(y[r], mu[r])
+ *                over the group's rows ascending from +0.0, un-fused (include/smcmc_event_sample.h); entry g = ngroups holds
+ *                the same two sums over all rows, as running sums of their own.  For SMCMC_LIKE_EVENT_SAMPLE the total
+ *                T_obs is the likelihood's logl, bit for bit.
+ *   results      host, all INTEGERS -- ranks, windows of slots and replicas add theirs exactly; the same numbers on every
+ *                run and on every grid:
+ *                  below[r], equal[r]       the valid points with y[r] < data[r], with y[r] == data[r]           [rows]
+ *                  stat_counts[g][3]        the valid points with T_rep < T_obs, with T_rep == T_obs, and the number
+ *                                           compared                                                  [ngroups + 1][3]
+ *                  *invalid                 the invalid points; they enter nothing else
+ *   rep_device   optional device output [slot][rows][nchains_padded]: y as doubles, NaN in every row of an invalid point,
+ *                +0.0 in lanes >= nchains -- the layout smcmc_trace_order_statistics takes: its quantiles are the band the
+ *                DATA are expected to lie in.
+ *   stat_device  optional device output [slot][2 (ngroups + 1)][nchains_padded]: row 2 g is T_obs, row 2 g + 1 is T_rep,
+ *                invalid points and padding likewise.  The reducers over a trace take it as it is.
+ * The p-value of group g is (stat_counts[g][0] + stat_counts[g][1]) / stat_counts[g][2].
+ * SMCMC_ERR_INVALID, with nothing launched and nothing written: hist_device, data, below, equal, stat_counts or invalid
+ * NULL; nslots < 1, rows outside 1 .. SMCMC_PREDICTIVE_CHECK_MAX_ROWS, nchains < 1, nchains_padded < nchains or not a
+ * multiple of 64; ngroups outside 1 .. SMCMC_PREDICTIVE_CHECK_MAX_GROUPS or not dividing rows; a data[r] that is negative
+ * or not finite; slot_offset + nslots > 2^28 or replica >= 2^16 (the text through smcmc_event_sample_last_error).
+ * SMCMC_ERR_NO_DEVICE without a GPU, checked after all of these.  `stream` is a hipStream_t or NULL. */
+#define SMCMC_POISSON_MAX_MEAN 1048576.0
+#define SMCMC_PREDICTIVE_CHECK_MAX_ROWS 4096    /* two 64-bit counters per row in 64 KB of LDS */
+#define SMCMC_PREDICTIVE_CHECK_MAX_GROUPS 8
+int smcmc_poisson_draw(uint64_t seed, uint32_t chain, uint32_t slot, uint32_t row, uint32_t replica, double expectation,
+                       double* y, int* valid);
+int smcmc_predictive_check(const double* hist_device, int nslots, int rows, int nchains, int nchains_padded,
+                           const double* data, int ngroups, uint64_t seed, uint32_t chain_offset, uint32_t slot_offset,
+                           uint32_t replica, double* rep_device, double* stat_device, uint64_t* below, uint64_t* equal,
+                           uint64_t* stat_counts, uint64_t* invalid, void* stream);
+
 /* ---- the Gaussian stand-in chain of a mean and a covariance ---------------------
  * CholeskyChain.C:18-66: covariance = U^T U with U upper triangular (:39-46; here the row-ordered routine the adaptive
  * proposal uses, a pivot that is not positive and finite is SMCMC_ERR_RUNTIME and nothing is launched or written, where

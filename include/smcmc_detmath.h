@@ -116,6 +116,8 @@ SMCMC_HD smcmc_u32x4 smcmc_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2,
                                  * Uniform() of a queue shuffle made during that step (TProposeVAATStep.H:190-193) */
 #define SMCMC_STREAM_CHOLESKY 4u /* smcmc_cholesky_chain: the normals of a draw, laid out as a chain-step's (block b of
                                  * (chain, slot) gives normals 4b .. 4b+3), CholeskyChain.C:56 */
+#define SMCMC_STREAM_REPLICA 5u  /* smcmc_predictive_check: the uniform of one Poisson variate, words 0 and 1 of block 0 at
+                                 * step = slot | row << 28 | replica << 44 (include/smcmc_poisson.h) */
 
 /* Every draw of the engine is a block of Philox4x32-7: seven rounds is the count Salmon et al. (SC'11, table 2) report
  * as the fewest that pass BigCrush ("Crush-resistant"), ten their default with a safety margin.  The headline kernel

@@ -232,7 +232,13 @@ SIGNATURES = {
                                            C.c_void_p]),
     "smcmc_trace_order_statistics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _up, _dp, _up,
                                                _up, C.c_void_p]),
+    "smcmc_poisson_draw": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, _dp,
+                                     C.POINTER(C.c_int)]),
+    "smcmc_predictive_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64, C.c_uint32,
+                                         C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _up, _up, _up, _up, C.c_void_p]),
 }
+POISSON_MAX_MEAN = 1048576.0   # SMCMC_POISSON_MAX_MEAN of include/smcmc.h
+PREDICTIVE_CHECK_MAX_ROWS, PREDICTIVE_CHECK_MAX_GROUPS = 4096, 8   # SMCMC_PREDICTIVE_CHECK_MAX_* of include/smcmc.h
 ORDER_DIGIT_BITS, ORDER_PASSES, ORDER_MAX_RANKS, ORDER_MAX_DIM = 8, 8, 32, 65535   # SMCMC_ORDER_* of include/smcmc.h
 AUTOCORR_LAGS = 64
 AUTOCORR_GRID_MAX_LAGS = 512   # SMCMC_AUTOCORR_GRID_MAX_LAGS of include/smcmc.h

@@ -73,7 +73,8 @@ def _units(user_flag=None, name="user"):
              wave, wg, stream,
              ("smcmc_panel_mfma_inst.hip", [], "panel_mfma"), ("smcmc_fold_inst.hip", [], "fold"),
              ("smcmc_event_sample.hip", [], "event_sample"), ("smcmc_event_predictive.hip", [], "event_predictive"),
-             ("smcmc_order_statistics.hip", [], "order_statistics")]
+             ("smcmc_order_statistics.hip", [], "order_statistics"),
+             ("smcmc_predictive_check.hip", [], "predictive_check")]
     for dp in dp_list():
         for like in LIKELIHOODS:
             units.append(("smcmc_inst.hip", [f"-DSMCMC_DP={dp}", f"-DSMCMC_LIKE={like}"], f"inst_dp{dp}_l{like}"))
@@ -178,7 +179,7 @@ def _compile(unit):
 # per kernel.  A unit that spills is refused, not built.
 NO_SCRATCH_SOURCES = ("smcmc_perchain_wg_inst.hip", "smcmc_perchain_stream_inst.hip", "smcmc_marginals.hip", "smcmc_trace_moments.hip",
                       "smcmc_convergence.hip", "smcmc_autocorr_grid.hip", "smcmc_event_predictive.hip",
-                      "smcmc_order_statistics.hip")
+                      "smcmc_order_statistics.hip", "smcmc_predictive_check.hip")
 
 
 def _check_no_scratch(name, obj, remarks):

@@ -15,9 +15,9 @@ from ._capi import (LIKE_ASYM, LIKE_CONSTRAINED, LIKE_EVENT_SAMPLE, LIKE_EVENT_S
                     SmcmcError)
 # the reducers over a saved trace live in trace.py; their names stay importable from here
 from .trace import (Autocorrelation, AutocorrelationGrid, AutocorrelationPlan, Convergence, MacroAutocorrelation, Marginals,  # noqa: F401
-                    PosteriorPredictive, TraceMoments, TraceQuantiles, TraceReducers, autocorrelation_plan, cholesky_chain,
-                    event_predictive, order_keys, order_statistics_combined, order_values, quantile_ranks, trace_digit_counts,
-                    _event_data_shape, _f64, _order_statistics, _ptr)
+                    PosteriorPredictive, PredictiveCheck, TraceMoments, TraceQuantiles, TraceReducers, autocorrelation_plan,
+                    cholesky_chain, event_predictive, order_keys, order_statistics_combined, order_values, poisson_draw,
+                    predictive_check, quantile_ranks, trace_digit_counts, _event_data_shape, _f64, _order_statistics, _ptr)
 
 
 class Engine(TraceReducers):
@@ -33,6 +33,7 @@ class Engine(TraceReducers):
         # device memory (SMCMC_P_PERCHAIN_STREAM), 63 < dim <= smcmc_max_perchain_stream_dim()
         self._lib = _capi.load(library)
         self.dim, self.nchains = int(dim), int(nchains)
+        self.seed, self.chain_offset = int(seed), int(chain_offset)
         h = C.c_void_p()
         st = self._lib.smcmc_create(self.dim, self.nchains, likelihood, seed, chain_offset, device, C.byref(h))
         self._h = h
@@ -124,6 +125,25 @@ class Engine(TraceReducers):
         rows = nh * nbins
         return _order_statistics(self._lib, self._check, histograms_ptr, nslots, rows, rows, self.nchains, self.nchains_padded,
                                  quantile_ranks(int(nslots) * self.nchains, q), stream, shape=(nh, nbins))
+
+    def PredictiveCheck(self, histograms_ptr, nslots, seed=None, replica=0, slot_offset=0, replicates_ptr=None,
+                        statistics_ptr=None, stream=0):
+        """The posterior-predictive check (smcmc_predictive_check) of the device buffer [nslots][NH nbins][nchains_padded]
+        that PosteriorPredictive(..., histograms_ptr=...) filled, against the likelihood's own data: replicated data
+        y_rep ~ Poisson(expectation) at every point, the bin term summed over them and over the data, one group per
+        histogram.  seed: of the replicates (default: the engine's); replica: which of 2^16 independent sets; slot_offset:
+        the global number of the buffer's first slot, for a window of a longer trace.  replicates_ptr / statistics_ptr:
+        optional device memory [nslots][NH nbins][nchains_padded] / [nslots][2 (NH + 1)][nchains_padded] that receives the
+        replicates (PredictiveQuantiles takes it: the band the data are expected in) / T_obs and T_rep.  Returns a
+        PredictiveCheck: p-values per histogram and overall, and per bin how often the replicate fell below or on the data."""
+        if self.likelihood not in (LIKE_EVENT_SAMPLE, LIKE_EVENT_TEMPLATE, LIKE_EVENT_SHAPE) or self._likelihood_params is None:
+            raise SmcmcError(_capi.ERR_LOGIC, "PredictiveCheck needs LIKE_EVENT_SAMPLE, LIKE_EVENT_TEMPLATE or "
+                                              "LIKE_EVENT_SHAPE and its parameters")
+        header, nh, nbins = _event_data_shape(self.likelihood, self._likelihood_params)
+        rows = nh * nbins
+        return predictive_check(histograms_ptr, nslots, rows, self.nchains, self.nchains_padded,
+                                self._likelihood_params[header:header + rows], nh, self.seed if seed is None else seed,
+                                self.chain_offset, slot_offset, replica, replicates_ptr, statistics_ptr, stream, _lib=self._lib)
 
     def set_stream(self, stream):
         """stream: a raw hipStream_t value (e.g. torch.cuda.current_stream().cuda_stream)."""

@@ -10,6 +10,8 @@ class the six methods that call the library on a trace of its own layout.  `even
 sample besides the trace, so only Engine, the one engine that serves that family, has a method for it.  The order
 statistics (smcmc_trace_order_statistics, smcmc_trace_digit_counts; `TraceQuantiles`) are selected values, not sums: the
 mixin's OrderStatistics, Quantiles and DigitCounts, and order_statistics_combined for several ranks' shards.
+`predictive_check` and its result, `PredictiveCheck`, are the posterior-predictive check of the buffer `event_predictive`
+fills (smcmc_predictive_check): integer counts; `poisson_draw` is its Poisson variate on the host.
 """
 import ctypes as C
 
@@ -743,6 +745,127 @@ def event_predictive(likelihood, params, trace_ptr, nslots, dim_stride, nchains,
 
 _u64 = np.uint64
 _up = C.POINTER(C.c_uint64)
+
+
+def poisson_draw(seed, chain, slot, row, replica, expectation, _lib=None):
+    """smcmc_poisson_draw on the host (no GPU needed): the Poisson variate of include/smcmc_poisson.h at
+    (seed, chain, slot, row, replica) -- the global chain and slot -- and `expectation`.  chain, slot, row, replica and
+    expectation broadcast against each other; returns doubles of that shape, NaN where the variate is invalid (an
+    expectation that is NaN or infinite, or above POISSON_MAX_MEAN)."""
+    lib = _lib or _capi.load()
+    args = np.broadcast_arrays(np.asarray(chain, dtype=np.uint32), np.asarray(slot, dtype=np.uint32),
+                               np.asarray(row, dtype=np.uint32), np.asarray(replica, dtype=np.uint32),
+                               np.asarray(expectation, dtype=np.float64))
+    out = np.empty(args[0].shape)
+    flat = out.reshape(-1)
+    y, valid = C.c_double(), C.c_int()
+    draw, seed = lib.smcmc_poisson_draw, int(seed)
+    for i, (c, t, r, k, e) in enumerate(zip(*(a.ravel().tolist() for a in args))):
+        st = draw(seed, c, t, r, k, e, C.byref(y), C.byref(valid))
+        if st != _capi.OK:
+            raise SmcmcError(st, "poisson_draw: slot < 2^28, row < 2^16 and replica < 2^16")
+        flat[i] = y.value
+    return out if out.ndim else float(out)
+
+
+class PredictiveCheck:
+    """The posterior-predictive check of a buffer of predicted histograms against the observed ones, from the integer
+    counts of smcmc_predictive_check (include/smcmc.h): for every valid posterior point the replicated data
+    y_rep ~ Poisson(expectation) were drawn and the likelihood's own bin term summed over them (T_rep) and over the
+    observed data (T_obs), per histogram and over all bins.
+      names          the histograms: ("Close", "Separated", "DecayTag"), for the shape "VeryClose" first (the groups
+                     numbered where the data are not an event likelihood's)
+      data           [NH][nbins], the observed histograms
+      below, equal   [NH][nbins] uint64: the valid points whose replicate fell below / on the observed count
+      stat_counts    [NH + 1][3] uint64: points with T_rep < T_obs, with T_rep == T_obs, and the number compared; the
+                     last entry is over all bins
+      n, invalid     the valid points, and the points left out (an expectation that is NaN, infinite or above 2^20)
+      pvalue, group_pvalues       (less + equal) / compared over all bins, and per histogram as {name: value}: the
+                     fraction of replicates that fit no better than the data do (T is a log-likelihood: smaller is worse)
+      mid_pvalue, group_mid_pvalues   (less + equal / 2) / compared
+      bin_tail()     (P(y_rep <= data), P(y_rep >= data)) per bin, [NH][nbins] each
+    Counts of several ranks, of windows of slots and of replicas add (`+`); operands whose data differ are refused."""
+
+    def __init__(self, data, below, equal, stat_counts, invalid, names=None):
+        self.data = _f64(data).copy()
+        if self.data.ndim != 2:
+            raise ValueError("data must be [NH][nbins]")
+        shape, nh = self.data.shape, self.data.shape[0]
+        self.below = np.array(below, dtype=_u64).reshape(shape)
+        self.equal = np.array(equal, dtype=_u64).reshape(shape)
+        self.stat_counts = np.array(stat_counts, dtype=_u64).reshape(nh + 1, 3)
+        self.invalid = int(invalid)
+        if names is None:
+            names = PosteriorPredictive.NAMES[4 - nh:] if nh in (3, 4) else tuple("group%d" % g for g in range(nh))
+        self.names = tuple(names)
+        if len(self.names) != nh:
+            raise ValueError("one name per histogram")
+
+    @property
+    def n(self):
+        return int(self.stat_counts[-1, 2])
+
+    def __add__(self, other):
+        if self.data.shape != other.data.shape or not np.array_equal(self.data, other.data):
+            raise ValueError("checks against different data do not add")
+        return PredictiveCheck(self.data, self.below + other.below, self.equal + other.equal,
+                               self.stat_counts + other.stat_counts, self.invalid + other.invalid, self.names)
+
+    def _tail(self, half):
+        less, same, n = (self.stat_counts[:, k].astype(np.float64) for k in range(3))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (less + (0.5 if half else 1.0) * same) / n
+
+    @property
+    def pvalue(self):
+        return float(self._tail(False)[-1])
+
+    @property
+    def mid_pvalue(self):
+        return float(self._tail(True)[-1])
+
+    @property
+    def group_pvalues(self):
+        return dict(zip(self.names, self._tail(False)[:-1].tolist()))
+
+    @property
+    def group_mid_pvalues(self):
+        return dict(zip(self.names, self._tail(True)[:-1].tolist()))
+
+    def bin_tail(self):
+        """(P(y_rep <= data), P(y_rep >= data)) of every bin over the valid points"""
+        n = float(self.n)
+        below, equal = self.below.astype(np.float64), self.equal.astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (below + equal) / n, (n - below) / n
+
+
+def predictive_check(hist_ptr, nslots, rows, nchains, nchains_padded, data, ngroups, seed, chain_offset=0, slot_offset=0,
+                     replica=0, replicates_ptr=None, statistics_ptr=None, stream=0, names=None, _lib=None):
+    """smcmc_predictive_check: the posterior-predictive check of the Poisson means at `hist_ptr`
+    ([nslots][rows][nchains_padded] on the device, as PosteriorPredictive(histograms_ptr=...) filled it) against
+    `data` ([ngroups][rows / ngroups], or flat [rows]).  replicates_ptr: optional device memory
+    [nslots][rows][nchains_padded] that receives the replicated data; statistics_ptr: optional device memory
+    [nslots][2 (ngroups + 1)][nchains_padded] that receives T_obs and T_rep of every group and of all rows.  Returns a
+    PredictiveCheck.  (_lib: the library an engine has loaded, for Engine.PredictiveCheck.)"""
+    lib = _lib or _capi.load()
+    rows, ngroups = int(rows), int(ngroups)
+    d = _f64(data).ravel()
+    if d.size != rows:
+        raise ValueError("data must hold one value per row")
+    below, equal = np.zeros(max(rows, 0), dtype=_u64), np.zeros(max(rows, 0), dtype=_u64)
+    stat_counts, invalid = np.zeros((max(ngroups, 0) + 1, 3), dtype=_u64), np.zeros(1, dtype=_u64)
+    st = lib.smcmc_predictive_check(C.c_void_p(int(hist_ptr)) if hist_ptr else None, int(nslots), rows, int(nchains),
+                                    int(nchains_padded), _ptr(d), ngroups, int(seed), int(chain_offset), int(slot_offset),
+                                    int(replica), C.c_void_p(int(replicates_ptr)) if replicates_ptr else None,
+                                    C.c_void_p(int(statistics_ptr)) if statistics_ptr else None, below.ctypes.data_as(_up),
+                                    equal.ctypes.data_as(_up), stat_counts.ctypes.data_as(_up), invalid.ctypes.data_as(_up),
+                                    C.c_void_p(int(stream)))
+    if st != _capi.OK:
+        raise SmcmcError(st, lib.smcmc_event_sample_last_error().decode() or lib.smcmc_status_string(st).decode())
+    return PredictiveCheck(d.reshape(ngroups, rows // ngroups), below, equal, stat_counts, invalid[0], names)
+
+
 _SIGN, _ONES = _u64(0x8000000000000000), _u64(0xFFFFFFFFFFFFFFFF)
 
 
