@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstddef>
 #include <string>
 #include <vector>
@@ -113,6 +114,24 @@ inline int pick_dp(int dim, int like) {
     for (int i = 0; i < kNumDP; ++i)
         if (dim <= kDPList[i] && (!stress_likelihood(like) || kDPList[i] == 31 || kDPList[i] == 63)) return kDPList[i];
     return -1;
+}
+
+// A kernel whose workgroup takes more dynamic LDS than the default limit (the headline step kernels: StepWorkgroupLds of
+// smcmc_step_deal.h) has the limit raised before its first launch.  The attribute belongs to the function on one device,
+// so it is set once per call site (`Site`: one tag type per kernel, which the launcher's template gives for nothing) and
+// device; a second thread that gets there at the same time sets it again, to the same value.
+template <typename Site>
+hipError_t raise_dynamic_lds_once(const void* kernel, int bytes) {
+    constexpr int kMaxDevices = 64;
+    static std::atomic<bool> done[kMaxDevices];
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return e;
+    const bool tracked = device >= 0 && device < kMaxDevices;
+    if (tracked && done[device].load(std::memory_order_acquire)) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess && tracked) done[device].store(true, std::memory_order_release);
+    return e;
 }
 
 template <typename T>

@@ -1,6 +1,9 @@
 // smcmc_inst.hip -- explicit instantiations of the step kernels for one
 // (register-array size, likelihood) pair; built once per
 // -DSMCMC_DP=<n> -DSMCMC_LIKE=<k> (see root-simple-mcmc_amd/build.py).
+#include <utility>
+
+#include "smcmc_host.hpp"
 #include "smcmc_kernels.hip.h"
 #include "smcmc_vaat_kernel.hip.h"
 
@@ -22,6 +25,16 @@ static hipError_t go(const StepParams& p, hipStream_t s) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kernel, dim3(p.npad / kWave), dim3(kWave), (size_t)p.like_lds_bytes, s, p);
+        return hipGetLastError();
+    }
+    if constexpr (kStepHeadline<DP, LIKE, EXACT, FULLU, SPECIAL>) {
+        // one workgroup of kStepWaves wavefronts per CU, chain group kStepWaves b + w in wavefront w of block b; its LDS
+        // (StepWorkgroupLds: more than the default limit) is dynamic, the limit raised once per function and device
+        auto kernel = step_kernel<DP, LIKE, EXACT, FULLU, MOM, SPECIAL>;
+        constexpr int lds = StepWorkgroupLds<DP, MOM>::TOTAL;
+        const hipError_t e = raise_dynamic_lds_once<std::integer_sequence<int, DP, LIKE, EXACT, FULLU, MOM, SPECIAL>>(reinterpret_cast<const void*>(kernel), lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(step_blocks_for(p.npad / kWave)), dim3(kStepWaves * kWave), (size_t)lds, s, p);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(HIP_KERNEL_NAME(step_kernel<DP, LIKE, EXACT, FULLU, MOM, SPECIAL>), dim3(p.npad / kWave),

@@ -1,7 +1,7 @@
 // smcmc_kernels.hip.h -- gfx950 kernels of the many-chain Metropolis step.
 //
 // One chain per lane, one 64-chain group per wavefront, one wavefront per
-// workgroup.  A launch advances every chain by `nsteps` calls of
+// workgroup (the headline's instantiations: four, SHARED in step_kernel).  A launch advances every chain by `nsteps` calls of
 // sMCMC::TSimpleMCMC::Step() (reference TSimpleMCMC.H:370-496) without touching
 // HBM between the steps: the accepted point lives in LDS as x[dim][lane]
 // (conflict-free column per lane), the proposal in registers.
@@ -84,10 +84,12 @@ struct NormalTables { f64x2 le, ae; };
 // a compiler instruction that touches a register with an assembly read in flight.
 template <int DP>
 constexpr bool kAsmReads = DP >= 47;
-template <bool ASM>
+// LSH, ASH: log2 of the bytes from an entry to the next (4: one copy of a table; the headline kernels' replicated tables,
+// NormalTableLayout, have the lane's copy in lt_base / at_base and a wider stride: the same shift-and-add)
+template <bool ASM, int LSH = 4, int ASH = 4>
 __device__ __forceinline__ NormalTables normal_tables_fetch(uint32_t w0, uint32_t w1, uint32_t lt_base, uint32_t at_base) {
     NormalTables t;
-    const uint32_t la = lt_base + 16u * smcmc_normal_log_index(w0), aa = at_base + 16u * smcmc_normal_angle_index_halfcircle(w1);
+    const uint32_t la = lt_base + (smcmc_normal_log_index(w0) << LSH), aa = at_base + (smcmc_normal_angle_index_halfcircle(w1) << ASH);
     if constexpr (ASM) {
         asm volatile("ds_read_b128 %0, %1" : "=v"(t.le) : "v"(la));
         asm volatile("ds_read_b128 %0, %1" : "=v"(t.ae) : "v"(aa));
@@ -719,8 +721,16 @@ __device__ __forceinline__ double quadform_csr(const Point& point, const QuadCsr
     return logl;
 }
 
+// The headline's two instantiations (D = 50 family, iso-Gaussian, reference order, triangular decomposition, no uniform
+// dimensions / scan; with and without the moment fold).  They run as ONE workgroup of kStepWaves wavefronts per CU
+// (StepWorkgroupLds of smcmc_step_deal.h; step_launch_shape below is the host's side of it), every other instantiation
+// as one wavefront per workgroup.
+template <int DP, int LIKE, bool EXACT, bool FULLU, bool SPECIAL>
+constexpr bool kStepHeadline = EXACT && !FULLU && !SPECIAL && DP == 50 && LIKE == SMCMC_LIKE_ISO_GAUSS;
+
 template <int DP, int LIKE, bool EXACT, bool FULLU, bool MOMENTS, bool SPECIAL>
-__global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
+__global__ void __launch_bounds__((kStepHeadline<DP, LIKE, EXACT, FULLU, SPECIAL> ? kStepWaves * kWave : kWave),
+                                  (kStepHeadline<DP, LIKE, EXACT, FULLU, SPECIAL> ? 1 : 2)) step_kernel(const StepParams p) {
     constexpr int T = Geo<DP>::T;
     constexpr int NT = Geo<DP>::NT;
     constexpr int NB = Geo<DP>::NB;
@@ -728,7 +738,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     // The headline's two instantiations (D = 50 family, iso-Gaussian, reference order, triangular decomposition, no
     // uniform dimensions / scan; with and without the moment fold): what was measured on them alone is theirs alone, and
     // every other instantiation keeps its code instruction for instruction.
-    constexpr bool HEADLINE = EXACT && !FULLU && !SPECIAL && DP == 50 && LIKE == SMCMC_LIKE_ISO_GAUSS;
+    constexpr bool HEADLINE = kStepHeadline<DP, LIKE, EXACT, FULLU, SPECIAL>;
     // PAIRS: the accepted point in row pairs (XLayout): reload, StepRMS batch and commit are 16-byte accesses on one base
     // address.  FIXED_AW: the accept word taken from the one Philox block that holds it for every dimension the family
     // serves (AcceptBlock).  A dimension outside that range does not reach this kernel: the engine launches family
@@ -744,9 +754,30 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     // With the fold only: the other image has no such row.
     constexpr bool ZROW = HEADLINE && MOMENTS;
     static_assert(!ZROW || XL::ZERO_ROW == DP + 1, "the ones row's partner is the zero row");
-    __shared__ alignas(PAIRS ? 16 : 8) double xs[XL::DOUBLES];   // accepted point, x[row][lane]
-    __shared__ __attribute__((aligned(16))) double us[UL::SIZE];   // decomposition, every lane reads the same word
-    __shared__ __attribute__((aligned(16))) double ntab[384];      // tables of the normal transform: log [64][2], angle over the half circle [128][2]
+    // SHARED: one workgroup of kStepWaves wavefronts per CU.  Wavefront w of block b is chain group kStepWaves b + w and
+    // has an image of the accepted point of its own, which no other wavefront touches: its LDS operations on it execute
+    // in issue order, so what BOUNDARY (below) says of the lone wavefront holds for it.  The decomposition and the
+    // tables of the normal transform are held ONCE, staged by all the threads in front of the one barrier of the kernel;
+    // the LDS that frees holds the tables in copies, so that a gather cannot conflict (NormalTableLayout;
+    // profiles/step_shared_tables_notes.md).  A wavefront past the last group stages, reaches the barrier and ends.
+    constexpr bool SHARED = HEADLINE;
+    typedef StepWorkgroupLds<DP, MOMENTS> WL;
+    static_assert(!SHARED || (PAIRS && WL::FITS && WL::IMAGE_BYTES == XL::BYTES), "the wavefronts' images lie end to end, within the CU's LDS");
+    __shared__ alignas(PAIRS ? 16 : 8) double xs_own[SHARED ? 2 : XL::DOUBLES];   // accepted point, x[row][lane]
+    __shared__ __attribute__((aligned(16))) double us_own[SHARED ? 2 : UL::SIZE];   // decomposition, every lane reads the same word
+    __shared__ __attribute__((aligned(16))) double ntab_own[SHARED ? 2 : 384];      // tables of the normal transform: log [64][2], angle over the half circle [128][2]
+    constexpr int NTHREADS = SHARED ? kStepWaves * kWave : kWave;
+    int wave = 0;
+    if constexpr (SHARED) wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    double* xs = xs_own;
+    double* us = us_own;
+    double* ntab = ntab_own;
+    if constexpr (SHARED) {
+        extern __shared__ __attribute__((aligned(16))) double wg_lds[];
+        xs = wg_lds + (WL::IMAGE_BYTES / 8) * wave;
+        us = wg_lds + WL::US / 8;
+        ntab = wg_lds + WL::LOG / 8;
+    }
 
     // SMCMC_LIKE_EVENT_SAMPLE: the lanes' histograms, hist[bin][lane] (event_sample_loglike), in dynamic LDS
     double* es_hist = nullptr;
@@ -756,10 +787,15 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     }
     (void)es_hist;
 
-    const int lane = threadIdx.x;
-    const int group = blockIdx.x;
+    const int lane = SHARED ? (int)(threadIdx.x & (kWave - 1)) : (int)threadIdx.x;
+    // SHARED: a wavefront past the last group (`live` false, wave-uniform) takes the last group's place in every address
+    // it forms, so that all it reads exists; it is idle in every lane, runs no step and stores nothing
+    const int ngroups = p.npad / kWave;
+    const bool live = !SHARED || step_group_of((int)blockIdx.x, wave) < ngroups;
+    const int group = !SHARED ? (int)blockIdx.x : live ? step_group_of((int)blockIdx.x, wave) : ngroups - 1;
+    const int nsteps = live ? p.nsteps : 0;
     const int chain = group * kWave + lane;
-    const bool active = chain < p.nchains;
+    const bool active = live && chain < p.nchains;
     const int D = p.dim;
     const size_t NP = (size_t)p.npad;
     const uint32_t gid = p.chain_offset + (uint32_t)chain;
@@ -820,24 +856,53 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     int last_accept = li[SMCMC_LANE_LAST_ACCEPT * NP];
 
     // stage U: lane-strided copy of each kept row segment
+    const int tid = (int)threadIdx.x;   // (the staging is the workgroup's: SHARED, all its wavefronts')
 #pragma unroll
     for (int i = 0; i < DP; ++i) {
-        for (int k = lane; k < UL::len(i); k += kWave) {
+        for (int k = tid; k < UL::len(i); k += NTHREADS) {
             const int j = UL::j0(i) + k;
             us[UL::off(i) + k] = (j < DP) ? p.U[i * DP + j] : 0.0;
         }
     }
 
-    for (int k = lane; k < 128; k += kWave) ntab[k] = smcmc_log_table_dev[k];
-    for (int k = lane; k < 64; k += kWave) {
-        // entry 64 + k is entry k turned by pi / 2: (-sin, cos) (SMCMC_NORMAL_PAIR_BODY_HALFCIRCLE)
-        const double c = smcmc_angle_table_dev[2 * k], sn = smcmc_angle_table_dev[2 * k + 1];
-        ntab[128 + 2 * k] = c;
-        ntab[128 + 2 * k + 1] = sn;
-        ntab[128 + 128 + 2 * k] = -sn;
-        ntab[128 + 128 + 2 * k + 1] = c;
+    uint32_t ltab, atab;   // LDS byte addresses the gathers start from
+    if constexpr (SHARED) {
+        // slot s of a table (16 bytes at NormalTableLayout::slot_offset(s)) holds entry slot_entry(s) of the source
+        typedef LogTableLayout LT;
+        typedef AngleTableLayout AT;
+        double* const atb = ntab + (WL::ANGLE - WL::LOG) / 8;
+        for (int s = tid; s < LT::SLOTS; s += NTHREADS) {
+            const int k = LT::slot_entry(s);
+            f64x2 v;
+            v[0] = smcmc_log_table_dev[2 * k];
+            v[1] = smcmc_log_table_dev[2 * k + 1];
+            *(f64x2*)(ntab + LT::slot_offset(s) / 8) = v;
+        }
+        for (int s = tid; s < AT::SLOTS; s += NTHREADS) {
+            // entry 64 + k is entry k turned by pi / 2: (-sin, cos) (SMCMC_NORMAL_PAIR_BODY_HALFCIRCLE)
+            const int e = AT::slot_entry(s), k = e & 63;
+            const double c = smcmc_angle_table_dev[2 * k], sn = smcmc_angle_table_dev[2 * k + 1];
+            f64x2 v;
+            v[0] = (e < 64) ? c : -sn;
+            v[1] = (e < 64) ? sn : c;
+            *(f64x2*)(atb + AT::slot_offset(s) / 8) = v;
+        }
+        ltab = (uint32_t)(uintptr_t)(lds_cptr_f64)ntab + (uint32_t)LT::lane_offset(lane);
+        atab = (uint32_t)(uintptr_t)(lds_cptr_f64)atb + (uint32_t)AT::lane_offset(lane);
+    } else {
+        for (int k = lane; k < 128; k += kWave) ntab[k] = smcmc_log_table_dev[k];
+        for (int k = lane; k < 64; k += kWave) {
+            // entry 64 + k is entry k turned by pi / 2: (-sin, cos) (SMCMC_NORMAL_PAIR_BODY_HALFCIRCLE)
+            const double c = smcmc_angle_table_dev[2 * k], sn = smcmc_angle_table_dev[2 * k + 1];
+            ntab[128 + 2 * k] = c;
+            ntab[128 + 2 * k + 1] = sn;
+            ntab[128 + 128 + 2 * k] = -sn;
+            ntab[128 + 128 + 2 * k + 1] = c;
+        }
+        ltab = (uint32_t)(uintptr_t)(lds_cptr_f64)ntab;
+        atab = ltab + 128u * 8u;
     }
-    const uint32_t ltab = (uint32_t)(uintptr_t)(lds_cptr_f64)ntab, atab = ltab + 128u * 8u;   // LDS byte addresses
+    constexpr int LSH = SHARED ? LogTableLayout::SHIFT : 4, ASH = SHARED ? AngleTableLayout::SHIFT : 4;
 
     constexpr bool STRIP = MOMENTS && Geo<DP>::STRIP;
     constexpr int NT16 = Geo<DP>::NT16;
@@ -1047,8 +1112,8 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         }
         SMCMC_PROF_MARK(PROF_COMMIT);
         if constexpr (BOUNDARY) x0 = take ? xp[0] : x0;
-        // The next step's operand reads (inline assembly) must see this step's accepts.  The workgroup is ONE wavefront
-        // and its LDS operations execute in issue order: all that is needed is that the compiler keeps the order, not a
+        // The next step's operand reads (inline assembly) must see this step's accepts.  The image is ONE wavefront's
+        // (SHARED: its own among the workgroup's) and its LDS operations execute in issue order: all that is needed is that the compiler keeps the order, not a
         // barrier and not a wait for the writes -- they drain under the next step's scalar half.  The compiler keeps it
         // because this statement clobbers memory and because the operand reads (fetch_operands, fetch_operand) are
         // `asm volatile`, which are never reordered among each other: those reads must stay volatile.
@@ -1064,7 +1129,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     };
 
     int s0 = 0;
-    if (p.has_forced && p.nsteps > 0) {
+    if (p.has_forced && nsteps > 0) {
         // ForceStep (TSimpleMCMC.H:671-678): the proposal is the forced point and the
         // proposal state is not updated
 #pragma unroll
@@ -1079,7 +1144,7 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         // with that dimension redrawn; the proposal state is not updated
         const uint32_t sd = (uint32_t)p.scan_dim;
 #pragma nounroll
-        for (int s = s0; s < p.nsteps; ++s) {
+        for (int s = s0; s < nsteps; ++s) {
             const uint64_t step = (uint64_t)(p.step0 + (uint32_t)s + 1u);
             const smcmc_u32x4 sblk = smcmc_draw_block(p.seed, gid, step, sd >> 2, SMCMC_STREAM_STEP);
             double val;
@@ -1095,10 +1160,10 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
             const smcmc_u32x4 ablk = smcmc_draw_block(p.seed, gid, step, aw >> 2, SMCMC_STREAM_STEP);
             finish_step(s, smcmc_select_word(ablk, aw & 3u));
         }
-        s0 = p.nsteps;
+        s0 = nsteps;
     }
 
-    for (int s = s0; s < p.nsteps; ++s) {
+    for (int s = s0; s < nsteps; ++s) {
         const uint64_t step = (uint64_t)(p.step0 + (uint32_t)s + 1u);   // ++fTotalSteps, :376
         SMCMC_PROF_MARK(PROF_LOOP);
         SMCMC_PROF_MARK(PROF_STAMP);
@@ -1179,9 +1244,9 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
         auto draw_and_fetch = [&](auto bn) {
             constexpr int b1 = decltype(bn)::value;
             blks[b1 & 1] = smcmc_draw_block(p.seed, gid, step, (uint32_t)b1, SMCMC_STREAM_STEP);
-            tabs[b1 & 1][0] = normal_tables_fetch<kAsmReads<DP>>(blks[b1 & 1].v[0], blks[b1 & 1].v[1], ltab, atab);
+            tabs[b1 & 1][0] = normal_tables_fetch<kAsmReads<DP>, LSH, ASH>(blks[b1 & 1].v[0], blks[b1 & 1].v[1], ltab, atab);
             if constexpr (4 * b1 + 2 < DP)
-                tabs[b1 & 1][1] = normal_tables_fetch<kAsmReads<DP>>(blks[b1 & 1].v[2], blks[b1 & 1].v[3], ltab, atab);
+                tabs[b1 & 1][1] = normal_tables_fetch<kAsmReads<DP>, LSH, ASH>(blks[b1 & 1].v[2], blks[b1 & 1].v[3], ltab, atab);
         };
         if constexpr (PIPE) draw_and_fetch(std::integral_constant<int, 0>{});
         SMCMC_PROF_MARK(PROF_TOP);
@@ -1389,14 +1454,16 @@ __global__ void __launch_bounds__(kWave, 2) step_kernel(const StepParams p) {
     }
 #endif
     if constexpr (MOMENTS) {
+        if (live) {
 #pragma unroll
-        for (int t = 0; t < NT16; ++t)
+            for (int t = 0; t < NT16; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                p.gacc[(((size_t)group * NT + t) * 4 + r) * kWave + lane] = acc[t][r];
-        if constexpr (STRIP) {
+                for (int r = 0; r < 4; ++r)
+                    p.gacc[(((size_t)group * NT + t) * 4 + r) * kWave + lane] = acc[t][r];
+            if constexpr (STRIP) {
 #pragma unroll
-            for (int t = 0; t < T; ++t) p.gacc[(((size_t)group * NT + NT16 + t) * 4) * kWave + lane] = accs[t];
+                for (int t = 0; t < T; ++t) p.gacc[(((size_t)group * NT + NT16 + t) * 4) * kWave + lane] = accs[t];
+            }
         }
     }
     if (active) {

@@ -86,6 +86,51 @@ struct XLayout {
     static constexpr int ZERO_ROW = (PAIRS && MOMENTS && HELD > ROWS) ? ROWS : -1;
 };
 
+// LDS image of one table of the normal transform (64 or 128 entries of two doubles, gathered by ds_read_b128 at an index
+// that differs from lane to lane and comes from a random word), COPIES times: copy c of entry k at byte
+// k * STRIDE + 16 c, and lane l reads copy l & (COPIES - 1).  LDS has 64 banks of four bytes and serves a 16-byte read
+// sixteen lanes at a time.  With 16 copies an entry's copies cover the 64 banks once and a lane's banks are
+// 4 (l & 15) .. + 3 whatever its entry: any sixteen lanes with sixteen different l & 15 -- the contiguous quarters and
+// the groups the hardware forms (tests/test_step_rowpairs_layout_cpu.py) -- read disjoint banks for ANY indices.  With 8
+// copies two lanes of such a group share a copy, and only those two can meet in a bank: two-way at the most.  With one
+// copy (the layout every other kernel keeps) any two lanes with different entries sixteen apart do.
+// The lane's part of the address, lane_offset, does not change from step to step; the gather's address is one
+// shift-and-add of the index, as it is for one copy.
+template <int ENTRIES, int COPIES>
+struct NormalTableLayout {
+    static_assert(COPIES >= 1 && COPIES <= 16 && (COPIES & (COPIES - 1)) == 0, "a power of two, at most one per bank quad");
+    static constexpr int ENTRY_BYTES = 16;
+    static constexpr int STRIDE = ENTRY_BYTES * COPIES;     // bytes from an entry to the next
+    static constexpr int SLOTS = ENTRIES * COPIES;
+    static constexpr int BYTES = SLOTS * ENTRY_BYTES;
+    static constexpr int shift() {                          // address = base + lane_offset + (index << SHIFT)
+        int s = 0;
+        while ((1 << s) < STRIDE) ++s;
+        return s;
+    }
+    static constexpr int SHIFT = shift();
+    static constexpr int copy_of(int lane) { return lane & (COPIES - 1); }
+    static constexpr int lane_offset(int lane) { return ENTRY_BYTES * copy_of(lane); }
+    static constexpr int offset(int copy, int k) { return k * STRIDE + ENTRY_BYTES * copy; }
+    // staging: the prologue fills slot s (16 bytes at byte 16 s), s = 0 .. SLOTS - 1, with the source table's entry
+    static constexpr int slot_offset(int s) { return ENTRY_BYTES * s; }
+    static constexpr int slot_entry(int s) { return s / COPIES; }
+};
+
+// The copies each table gets in the headline kernels' workgroup (StepWorkgroupLds).  Sixteen of both do not fit beside
+// four images of the accepted point.  Two lanes that share a copy meet in a bank unless they drew the same entry, one
+// chance in 64 or in 128: either table with eight copies conflicts two-way in practically every pass, the counter cannot
+// tell the two splits apart, and the listing and the clock decided (profiles/step_shared_tables_notes.md, which built
+// the other splits with -D).
+#ifndef SMCMC_NTAB_LOG_COPIES
+#define SMCMC_NTAB_LOG_COPIES 8
+#endif
+#ifndef SMCMC_NTAB_ANGLE_COPIES
+#define SMCMC_NTAB_ANGLE_COPIES 16
+#endif
+typedef NormalTableLayout<64, SMCMC_NTAB_LOG_COPIES> LogTableLayout;        // log table
+typedef NormalTableLayout<128, SMCMC_NTAB_ANGLE_COPIES> AngleTableLayout;   // angle table over the half circle
+
 // LDS image of the decomposition: row i keeps columns j0(i)..DP-1 (j0 = i rounded
 // down to even for the triangular factor, 0 for a full matrix), padded to an even
 // length so that every row starts 16-byte aligned (ds_read_b128 = two columns).
@@ -100,6 +145,27 @@ struct ULayout {
                      : i * DPE - ((i & 1) ? 2 * (i / 2) * (i / 2) : 2 * (i / 2) * (i / 2 - 1));
     }
     static constexpr int SIZE = off(DP);
+};
+
+// LDS of the headline kernels' workgroup: kStepWaves wavefronts (chain groups kStepWaves b + w of block b), each with an
+// image of the accepted point of its own (row pairs), behind them ONE decomposition and ONE set of tables.  More than
+// 64 KB: dynamic shared memory, all offsets in bytes from its start.
+constexpr int kStepWaves = 4;
+constexpr int kLdsPerCU = 160 * 1024;
+constexpr int step_group_of(int block, int wave) { return kStepWaves * block + wave; }
+constexpr int step_blocks_for(int groups) { return (groups + kStepWaves - 1) / kStepWaves; }
+template <int DP, bool MOMENTS>
+struct StepWorkgroupLds {
+    typedef XLayout<DP, MOMENTS, true> XL;
+    static constexpr int round16(int n) { return (n + 15) / 16 * 16; }
+    static constexpr int IMAGE_BYTES = round16(XL::BYTES);
+    static constexpr int image(int wave) { return wave * IMAGE_BYTES; }
+    static constexpr int US = kStepWaves * IMAGE_BYTES;
+    static constexpr int US_BYTES = round16(8 * ULayout<DP, false>::SIZE);
+    static constexpr int LOG = US + US_BYTES;
+    static constexpr int ANGLE = LOG + LogTableLayout::BYTES;
+    static constexpr int TOTAL = ANGLE + AngleTableLayout::BYTES;
+    static constexpr bool FITS = TOTAL <= kLdsPerCU;   // one workgroup per CU: its LDS is the CU's
 };
 
 // The pieces (row, first column) that the rows of Philox block B contribute, in
